@@ -21,9 +21,19 @@ Unix-domain-socket rendezvous (speaker-recognition_amd/rendezvous.py): nothing h
 (`--rendezvous gloo` keeps torch.distributed as the carrier).  Every rank pins itself to the cores of its
 GPU's NUMA node.  At N > 1 the line also carries the weak-scaling efficiency against rank 0 running the same
 step ALONE in the same run, the configs[3] strong-scaling split, and the ONE-process path over the N devices
-(sr_multi_predict_pcm from page-locked host PCM).
+(sr_multi_predict_pcm from page-locked host PCM) -- these three with `--full` only.
 
-Beside the headline the full record (bench_blocks.json) carries a `configs` block (N = 1 only, outside the timed region):
+A plain run (no `--full`) does what the headline needs and nothing else: it sets the workload up, warms up, times the
+`--steps` steps, writes the last step's results if `--dump-outputs DIR` is given, and prints the line.  Its roofline is the
+scoring kernel's HIP-event time in the timed steps; the HBM copy ceiling, the matrix-pipe probes (`clock`), the PMC traffic passes,
+the CPU baseline, the parity samples and every secondary block below are `--full` only.
+
+`--dump-outputs DIR`: what the timed path handed its caller in the last timed step -- the per-utterance sums [U, S] and the argmax
+[U] -- as DIR/sums.npy and DIR/argmax.npy in float64 (suffix _rank<r> at N > 1), at most 64 MB in all; where all utterances do not
+fit, a fixed seeded sample of them (DIR/utterance_index.npy says which).  The inputs are seeded: the same arguments give the same
+inputs in every run, so two builds can be compared output for output.
+
+With `--full` the full record (bench_blocks.json) also carries a `configs` block (N = 1 only, outside the timed region):
 configs[0] end to end through the CLI surface with the reference's C++ + numpy MFCC timed beside it, configs[1], one rank's
 configs[3] shard in full, configs[4] latencies, the 256-mixture x 39-dim point of BASELINE.json's north_star on the matrix
 cores and on north_star's literal vector-ALU path, the feature stage in both precision modes, the headline from HOST PCM,
@@ -32,7 +42,7 @@ EM benchmark, the legacy ABI's per-speaker loop --
 each with its own roofline and a parity sample checked by oracle/parity_check.py on all host cores (per frame on the device's
 own features AND end to end from PCM against the float64 feature oracle).
 
-oracle/ is never imported by this process: the CPU baseline (oracle/cpu_baseline.py) and the parity
+oracle/ is never imported by this process: with `--full` the CPU baseline (oracle/cpu_baseline.py) and the parity
 samples (oracle/parity_check.py) run as subprocesses, outside every timed region, as checkers.
 
 Prints ONE compact JSON line (<= 1500 characters: headline + roofline + cpu_baseline + parity figures) as the LAST line of
@@ -1038,7 +1048,7 @@ def compact(result, blocks_file=None):
         "cpu_baseline": ({"error": str(cb.get("error"))[:80]} if "error" in cb else
                          {"value": _r(cb.get("value")), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
                           "sample": ("%s utt x 10.04 s, all %s models: reference C++ score_batch on Pool(%s) + f64 MFCC.py restatement"
-                                     % (e2e.get("utterances"), e2e.get("models"), cb.get("cores"))) if cb else "measured at N = 1 only"}),
+                                     % (e2e.get("utterances"), e2e.get("models"), cb.get("cores"))) if cb else "measured with --full, at N = 1 only"}),
         "parity": {"argmax_mismatches": e2e.get("argmax_mismatches"), "utt_sum_max_rel": _r(e2e.get("max_rel_sum_diff"), 3),
                    "frame_ll_from_pcm_max_rel": _r(pf.get("max_rel"), 3), "frame_ll_from_pcm_frames": pf.get("frames"),
                    "mfcc_max_abs": _r(mf.get("max_abs_diff_vs_oracle"), 3), "mfcc_mean_abs": _r(mf.get("mean_abs_diff_vs_oracle"), 3),
@@ -1093,6 +1103,26 @@ def peak_rss_mb():
     return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
 
 
+DUMP_LIMIT = 64 * 10 ** 6       # bytes of --dump-outputs, all ranks together
+
+
+def dump_outputs(d, sums, arg, rank=0, world=1):
+    """--dump-outputs: the last timed step's sums [U, S] and argmax [U] as float64 .npy files; when all U rows do not fit this
+    rank's share of DUMP_LIMIT, a fixed seeded sample of the utterances (sorted), with their indices beside them."""
+    os.makedirs(d, exist_ok=True)
+    U, S = sums.shape
+    per_row = 8 * (S + 2)                                 # sums row + argmax + utterance index
+    room = DUMP_LIMIT // max(1, world) - 4096             # (.npy headers)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    rows = None
+    if U * per_row > room:
+        rows = np.sort(np.random.default_rng(AUDIO_SEED).choice(U, max(1, room // per_row), replace=False))
+        np.save(os.path.join(d, "utterance_index%s.npy" % sfx), rows.astype(np.float64))
+    pick = (lambda a: a) if rows is None else (lambda a: a[rows])
+    np.save(os.path.join(d, "sums%s.npy" % sfx), np.ascontiguousarray(pick(sums), dtype=np.float64))
+    np.save(os.path.join(d, "argmax%s.npy" % sfx), pick(arg).astype(np.float64))
+
+
 def main():
     t_start = time.perf_counter()
     ap = argparse.ArgumentParser()
@@ -1116,7 +1146,14 @@ def main():
                          "carries the compact headline line only")
     ap.add_argument("--device-override", type=int, default=-1,
                     help="testing only: put every rank on this device (N>1 code path on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: HBM ceiling and matrix-pipe probes, PMC traffic, CPU baseline, parity "
+                         "samples, the secondary config blocks, and at N > 1 rank 0 alone, configs[3] and the one-process path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (sums, argmax) to DIR/<name>.npy in float64, <= 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
@@ -1182,7 +1219,7 @@ def main():
         step(i)
     # N > 1: rank 0 runs the same step ALONE first (the others wait), so that the line carries its own weak-scaling reference
     alone_rate = None
-    if grp is not None:
+    if grp is not None and args.full:
         barrier()
         if rank == 0:
             k = max(1, min(3, args.steps))
@@ -1200,6 +1237,8 @@ def main():
         sums, arg = step(i)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sums, arg, rank, world)
     prev = outs[args.steps & 1][0] if args.steps > 1 else None       # the step before the last
     rank_rate = n_frames * args.steps / elapsed
     if grp is not None:
@@ -1216,7 +1255,7 @@ def main():
     #      the whole 2048-mixture UBM + 1000 speakers; wall time = the slowest rank's
     strong = None
     one_process = None
-    if grp is not None and not args.no_config_blocks:
+    if grp is not None and args.full and not args.no_config_blocks:
         # (secondary blocks: whatever goes wrong in them -- on this rank or, seen as a closed connection, on another -- must not
         # take the headline down; the ranks meet again at the barrier below or not at all)
         try:
@@ -1251,11 +1290,13 @@ def main():
                 pass
         return
 
-    hbm = _lib.hbm_copy_gbps(1 << 30, 10)
-    # what the matrix pipe sustains on this box under its power cap: a kernel of v_mfma_f32_32x32x16_f16 chains only (csrc/probe.hip)
-    sustained = _lib.mfma_peak_probe(60.0)
-    # ... and on chains FED as the scoring kernel feeds them: a fresh A fragment from LDS per MFMA, random operand bits (probe mode 1)
-    streamed = _lib.mfma_streamed_probe(60.0)
+    hbm = sustained = streamed = None
+    if args.full:
+        hbm = _lib.hbm_copy_gbps(1 << 30, 10)
+        # what the matrix pipe sustains on this box under its power cap: a kernel of v_mfma_f32_32x32x16_f16 chains only (csrc/probe.hip)
+        sustained = _lib.mfma_peak_probe(60.0)
+        # ... and on chains FED as the scoring kernel feeds them: a fresh A fragment from LDS per MFMA, random operand bits (probe mode 1)
+        streamed = _lib.mfma_streamed_probe(60.0)
     kt1 = kt
     score_s = (kt1["gmm_score"]["ms_per_step"] + kt1["gmm_score_ref_prepass"]["ms_per_step"]) * 1e-3
     result = {
@@ -1303,33 +1344,34 @@ def main():
                    "last_two_steps_bit_identical": bool(np.array_equal(prev, sums)) if prev is not None else None},
     }
     rf = result["roofline"]
-    rf["sustained_mfma"] = {
-        "executed_tflops": sustained[0], "clock_mhz": sustained[1],
-        "frac_of_nominal_peak": sustained[0] / MFMA16_PEAK_TFLOPS,
-        "frac_executed_of_sustained": (rf["executed_16bit_tflops"] / sustained[0]) if rf.get("executed_16bit_tflops") and sustained[0] > 0 else None,
-        "note": "measured in this run: 12 waves per CU issuing nothing but v_mfma_f32_32x32x16_f16 for ~60 ms (sr_mfma_peak_probe). The nominal "
-                "peak assumes 2.4 GHz; under the socket power cap a matrix-only kernel holds ~1.55 GHz, so this is the ceiling any MFMA kernel "
-                "longer than a few ms has on this box; the scoring kernel's parts cost time in proportion to their energy "
-                "(profiles/r03_h2p_parts.txt). `frac` above stays algorithmic flops / nominal peak."}
-    rf["sustained_mfma_streamed"] = {
-        "executed_tflops": streamed[0], "clock_mhz": streamed[1], "frac_of_nominal_peak": streamed[0] / MFMA16_PEAK_TFLOPS,
-        "frac_executed_of_sustained": (rf["executed_16bit_tflops"] / streamed[0]) if rf.get("executed_16bit_tflops") and streamed[0] > 0 else None,
-        "note": "the same chains with every MFMA's A fragment re-read from LDS (8 KiB images of random finite fp16 bit patterns), 8 random B "
-                "fragments resident, chains of 8 links (sr_mfma_streamed_probe, ~60 ms): the matrix pipe + the LDS feed + operands whose bits "
-                "toggle, nothing else -- no LDS-DMA stream, no exponentials, no barriers.  The ceiling a kernel of the scoring kernel's shape "
-                "has on this box under its power cap; sustained_mfma above (operands held in registers for the whole launch) is a load no "
-                "real kernel presents."}
+    if sustained is not None:
+        rf["sustained_mfma"] = {
+            "executed_tflops": sustained[0], "clock_mhz": sustained[1],
+            "frac_of_nominal_peak": sustained[0] / MFMA16_PEAK_TFLOPS,
+            "frac_executed_of_sustained": (rf["executed_16bit_tflops"] / sustained[0]) if rf.get("executed_16bit_tflops") and sustained[0] > 0 else None,
+            "note": "measured in this run: 12 waves per CU issuing nothing but v_mfma_f32_32x32x16_f16 for ~60 ms (sr_mfma_peak_probe). The nominal "
+                    "peak assumes 2.4 GHz; under the socket power cap a matrix-only kernel holds ~1.55 GHz, so this is the ceiling any MFMA kernel "
+                    "longer than a few ms has on this box; the scoring kernel's parts cost time in proportion to their energy "
+                    "(profiles/r03_h2p_parts.txt). `frac` above stays algorithmic flops / nominal peak."}
+        rf["sustained_mfma_streamed"] = {
+            "executed_tflops": streamed[0], "clock_mhz": streamed[1], "frac_of_nominal_peak": streamed[0] / MFMA16_PEAK_TFLOPS,
+            "frac_executed_of_sustained": (rf["executed_16bit_tflops"] / streamed[0]) if rf.get("executed_16bit_tflops") and streamed[0] > 0 else None,
+            "note": "the same chains with every MFMA's A fragment re-read from LDS (8 KiB images of random finite fp16 bit patterns), 8 random B "
+                    "fragments resident, chains of 8 links (sr_mfma_streamed_probe, ~60 ms): the matrix pipe + the LDS feed + operands whose bits "
+                    "toggle, nothing else -- no LDS-DMA stream, no exponentials, no barriers.  The ceiling a kernel of the scoring kernel's shape "
+                    "has on this box under its power cap; sustained_mfma above (operands held in registers for the whole launch) is a load no "
+                    "real kernel presents."}
     if strong is not None:
         result["configs[3]_strong_scaling"] = strong
     if one_process is not None:
         result["one_process_all_devices"] = one_process
-    if world == 1 and not args.no_traffic:
+    if world == 1 and args.full and not args.no_traffic:
         tb, td = measure_traffic(kname.split("<")[0].split()[0], ["--utts", str(args.utts)])
         result["roofline"]["traffic"] = tb
         result["roofline"]["traffic_unit"] = "bytes per scoring pass (HBM side of L2)"
         result["roofline"]["traffic_over_algorithmic"] = (tb / result["roofline"]["algorithmic_bytes"]) if tb else None
         result["roofline"]["traffic_note"] = td
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         tmp = tempfile.mkdtemp()
         sample_models = [0] + list(range(1, 12))           # the UBM + 11 speakers: bounded CPU work
         files = []
@@ -1394,7 +1436,7 @@ def main():
                 single["kind"] = cb["kind"]
                 single["pool_leg"] = pool
                 result["cpu_baseline"] = single
-    if world == 1 and not args.no_config_blocks:
+    if world == 1 and args.full and not args.no_config_blocks:
         blocks, preq = {}, {}
         # headline parity for the pool of host cores: the first 200 utterances x ALL 201 models -- per frame on their own
         # batch (features = the device's own MFCC output) and per utterance against the sums of the timed 10 M-frame pass

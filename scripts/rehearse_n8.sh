@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out; mkdir -p $O
 free -g | head -2 > $O/r06_n8_wall.txt; nproc >> $O/r06_n8_wall.txt
-ARGS="--gpus 8 --device-override 0 --steps 3 --warmup 1 --no-cpu-baseline --blocks-out $O/r06_n8_stacked.json"
+ARGS="--full --gpus 8 --device-override 0 --steps 3 --warmup 1 --no-cpu-baseline --blocks-out $O/r06_n8_stacked.json"
 if [ "$1" = "torchrun" ]; then
   CMD="python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py $ARGS"
 else

@@ -77,3 +77,26 @@ def test_compact_line_names_the_run_it_describes():
     text = bench.compact(rec)
     assert len(text) <= bench.COMPACT_LIMIT
     json.loads(text)
+
+
+def test_dump_outputs_are_float_and_within_budget(tmp_path):
+    """--dump-outputs: the last step's sums / argmax as float32/64 .npy files, <= 64 MB in all; a larger output becomes the same
+    seeded sample of utterances in every run"""
+    import numpy as np
+    bench = _bench()
+    rng = np.random.default_rng(1)
+    sums, arg = rng.standard_normal((300, 201)), rng.integers(0, 201, 300).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "small"), sums, arg)
+    assert np.array_equal(np.load(tmp_path / "small" / "sums.npy"), sums)
+    assert np.array_equal(np.load(tmp_path / "small" / "argmax.npy"), arg) and np.load(tmp_path / "small" / "argmax.npy").dtype == np.float64
+    big = np.broadcast_to(np.arange(60000, dtype=np.float64)[:, None], (60000, 201))       # 96 MB of sums
+    barg = np.arange(60000, dtype=np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, barg)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["argmax.npy", "sums.npy", "utterance_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT <= 64 * 10 ** 6
+    idx = np.load(tmp_path / "a" / "utterance_index.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "sums.npy")[:, 0], idx) and np.array_equal(np.load(tmp_path / "a" / "argmax.npy"), idx)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

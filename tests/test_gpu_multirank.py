@@ -95,7 +95,7 @@ def test_ranks_on_the_device_equal_one_process(built_lib, backend, world):
     assert np.all(arg1 >= 0)
 
 
-BENCH_ARGS = ["--gpus", "2", "--device-override", "0", "--utts", "200", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+BENCH_ARGS = ["--full", "--gpus", "2", "--device-override", "0", "--utts", "200", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
               "--cfg3-total-frames", "400000"]
 
 
