@@ -326,6 +326,46 @@ int sr_last_em_stats_engine(void);
  * src/gmm/src/random.hh:22-25, gmm.hh:44, kmeansII.cc:94,133; csrc/kmeans_init.hip).  For checks. */
 int sr_reference_rand_sample(int *out, int count);
 
+/* ---- Full-covariance GMMs (csrc/gmm_full.hip): scikit-learn's GaussianMixture(covariance_type='full') ----
+ * Layout as sklearn's, so parameters convert 1:1: weights[K], means[K][D], precisions_cholesky[K][D][D] (upper triangular P_k,
+ * precision = P_k P_k^T), float64, row-major.  1 <= D <= 64, any K >= 1.  lp_k(x) = ln w_k + sum_i ln P_k[i][i] - D/2 ln 2 pi
+ * - 1/2 |P_k^T (x - mu_k)|^2; a frame's log-likelihood is the exact log-sum-exp over k (no clamp).  Every call returns a status
+ * (0 ok, -1 error: sr_last_error()) or a handle (NULL on error).  In a process forked after GPU initialisation the compute calls
+ * fail (no helper-process proxy for these). */
+typedef struct SRFullGMM SRFullGMM;
+typedef struct SRFullSet SRFullSet;
+struct SRFullFitParams {
+    double tol;             /* stop when |lower_bound - previous| < tol */
+    double reg_covar;       /* added to every covariance's diagonal */
+    int max_iter;           /* >= 1 */
+    int init_given;         /* 1: the handle's parameters are the initialisation (weights_init / means_init / precisions_init);
+                               0: one-hot responsibilities from the library's seeded k-means (kmeans_init.hip) + one M-step */
+    long long seed;         /* the k-means stream's seed (>= 0) */
+};
+struct SRFullFitStats {
+    int n_iter;
+    int converged;
+    double lower_bound;     /* mean log-likelihood of the last E-step */
+};
+/* A model of K mixtures in D dims; weights / means / prec_chol may all be NULL (no parameters yet: fit it with init_given 0). */
+SRFullGMM *sr_fullgmm_create(int K, int D, const double *weights, const double *means, const double *prec_chol);
+/* EM in float64 on the device, as GaussianMixture.fit with n_init = 1.  X: [n][D] float64.  A component whose covariance's
+ * Cholesky meets a pivot <= 0 fails the fit with scikit-learn's message ("Fitting the mixture model failed because some
+ * components have ill-defined empirical covariance ..."); the handle keeps its previous parameters then. */
+int sr_fullgmm_fit(SRFullGMM *g, const double *X, int64_t n, int D, const struct SRFullFitParams *params, struct SRFullFitStats *out);
+/* K and D of a handle; 1 when it has parameters, 0 when not, -1 on error.  Either pointer may be NULL. */
+int sr_fullgmm_info(SRFullGMM *g, int *K, int *D);
+/* Copies the parameters out; any pointer may be NULL.  covariances: the last M-step's (zeros for a model built from arrays). */
+int sr_fullgmm_get(SRFullGMM *g, double *weights, double *means, double *covariances, double *prec_chol);
+void sr_fullgmm_free(SRFullGMM *g);
+/* S >= 1 trained models of one dimension packed and uploaded once to the calling thread's device. */
+SRFullSet *sr_fullset_create(SRFullGMM *const *models, int S);
+/* Every utterance of a feature batch (dim == the set's D) against every model in one pass: sums_out [U][S] float64 per-utterance
+ * totals added in a fixed order (the bits depend neither on the batch's other utterances nor on the position), argmax_out [U]
+ * (first maximum wins), frame_ll_out [S][n_rows] fp32 or NULL.  sums_out / argmax_out may be NULL. */
+int sr_fullset_score_batch(SRFullSet *set, SRBatch *batch, double *sums_out, int *argmax_out, float *frame_ll_out);
+void sr_fullset_free(SRFullSet *set);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ EXT_SYMBOLS = [
     "sr_multi_create", "sr_multi_free", "sr_multi_slots", "sr_multi_slot_device", "sr_multi_predict_pcm",
     "sr_hbm_copy_gbps", "sr_reference_rand_sample", "sr_flush_stats", "sr_host_register", "sr_host_unregister",
     "sr_mfma_peak_probe", "sr_mfma_streamed_probe", "sr_kmeans_fast_stats",
+    "sr_fullgmm_create", "sr_fullgmm_fit", "sr_fullgmm_info", "sr_fullgmm_get", "sr_fullgmm_free", "sr_fullset_create",
+    "sr_fullset_score_batch", "sr_fullset_free",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -45,6 +47,17 @@ class Parameter(C.Structure):
     _fields_ = [("nr_instance", C.c_int), ("nr_dim", C.c_int), ("nr_mixture", C.c_int),
                 ("min_covar", C.c_double), ("threshold", C.c_double), ("nr_iteration", C.c_int),
                 ("init_with_kmeans", C.c_int), ("concurrency", C.c_int), ("verbosity", C.c_int)]
+
+
+class FullFitParams(C.Structure):
+    """struct SRFullFitParams (include/pygmm_hip.h)."""
+    _fields_ = [("tol", C.c_double), ("reg_covar", C.c_double), ("max_iter", C.c_int), ("init_given", C.c_int),
+                ("seed", C.c_longlong)]
+
+
+class FullFitStats(C.Structure):
+    """struct SRFullFitStats (include/pygmm_hip.h)."""
+    _fields_ = [("n_iter", C.c_int), ("converged", C.c_int), ("lower_bound", C.c_double)]
 
 
 class SRError(RuntimeError):
@@ -151,6 +164,14 @@ def lib():
         "sr_multi_slot_device": (i32, [vp, i32]),
         "sr_multi_predict_pcm": (i32, [vp, C.POINTER(C.c_int16), C.POINTER(i64), i32, i32, dp, C.POINTER(i32), dp, i32]),
         "sr_hbm_copy_gbps": (i32, [C.c_size_t, i32, dp]),
+        "sr_fullgmm_create": (vp, [i32, i32, dp, dp, dp]),
+        "sr_fullgmm_fit": (i32, [vp, dp, i64, i32, C.POINTER(FullFitParams), C.POINTER(FullFitStats)]),
+        "sr_fullgmm_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "sr_fullgmm_get": (i32, [vp, dp, dp, dp, dp]),
+        "sr_fullgmm_free": (None, [vp]),
+        "sr_fullset_create": (vp, [C.POINTER(vp), i32]),
+        "sr_fullset_score_batch": (i32, [vp, vp, dp, C.POINTER(i32), fp]),
+        "sr_fullset_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -2,6 +2,7 @@
 
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/ ./person*" -m model.out
     speaker-recognition.py -t predict -i "./*.wav" -m model.out
+    speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --covariance full
 
 Wav files in each input directory are labelled with the directory's basename; wildcard inputs
 must be quoted (they go to glob).  Extra options (not in the reference) select the feature
@@ -40,6 +41,9 @@ def get_args(argv=None):
     parser.add_argument("--deltas", type=int, default=0, choices=[0, 1, 2], help="append delta orders")
     parser.add_argument("--no-lpc", action="store_true", help="MFCC half of mix_feature only (13 dims)")
     parser.add_argument("--seed", type=int, default=-1, help="EM initialisation seed (-1: random)")
+    parser.add_argument("--covariance", choices=["diag", "full"], default="diag",
+                        help="enroll: speaker model covariance (diag: the C++ back-end's models; full: the reference CLI's "
+                             "scikit-learn GaussianMixture, skgmm.py)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--gpus", type=int, default=1,
                         help="predict: shard the input files over this many GPUs from one process (0 = all visible)")
@@ -108,7 +112,7 @@ def _make_interface(args):
         fk["FFT_SIZE"] = args.fft_size
     return ModelInterface(gmm_order=args.mixtures, feature_kwargs=fk, diff=args.deltas > 0,
                           nd=max(1, args.deltas), lpc=not args.no_lpc and args.deltas == 0,
-                          gmm_kwargs={"seed": args.seed})
+                          gmm_kwargs={"seed": args.seed}, covariance_type=args.covariance)
 
 
 def main(argv=None):

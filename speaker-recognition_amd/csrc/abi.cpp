@@ -6,6 +6,7 @@
 #include "batch.hpp"
 #include "common.hpp"
 #include "fork_proxy.hpp"
+#include "gmm_full.hpp"
 #include "gmm_model.hpp"
 #include "mfcc.hpp"
 #include "score.hpp"
@@ -933,5 +934,94 @@ int sr_reference_rand_sample(int *out, int count) {
     return 0;
     SR_CATCH(-1)
 }
+
+// ---- full-covariance GMMs (gmm_full.hip) ----
+SRFullGMM *sr_fullgmm_create(int K, int D, const double *weights, const double *means, const double *prec_chol) {
+    SR_TRY
+    if (K < 1) fail("n_components must be >= 1 (got %d)", K);
+    if (D < 1 || D > FULL_MAX_D) fail("full-covariance models support 1 <= D <= %d dims (got %d)", FULL_MAX_D, D);
+    const int given = (weights != nullptr) + (means != nullptr) + (prec_chol != nullptr);
+    if (given != 0 && given != 3) fail("give weights, means and prec_chol together, or none of them");
+    auto g = std::make_unique<SRFullGMM>();
+    g->K = K;
+    g->D = D;
+    if (given) {
+        g->weights.assign(weights, weights + K);
+        g->means.assign(means, means + (size_t)K * D);
+        g->prec_chol.assign(prec_chol, prec_chol + (size_t)K * D * D);
+        for (int k = 0; k < K; k++) {
+            if (!(g->weights[k] >= 0.0) || !std::isfinite(g->weights[k])) fail("weight %d is not a finite value >= 0", k);
+            for (int i = 0; i < D; i++) {
+                if (!(g->prec_chol[((size_t)k * D + i) * D + i] > 0.0)) fail("precisions_cholesky[%d] has a diagonal entry <= 0", k);
+                for (int j = 0; j < i; j++)
+                    if (g->prec_chol[((size_t)k * D + i) * D + j] != 0.0) fail("precisions_cholesky[%d] is not upper triangular", k);
+            }
+        }
+        for (double v : g->means)
+            if (!std::isfinite(v)) fail("means must be finite");
+        for (double v : g->prec_chol)
+            if (!std::isfinite(v)) fail("precisions_cholesky must be finite");
+        g->trained = true;
+    }
+    return g.release();
+    SR_CATCH(nullptr)
+}
+
+int sr_fullgmm_fit(SRFullGMM *g, const double *X, int64_t n, int D, const SRFullFitParams *params, SRFullFitStats *out) {
+    SR_TRY
+    if (!g || !X || !params || !out) fail("null argument");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_fullgmm_fit");
+    fullgmm_fit(*g, X, (long)n, D, *params, *out);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_fullgmm_info(SRFullGMM *g, int *K, int *D) {
+    SR_TRY
+    if (!g) fail("null handle");
+    if (K) *K = g->K;
+    if (D) *D = g->D;
+    return g->trained ? 1 : 0;
+    SR_CATCH(-1)
+}
+
+int sr_fullgmm_get(SRFullGMM *g, double *weights, double *means, double *covariances, double *prec_chol) {
+    SR_TRY
+    if (!g) fail("null handle");
+    if (!g->trained) fail("the model has no parameters yet (fit it first)");
+    const size_t K = g->K, D = g->D;
+    if (weights) std::memcpy(weights, g->weights.data(), sizeof(double) * K);
+    if (means) std::memcpy(means, g->means.data(), sizeof(double) * K * D);
+    if (prec_chol) std::memcpy(prec_chol, g->prec_chol.data(), sizeof(double) * K * D * D);
+    if (covariances) {
+        if (g->covariances.empty()) std::memset(covariances, 0, sizeof(double) * K * D * D);
+        else std::memcpy(covariances, g->covariances.data(), sizeof(double) * K * D * D);
+    }
+    return 0;
+    SR_CATCH(-1)
+}
+
+void sr_fullgmm_free(SRFullGMM *g) { delete g; }
+
+SRFullSet *sr_fullset_create(SRFullGMM *const *models, int S) {
+    SR_TRY
+    if (!models) fail("null argument");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_fullset_create");
+    auto set = std::make_unique<SRFullSet>();
+    fullset_pack(*set, models, S);
+    return set.release();
+    SR_CATCH(nullptr)
+}
+
+int sr_fullset_score_batch(SRFullSet *set, SRBatch *batch, double *sums_out, int *argmax_out, float *frame_ll_out) {
+    SR_TRY
+    if (!set || !batch) fail("null argument");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_fullset_score_batch");
+    fullset_score(*set, *batch, sums_out, argmax_out, frame_ll_out);
+    return 0;
+    SR_CATCH(-1)
+}
+
+void sr_fullset_free(SRFullSet *set) { delete set; }
 
 }  // extern "C"

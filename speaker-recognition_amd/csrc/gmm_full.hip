@@ -1,0 +1,564 @@
+// gmm_full.hip -- full-covariance GMMs: scikit-learn's GaussianMixture(covariance_type='full'), the model the reference's shipped
+// CLI trains and scores (src/gui/skgmm.py:20, GaussianMixture(32) on mix_feature's 28 columns).
+//
+// Scoring (fp32, the hot path): lp_k(x) = c_k - 1/2 |P_k^T (x - mu_k)|^2 with c_k = ln w_k + sum_i ln P_k[i][i] - D/2 ln 2 pi.
+// y = P_k^T (x - mu_k) is a matrix product: v_mfma_f32_32x32x2_f32 with A = P_k^T (rows: the output dims j, a row block of 32)
+// and B = x - mu_k (32 frames as columns, two dims per step).  The frames of a wave stay in registers for the whole launch and
+// every mixture's mean is subtracted on the way into the MFMA (one v_sub per MFMA: no cancellation of the expanded x P - mu P
+// form in fp32).  C then holds y_j(frame) with the frame = lane & 31: |y|^2 is 16 in-lane FMAs plus one exchange between the
+// lane halves, and the log-sum-exp over k runs per lane (online, in mixture order).  The model is staged in LDS a chunk of
+// mixtures at a time, in the lane image the MFMA reads (one conflict-free ds_read_b32 per step, serving the wave's T frame
+// tiles), and shared by the workgroup's 4 waves: 4 T 32 frames per staged copy.  The per-utterance sums are formed by a second
+// kernel from the per-frame values in an order fixed by the utterance alone (lane j of a wave adds frames j, j + 64, ... of the
+// utterance in float64, then a butterfly), so the bits do not depend on tiling or on the batch around the utterance.
+//
+// Training (float64, the whole fit on the device; em_f64.hip's pattern): an iteration is seven launches -- log densities,
+// log-sum-exp + responsibilities, the mean (lower bound), nk + means, the covariance sums by frame chunks, the per-mixture
+// Cholesky + inverse (one workgroup per mixture), the weights -- and the host reads 16 bytes ({lower bound, failure flag}) for the
+// stop rule.  The statistics run on the vector ALU in float64: at speaker size (K 32, D 28, ~5600 frames) the covariance GEMMs are
+// 8e7 FMAs per iteration, microseconds of arithmetic, while a measured iteration takes ~0.4 ms (K-wide per-mixture kernels, DESIGN
+// section 7); the fp64 MFMA (D = 28 padded to 32, the responsibility applied to an operand first) was therefore not tried.
+#include "gmm_full.hpp"
+
+#include <cfloat>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+namespace sr {
+
+namespace {
+
+typedef float fc_f32x16 __attribute__((ext_vector_type(16)));
+constexpr double FC_LN_2PI = 1.8378770664093453;
+const char *const FC_ILL_DEFINED =
+    "Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance caused by "
+    "singleton or collapsed samples). Try to decrease the number of components, increase reg_covar, or scale the input data.";
+
+// ---------------------------------------------------------------- scoring
+// NS: steps of two dims the kernel is built for (16: D <= 32, one row block; 32: D <= 64, two row blocks); T: 32-frame tiles per
+// wave.  KC mixtures per LDS chunk: KC * RB * NS * 64 floats = 32 KiB (four workgroups per CU).
+template <int NS, int T>
+__global__ __launch_bounds__(256)
+void fullcov_score_kernel(const float *__restrict__ X, long n, int D, int ns, int nrb, const float *__restrict__ P,
+                          const float *__restrict__ MU, const float *__restrict__ C, const int *__restrict__ kbeg, float *__restrict__ fll) {
+    constexpr int RB = NS / 16, KC = 128 / (NS * RB);
+    __shared__ __attribute__((aligned(16))) float sP[KC * RB * NS * 64];
+    __shared__ float sMu[KC * 64];
+    __shared__ float sC[KC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
+    const int m = blockIdx.y;
+    const long f0 = (long)blockIdx.x * (4 * T * 32) + (long)wave * T * 32;
+    float xr[T][NS];
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        const long f = f0 + 32 * t + col;
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const int d = 2 * s + half;
+            xr[t][s] = (f < n && d < D) ? X[f * D + d] : 0.f;
+        }
+    }
+    float mx[T], sm[T];
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        mx[t] = -__builtin_inff();
+        sm[t] = 0.f;
+    }
+    const int kb0 = kbeg[m], kb1 = kbeg[m + 1];
+    const int per = nrb * ns * 64;                       // floats of one mixture's image
+    for (int kc0 = kb0; kc0 < kb1; kc0 += KC) {
+        const int nk = min(KC, kb1 - kc0);
+        __syncthreads();
+        const float4 *src = reinterpret_cast<const float4 *>(P + (size_t)kc0 * per);
+        float4 *dst = reinterpret_cast<float4 *>(sP);
+        for (int i = threadIdx.x; i < nk * per / 4; i += 256) dst[i] = src[i];
+        for (int i = threadIdx.x; i < nk * 64; i += 256) sMu[i] = MU[(size_t)kc0 * 64 + i];
+        if (threadIdx.x < nk) sC[threadIdx.x] = C[kc0 + threadIdx.x];
+        __syncthreads();
+        for (int j = 0; j < nk; j++) {
+            float q[T];
+#pragma unroll
+            for (int t = 0; t < T; t++) q[t] = 0.f;
+            for (int rb = 0; rb < nrb; rb++) {
+                fc_f32x16 acc[T];
+#pragma unroll
+                for (int t = 0; t < T; t++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+                const float *pa = sP + (size_t)(j * nrb + rb) * ns * 64 + lane;
+                const float *pm = sMu + j * 64 + half;
+#pragma unroll
+                for (int s = 0; s < NS; s++) {
+                    if (s < ns) {
+                        const float a = pa[s * 64], mu = pm[2 * s];
+#pragma unroll
+                        for (int t = 0; t < T; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, xr[t][s] - mu, acc[t], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < T; t++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) q[t] = fmaf(acc[t][r], acc[t][r], q[t]);
+            }
+            const float c = sC[j];
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                const float qq = q[t] + __shfl_xor(q[t], 32);
+                const float lp = c - 0.5f * qq;
+                if (lp > mx[t]) {
+                    sm[t] = sm[t] * __expf(mx[t] - lp) + 1.f;
+                    mx[t] = lp;
+                } else if (lp > -__builtin_inff()) {
+                    sm[t] += __expf(lp - mx[t]);
+                }
+            }
+        }
+    }
+    if (half == 0) {
+#pragma unroll
+        for (int t = 0; t < T; t++) {
+            const long f = f0 + 32 * t + col;
+            if (f < n) fll[(size_t)m * n + f] = mx[t] + __logf(sm[t]);
+        }
+    }
+}
+
+// a wave per (utterance, model): lane j adds the utterance's frames j, j + 64, ... in float64, then a butterfly -- an order set by the
+// utterance alone
+__global__ __launch_bounds__(256)
+void fullcov_sum_kernel(const float *__restrict__ fll, long n, const int64_t *__restrict__ off, int U, int S, double *__restrict__ sums) {
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)U * S) return;
+    const int u = (int)(item / S), m = (int)(item % S);
+    const int64_t b = off[u], e = off[u + 1];
+    const float *row = fll + (size_t)m * n;
+    double s = 0.0;
+    for (int64_t i = b + lane; i < e; i += 64) s += (double)row[i];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) sums[(size_t)u * S + m] = s;
+}
+
+// ---------------------------------------------------------------- training (float64)
+constexpr int FE_FB = 32;          // frames of a density workgroup
+constexpr int FE_PQ = 9;           // covariance pairs per thread: 9 x 256 >= 64 x 65 / 2
+constexpr int FE_CB = 32;          // frames staged per covariance step
+
+struct FeArgs {
+    const double *X;                // [n][D]
+    long n;
+    int D, K, n_chunks, chunk;
+    double *w, *logw, *mu, *prec, *logdet, *cov;     // [K], [K], [K][D], [K][D][D], [K], [K][D][D]
+    double *lp;                     // [n][K]: log densities, then responsibilities
+    double *lpn;                    // [n]
+    double *nk;                     // [K]
+    double *partial;                // [n_chunks][K][D (D + 1) / 2]
+    double *head;                   // [2]: lower bound, failure flag
+    double reg;
+};
+
+// weighted log densities: -1/2 (D ln 2 pi + |P^T (x - mu)|^2) + log det + ln w  (sklearn _estimate_log_gaussian_prob + _estimate_log_weights)
+__global__ __launch_bounds__(256)
+void fe_logprob_kernel(const FeArgs a) {
+    extern __shared__ double fe_lds[];
+    const int D = a.D, k = blockIdx.y, XS = D + 1;
+    double *sP = fe_lds, *sMu = sP + D * D, *sDiff = sMu + D, *sQ = sDiff + FE_FB * XS;
+    const int tid = threadIdx.x, f = tid & (FE_FB - 1), g = tid / FE_FB;
+    const long f0 = (long)blockIdx.x * FE_FB;
+    for (int i = tid; i < D * D; i += 256) sP[i] = a.prec[(size_t)k * D * D + i];
+    for (int i = tid; i < D; i += 256) sMu[i] = a.mu[(size_t)k * D + i];
+    __syncthreads();
+    for (int i = tid; i < FE_FB * D; i += 256) {
+        const int fr = i / D, d = i - fr * D;
+        sDiff[fr * XS + d] = f0 + fr < a.n ? a.X[(size_t)(f0 + fr) * D + d] - sMu[d] : 0.0;
+    }
+    __syncthreads();
+    double q = 0.0;
+    for (int j = g; j < D; j += 256 / FE_FB) {
+        double y = 0.0;
+        for (int i = 0; i <= j; i++) y = fma(sP[i * D + j], sDiff[f * XS + i], y);      // P upper triangular
+        q = fma(y, y, q);
+    }
+    sQ[g * FE_FB + f] = q;
+    __syncthreads();
+    if (g == 0 && f0 + f < a.n) {
+        double qq = 0.0;
+        for (int h = 0; h < 256 / FE_FB; h++) qq += sQ[h * FE_FB + f];
+        a.lp[(size_t)(f0 + f) * a.K + k] = -0.5 * (D * FC_LN_2PI + qq) + a.logdet[k] + a.logw[k];
+    }
+}
+
+// a frame's log-sum-exp (max + log sum exp(a - max)) and its responsibilities exp(lp - lse), in place
+__global__ __launch_bounds__(256)
+void fe_lse_kernel(const FeArgs a) {
+    const long f = (long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= a.n) return;
+    double *row = a.lp + (size_t)f * a.K;
+    double m = -__builtin_inf();
+    for (int k = 0; k < a.K; k++) m = fmax(m, row[k]);
+    double s = 0.0;
+    for (int k = 0; k < a.K; k++) s += exp(row[k] - m);
+    const double l = log(s) + m;
+    a.lpn[f] = l;
+    for (int k = 0; k < a.K; k++) row[k] = exp(row[k] - l);
+}
+
+// fixed-order block sum of 256 threads' values (every thread gets the total)
+__device__ double fe_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double t = red[0];
+    __syncthreads();
+    return t;
+}
+
+__global__ __launch_bounds__(256)
+void fe_bound_kernel(const FeArgs a) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (long f = threadIdx.x; f < a.n; f += 256) s += a.lpn[f];
+    s = fe_block_sum(s, red);
+    if (threadIdx.x == 0) a.head[0] = s / (double)a.n;
+}
+
+// nk = sum resp + 10 eps, means = resp^T X / nk (the new means: the covariance below is formed around them)
+__global__ __launch_bounds__(256)
+void fe_means_kernel(const FeArgs a) {
+    __shared__ double red[256];
+    const int k = blockIdx.x, K = a.K, D = a.D;
+    double s = 0.0;
+    for (long f = threadIdx.x; f < a.n; f += 256) s += a.lp[(size_t)f * K + k];
+    const double nk = fe_block_sum(s, red) + 10.0 * DBL_EPSILON;
+    if (threadIdx.x == 0) a.nk[k] = nk;
+    for (int d = 0; d < D; d++) {
+        double t = 0.0;
+        for (long f = threadIdx.x; f < a.n; f += 256) t = fma(a.lp[(size_t)f * K + k], a.X[(size_t)f * D + d], t);
+        t = fe_block_sum(t, red);
+        if (threadIdx.x == 0) a.mu[(size_t)k * D + d] = t / nk;
+    }
+}
+
+// sum over a chunk of frames of resp (x - mu)(x - mu)^T, the upper triangle, pair p = (i, j >= i) in row order
+__global__ __launch_bounds__(256)
+void fe_cov_kernel(const FeArgs a) {
+    __shared__ double sDiff[FE_CB * (FULL_MAX_D + 1)];
+    __shared__ double sR[FE_CB];
+    const int k = blockIdx.x, c = blockIdx.y, D = a.D, K = a.K, XS = D + 1, npairs = D * (D + 1) / 2;
+    int pi[FE_PQ], pj[FE_PQ];
+    double acc[FE_PQ];
+#pragma unroll
+    for (int q = 0; q < FE_PQ; q++) {
+        int rem = threadIdx.x + 256 * q, i = 0;
+        if (rem >= npairs) rem = 0;
+        while (rem >= D - i) {
+            rem -= D - i;
+            i++;
+        }
+        pi[q] = i;
+        pj[q] = i + rem;
+        acc[q] = 0.0;
+    }
+    const long b = (long)c * a.chunk, e = min(a.n, b + a.chunk);
+    for (long t0 = b; t0 < e; t0 += FE_CB) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < FE_CB * D; i += 256) {
+            const int fr = i / D, d = i - fr * D;
+            sDiff[fr * XS + d] = t0 + fr < e ? a.X[(size_t)(t0 + fr) * D + d] - a.mu[(size_t)k * D + d] : 0.0;
+        }
+        if (threadIdx.x < FE_CB) sR[threadIdx.x] = t0 + threadIdx.x < e ? a.lp[(size_t)(t0 + threadIdx.x) * K + k] : 0.0;
+        __syncthreads();
+        const int nf = (int)min((long)FE_CB, e - t0);
+#pragma unroll
+        for (int q = 0; q < FE_PQ; q++) {
+            if ((int)threadIdx.x + 256 * q < npairs) {
+                double s = acc[q];
+                for (int fr = 0; fr < nf; fr++) s = fma(sR[fr] * sDiff[fr * XS + pi[q]], sDiff[fr * XS + pj[q]], s);
+                acc[q] = s;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < FE_PQ; q++) {
+        const int p = threadIdx.x + 256 * q;
+        if (p < npairs) a.partial[((size_t)c * K + k) * npairs + p] = acc[q];
+    }
+}
+
+// covariance = chunk sums in order / nk + reg I; Cholesky L (a pivot <= 0 sets the failure flag); P = (L^-1)^T; log det = sum ln P_ii
+__global__ __launch_bounds__(64)
+void fe_chol_kernel(const FeArgs a) {
+    __shared__ double sA[FULL_MAX_D * (FULL_MAX_D + 1)];
+    __shared__ int bad;
+    const int k = blockIdx.x, D = a.D, XS = D + 1, npairs = D * (D + 1) / 2, t = threadIdx.x;
+    if (t == 0) bad = 0;
+    const double nk = a.nk[k];
+    double *cov = a.cov + (size_t)k * D * D, *P = a.prec + (size_t)k * D * D;
+    for (int p = t; p < npairs; p += 64) {
+        int rem = p, i = 0;
+        while (rem >= D - i) {
+            rem -= D - i;
+            i++;
+        }
+        const int j = i + rem;
+        double s = 0.0;
+        for (int c = 0; c < a.n_chunks; c++) s += a.partial[((size_t)c * a.K + k) * npairs + p];
+        double v = s / nk;
+        if (i == j) v += a.reg;
+        sA[i * XS + j] = sA[j * XS + i] = v;
+        cov[i * D + j] = cov[j * D + i] = v;
+    }
+    __syncthreads();
+    // column by column, in place (lower triangle)
+    for (int j = 0; j < D; j++) {
+        if (t == j) {
+            double s = sA[j * XS + j];
+            for (int m = 0; m < j; m++) s -= sA[j * XS + m] * sA[j * XS + m];
+            if (!(s > 0.0)) bad = 1;
+            sA[j * XS + j] = sqrt(s);
+        }
+        __syncthreads();
+        if (t > j && t < D) {
+            double s = sA[t * XS + j];
+            for (int m = 0; m < j; m++) s -= sA[t * XS + m] * sA[j * XS + m];
+            sA[t * XS + j] = s / sA[j * XS + j];
+        }
+        __syncthreads();
+    }
+    // column c of Z = L^-1 by forward substitution, written as row c of P (P = Z^T: P[c][i] = Z[i][c], upper triangular)
+    if (t < D) {
+        for (int i = 0; i < t; i++) P[t * D + i] = 0.0;
+        for (int i = t; i < D; i++) {
+            double s = i == t ? 1.0 : 0.0;
+            for (int m = t; m < i; m++) s -= sA[i * XS + m] * P[t * D + m];
+            P[t * D + i] = s / sA[i * XS + i];
+        }
+    }
+    if (t == 0) {
+        double ld = 0.0;
+        for (int i = 0; i < D; i++) ld += log(1.0 / sA[i * XS + i]);     // (P_ii, as the substitution above forms it)
+        a.logdet[k] = ld;
+        if (bad) a.head[1] = 1.0;
+    }
+}
+
+// mode 0 (EM): w = nk / sum nk; mode 1 (k-means initialisation): w = nk / n.  Then ln w.
+__global__ void fe_weights_kernel(const FeArgs a, int mode) {
+    if (threadIdx.x != 0) return;
+    double tot = 0.0;
+    if (mode == 0)
+        for (int k = 0; k < a.K; k++) tot += a.nk[k];
+    else
+        tot = (double)a.n;
+    for (int k = 0; k < a.K; k++) {
+        a.w[k] = a.nk[k] / tot;
+        a.logw[k] = log(a.w[k]);
+    }
+}
+
+// explicit initialisation: ln w and log det from the given arrays
+__global__ void fe_derive_kernel(const FeArgs a) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.K) return;
+    double ld = 0.0;
+    for (int i = 0; i < a.D; i++) ld += log(a.prec[((size_t)k * a.D + i) * a.D + i]);
+    a.logdet[k] = ld;
+    a.logw[k] = log(a.w[k]);
+}
+
+struct FeWorkspace {
+    DevBuf<double> X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head;
+};
+FeWorkspace &few() { return per_device<FeWorkspace>(); }
+
+}  // namespace
+
+void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out) {
+    const int K = g.K;
+    if (D != g.D) fail("data has %d columns, the model %d", D, g.D);
+    if (n < K) fail("Expected n_samples >= n_components but got n_components = %d, n_samples = %ld", K, n);
+    if (p.max_iter < 1) fail("max_iter must be >= 1 (got %d)", p.max_iter);
+    if (p.init_given && !g.trained) fail("init_given: the handle has no parameters");
+    if (!(p.reg_covar >= 0.0) || !(p.tol >= 0.0)) fail("tol and reg_covar must be >= 0");
+    if (p.seed < 0) fail("seed must be >= 0");
+    for (long e = 0; e < n * D; e++)
+        if (!std::isfinite(X[e])) fail("Input X contains NaN or infinity.");
+    ensure_device();
+    auto &ws = few();
+    const int npairs = D * (D + 1) / 2;
+    FeArgs a{};
+    a.n = n;
+    a.D = D;
+    a.K = K;
+    a.n_chunks = (int)std::min<long>(32, (n + 255) / 256);
+    a.chunk = (int)((n + a.n_chunks - 1) / a.n_chunks);
+    a.reg = p.reg_covar;
+    ws.X.upload(X, (size_t)n * D);
+    ws.w.ensure(K);
+    ws.logw.ensure(K);
+    ws.mu.ensure((size_t)K * D);
+    ws.prec.ensure((size_t)K * D * D);
+    ws.logdet.ensure(K);
+    ws.cov.ensure((size_t)K * D * D);
+    ws.lp.ensure((size_t)n * K);
+    ws.lpn.ensure(n);
+    ws.nk.ensure(K);
+    ws.partial.ensure((size_t)a.n_chunks * K * npairs);
+    ws.head.ensure(2);
+    a.X = ws.X.p; a.w = ws.w.p; a.logw = ws.logw.p; a.mu = ws.mu.p; a.prec = ws.prec.p; a.logdet = ws.logdet.p; a.cov = ws.cov.p;
+    a.lp = ws.lp.p; a.lpn = ws.lpn.p; a.nk = ws.nk.p; a.partial = ws.partial.p; a.head = ws.head.p;
+    hipStream_t st = ctx().stream;
+    SR_HIP(hipMemsetAsync(ws.head.p, 0, 2 * sizeof(double), st));
+    const size_t lds_lp = sizeof(double) * ((size_t)D * D + D + FE_FB * (D + 1) + 256);
+    auto mstep = [&](int weight_mode) {
+        hipLaunchKernelGGL(fe_means_kernel, dim3(K), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(fe_cov_kernel, dim3(K, a.n_chunks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(fe_chol_kernel, dim3(K), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(fe_weights_kernel, dim3(1), dim3(64), 0, st, a, weight_mode);
+    };
+    double head[2] = {0.0, 0.0};
+    if (p.init_given) {
+        ws.w.upload(g.weights.data(), K);
+        ws.mu.upload(g.means.data(), (size_t)K * D);
+        ws.prec.upload(g.prec_chol.data(), (size_t)K * D * D);
+        hipLaunchKernelGGL(fe_derive_kernel, dim3((K + 63) / 64), dim3(64), 0, st, a);
+    } else {
+        // sklearn's init_params='kmeans': one-hot responsibilities from k-means labels, then the M-step with weights nk / n
+        std::vector<float> Xf((size_t)n * D);
+        for (size_t e = 0; e < Xf.size(); e++) Xf[e] = (float)X[e];
+        const std::vector<int> label = kmeans_labels(Xf.data(), n, D, K, p.seed);
+        std::vector<double> resp((size_t)n * K, 0.0);
+        for (long f = 0; f < n; f++) resp[(size_t)f * K + label[f]] = 1.0;
+        ws.lp.upload(resp.data(), resp.size());
+        mstep(1);
+        SR_HIP(hipGetLastError());
+        ws.head.download(head, 2);
+        sync_stream();
+        if (head[1] != 0.0) fail("%s", FC_ILL_DEFINED);
+    }
+    double lower = -std::numeric_limits<double>::infinity();
+    out.converged = 0;
+    int it = 1;
+    for (; it <= p.max_iter; it++) {
+        const double prev = lower;
+        hipLaunchKernelGGL(fe_logprob_kernel, dim3((unsigned)((n + FE_FB - 1) / FE_FB), K), dim3(256), lds_lp, st, a);
+        hipLaunchKernelGGL(fe_lse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(fe_bound_kernel, dim3(1), dim3(256), 0, st, a);
+        mstep(0);
+        SR_HIP(hipGetLastError());
+        ws.head.download(head, 2);
+        sync_stream();
+        if (head[1] != 0.0) fail("%s", FC_ILL_DEFINED);
+        lower = head[0];
+        if (std::fabs(lower - prev) < p.tol) {
+            out.converged = 1;
+            break;
+        }
+    }
+    out.n_iter = std::min(it, p.max_iter);
+    out.lower_bound = lower;
+    g.weights.resize(K);
+    g.means.resize((size_t)K * D);
+    g.prec_chol.resize((size_t)K * D * D);
+    g.covariances.resize((size_t)K * D * D);
+    ws.w.download(g.weights.data(), K);
+    ws.mu.download(g.means.data(), (size_t)K * D);
+    ws.prec.download(g.prec_chol.data(), (size_t)K * D * D);
+    ws.cov.download(g.covariances.data(), (size_t)K * D * D);
+    sync_stream();
+    g.trained = true;
+}
+
+void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S) {
+    if (S < 1) fail("a set needs at least one model");
+    const int D = models[0] ? models[0]->D : 0;
+    set.S = S;
+    set.D = D;
+    set.ns = (D + 1) / 2;
+    set.nrb = (D + 31) / 32;
+    set.kbeg.assign(S + 1, 0);
+    for (int m = 0; m < S; m++) {
+        const SRFullGMM *g = models[m];
+        if (!g) fail("null model %d", m);
+        if (!g->trained) fail("model %d has no parameters", m);
+        if (g->D != D) fail("model %d has %d dims, model 0 has %d", m, g->D, D);
+        set.kbeg[m + 1] = set.kbeg[m] + g->K;
+    }
+    const int KT = set.kbeg[S], ns = set.ns, nrb = set.nrb, per = nrb * ns * 64;
+    std::vector<float> P((size_t)KT * per, 0.f), mu((size_t)KT * 64, 0.f), c(KT);
+    for (int m = 0; m < S; m++) {
+        const SRFullGMM *g = models[m];
+        for (int k = 0; k < g->K; k++) {
+            const int kt = set.kbeg[m] + k;
+            const double *Pk = g->prec_chol.data() + (size_t)k * D * D;
+            // A of v_mfma_f32_32x32x2_f32: lane l holds A[row l & 31][step dim l >> 5] = P^T[j][d] = P[d][j]
+            for (int rb = 0; rb < nrb; rb++)
+                for (int s = 0; s < ns; s++)
+                    for (int l = 0; l < 64; l++) {
+                        const int d = 2 * s + (l >> 5), j = 32 * rb + (l & 31);
+                        if (d < D && j < D) P[(size_t)kt * per + ((size_t)rb * ns + s) * 64 + l] = (float)Pk[(size_t)d * D + j];
+                    }
+            double ld = 0.0;
+            for (int i = 0; i < D; i++) {
+                mu[(size_t)kt * 64 + i] = (float)g->means[(size_t)k * D + i];
+                ld += std::log(Pk[(size_t)i * D + i]);
+            }
+            c[kt] = (float)(std::log(g->weights[k]) + ld - 0.5 * D * FC_LN_2PI);
+        }
+    }
+    ensure_device();
+    set.device = current_device();
+    set.P.upload(P.data(), P.size());
+    set.mu.upload(mu.data(), mu.size());
+    set.c.upload(c.data(), c.size());
+    set.d_kbeg.upload(set.kbeg.data(), set.kbeg.size());
+    sync_stream();
+}
+
+void fullset_score(SRFullSet &set, SRBatch &b, double *sums, int *argmax, float *frame_ll) {
+    if (b.kind != SRBatch::FEATURES) fail("full-covariance scoring needs a feature batch");
+    if (b.dim != set.D) fail("batch has %d dims, the models %d", b.dim, set.D);
+    ensure_device();
+    if (set.device != current_device()) fail("model set lives on device %d, the calling thread is on device %d", set.device, current_device());
+    b.bind_device();
+    const long n = b.n_rows;
+    const int U = b.n_utt, S = set.S;
+    set.fll.ensure((size_t)S * std::max(1L, n));
+    set.sums.ensure((size_t)std::max(1, U) * S);
+    hipStream_t st = ctx().stream;
+    if (n > 0) {
+        ScopedKernelTimer timer(T_SCORE);
+        if (set.D <= 32) {
+            const unsigned gx = (unsigned)((n + 4 * 4 * 32 - 1) / (4 * 4 * 32));
+            hipLaunchKernelGGL((fullcov_score_kernel<16, 4>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
+                               set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
+        } else {
+            const unsigned gx = (unsigned)((n + 4 * 2 * 32 - 1) / (4 * 2 * 32));
+            hipLaunchKernelGGL((fullcov_score_kernel<32, 2>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
+                               set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
+        }
+        if (U > 0)
+            hipLaunchKernelGGL(fullcov_sum_kernel, dim3((unsigned)(((long)U * S + 3) / 4)), dim3(256), 0, st, set.fll.p, n, b.d_offsets.p, U, S,
+                               set.sums.p);
+        SR_HIP(hipGetLastError());
+    }
+    std::vector<double> h((size_t)U * S, 0.0);
+    if (n > 0 && U > 0) set.sums.download(h.data(), h.size());
+    if (frame_ll && n > 0) set.fll.download(frame_ll, (size_t)S * n);
+    sync_stream();
+    if (sums) std::copy(h.begin(), h.end(), sums);
+    if (argmax)
+        for (int u = 0; u < U; u++) {
+            int best = 0;
+            for (int m = 1; m < S; m++)
+                if (h[(size_t)u * S + m] > h[(size_t)u * S + best]) best = m;
+            argmax[u] = best;
+        }
+}
+
+}  // namespace sr

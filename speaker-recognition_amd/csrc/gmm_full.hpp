@@ -1,0 +1,38 @@
+// gmm_full.hpp -- full-covariance GMMs (C ABI handles `SRFullGMM *` / `SRFullSet *`): scikit-learn's GaussianMixture layout,
+// float64 EM on the device, fp32 matrix-core scoring of a packed set of speakers (csrc/gmm_full.hip).
+#pragma once
+
+#include "batch.hpp"
+#include "common.hpp"
+
+#include "../../include/pygmm_hip.h"
+
+#include <vector>
+
+// One model: weights[K], means[K][D], precisions_cholesky[K][D][D] (upper triangular P_k, precision = P_k P_k^T), float64 on the
+// host.  covariances[K][D][D] exists after a fit (the M-step's), empty for a model built from arrays.
+struct SRFullGMM {
+    int K = 0, D = 0;
+    bool trained = false;
+    std::vector<double> weights, means, prec_chol, covariances;
+};
+
+// S models of one dimension packed for the scoring kernel (gmm_full.hip: the lane image of P_k^T, the means, the constants).
+struct SRFullSet {
+    int S = 0, D = 0, ns = 0, nrb = 0, device = -1;
+    std::vector<int> kbeg;           // [S + 1] first mixture of every model
+    sr::DevBuf<float> P;             // [K_total][nrb][ns][64]
+    sr::DevBuf<float> mu;            // [K_total][64]
+    sr::DevBuf<float> c;             // [K_total]  ln w + sum ln P_ii - D/2 ln 2 pi
+    sr::DevBuf<int> d_kbeg;
+    sr::DevBuf<float> fll;           // [S][n] per-frame log-likelihoods of the last call
+    sr::DevBuf<double> sums;         // [U][S]
+};
+
+namespace sr {
+constexpr int FULL_MAX_D = 64;
+void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out);
+void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S);
+void fullset_score(SRFullSet &set, SRBatch &batch, double *sums, int *argmax, float *frame_ll);
+std::vector<int> kmeans_labels(const float *X, long n, int dim, int K, long seed);     // kmeans_init.hip
+}  // namespace sr

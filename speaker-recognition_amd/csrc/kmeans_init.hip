@@ -857,3 +857,18 @@ void init_gmm_like_reference(GMM &g, const float *X, long n, int dim, const Para
 }
 
 }  // namespace sr
+
+namespace sr {
+// Labels of the library's seeded k-means (k-means|| + Lloyd on the full data, then the nearest centre of every point): the
+// initialisation of a full-covariance fit (gmm_full.hip, sklearn's init_params='kmeans' with this library's k-means).
+std::vector<int> kmeans_labels(const float *X, long n, int dim, int K, long seed) {
+    ensure_device();
+    kws().X.upload(X, (size_t)n * dim);
+    RandStream rs(seed);
+    const std::vector<double> c = kmeans_parallel_init(X, n, dim, K, 1, rs, 0);
+    std::vector<double> dist((size_t)n);
+    std::vector<int> belong((size_t)n);
+    device_assign(n, dim, c, 0, K, dist, belong, true);
+    return belong;
+}
+}  // namespace sr

@@ -6,7 +6,11 @@ drop-in boundary of this repo; its scikit-learn default is third-party code).
 Extensions (all keyword-only, defaults = the reference's behaviour): ``gmm_order``,
 ``feature_kwargs`` (forwarded to the extractor), ``lpc`` (False: MFCC half of mix_feature only),
 ``diff``/``nd`` (append deltas to the MFCC half; excludes the LPC columns),
-``gmm_kwargs`` (forwarded to ``pygmm.GMM``), ``ubm`` (MAP-adapt speakers from a UBM).
+``gmm_kwargs`` (forwarded to ``pygmm.GMM``), ``ubm`` (MAP-adapt speakers from a UBM),
+``covariance_type`` ('diag', the default: the C++ back-end's diagonal models; 'full': the reference CLI's own speaker model,
+scikit-learn's full-covariance ``GaussianMixture``, as ``skgmm.GMMSet`` -- ``UBM_MODEL_FILE`` is then ignored, as the reference
+ignores it when its set is not ``GMMSetPyGMM``, interface.py:63-75; ``gmm_kwargs`` go to ``skgmm.GMM``, a ``seed`` among them
+becoming its ``random_state``, -1 = the library's default).
 VAD (``init_noise`` / ``filter``) is the LTSD detector of ``filters`` (third-party pyssp in the
 reference: restated, parity unpinned).
 """
@@ -30,14 +34,25 @@ class ModelInterface(object):
     UBM_MODEL_FILE = None
 
     def __init__(self, *, gmm_order=32, feature_kwargs=None, diff=False, nd=1, lpc=True, gmm_kwargs=None,
-                 verbose=True):
+                 verbose=True, covariance_type="diag"):
+        if covariance_type not in ("diag", "full"):
+            raise ValueError("covariance_type must be 'diag' or 'full' (got %r)" % (covariance_type,))
+        self.covariance_type = covariance_type
         self.features = defaultdict(list)
         self.gmm_order = gmm_order
         self.feature_kwargs = dict(feature_kwargs or {})
         self.diff, self.nd, self.lpc = diff, nd, lpc
         self.gmm_kwargs = dict(gmm_kwargs or {})
         self.verbose = verbose
-        self.gmmset = GMMSet(gmm_order=gmm_order, **self.gmm_kwargs)
+        self.gmmset = self._new_full_set() if covariance_type == "full" else GMMSet(gmm_order=gmm_order, **self.gmm_kwargs)
+
+    def _new_full_set(self):
+        from . import skgmm
+        kw = dict(self.gmm_kwargs)
+        if "seed" in kw:
+            seed = kw.pop("seed")
+            kw["random_state"] = None if seed is None or seed < 0 else int(seed)
+        return skgmm.GMMSet(gmm_order=self.gmm_order, **kw)
 
     def init_noise(self, fs, signal):
         """init vad from environment noise (gui/interface.py:37-41)"""
@@ -66,6 +81,8 @@ class ModelInterface(object):
 
     def _get_gmm_set(self):
         import os
+        if getattr(self, "covariance_type", "diag") == "full":
+            return self._new_full_set()
         if self.UBM_MODEL_FILE and os.path.isfile(self.UBM_MODEL_FILE):
             return GMMSet(ubm=GMM.load(self.UBM_MODEL_FILE), **self.gmm_kwargs)
         return GMMSet(gmm_order=self.gmm_order, **self.gmm_kwargs)
@@ -92,11 +109,12 @@ class ModelInterface(object):
     def predict_many(self, items, gpus=1):
         """Extension: [(fs, signal), ...] -> labels, every utterance scored in one batch.  ``gpus`` != 1
         (0 = every visible GPU) shards the utterances over the GPUs of the node from this one process
-        (core.MultiPredictor: a host thread and a model replica per GPU, no collective) -- for the MFCC-only
-        feature (``lpc=False``) on int16 audio of one sampling rate; anything else takes the one-GPU path."""
+        (core.MultiPredictor: a host thread and a model replica per GPU, no collective) -- for diagonal models on the
+        MFCC-only feature (``lpc=False``) on int16 audio of one sampling rate; anything else (full-covariance models among it)
+        takes the one-GPU path."""
         items = list(items)
         rates = {fs for fs, _ in items}
-        if gpus != 1 and not self.lpc and len(rates) == 1 and items and \
+        if gpus != 1 and getattr(self, "covariance_type", "diag") == "diag" and not self.lpc and len(rates) == 1 and items and \
                 all(np.asarray(sig).dtype == np.int16 and np.asarray(sig).ndim == 1 for _, sig in items):
             from .core import MultiPredictor
             kw = dict(self.feature_kwargs)
