@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised check of the serving stream (sr_stream_*: double-buffered H2D, optional hipGraph replay) against the synchronous
 fused call on the same windows: random rates, window counts, model sets (independent, UBM + MAP, with collapsed components
--> hybrid form), other API traffic between ticks.  `fuzz_stream.py [cases] [seed]`"""
+-> hybrid form), other API traffic between ticks -- incl. a result-delivering ModelSet.score on a UBM + MAP set with a speaker
+far from its UBM, whose pass leaves shared-sigma exception counts behind, which must equal its first answer bit for bit.
+`fuzz_stream.py [cases] [seed]`"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,6 +14,14 @@ from speaker_recognition_amd.pygmm import GMM
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 fails = 0
+# other traffic that delivers its results straight to host memory and relies on the pass counters being clear (csrc/gmm_score.hip)
+_lib.set_option("debug_verify_clean_counters", 1)
+r_ubm = synth.synth_gmm(64, 13, 4242)
+r_w, r_mu, r_sg = r_ubm
+r_models = [r_ubm] + [synth.synth_map_speaker(r_ubm, 600 + s) for s in range(12)] + [(r_w, r_mu + 3.0 * r_sg, r_sg)]
+rogue = ModelSet([GMM.from_arrays(*m) for m in r_models])
+rogue_feats = Batch.from_features([synth.draw_frames(r_models[1 + u], 150 + 7 * u, 31 + u) for u in range(3)])
+rogue_want = rogue.score(rogue_feats)
 for c in range(cases):
     fs = int(rng.choice([8000, 16000]))
     nwin = int(rng.integers(1, 9))
@@ -44,6 +54,10 @@ for c in range(cases):
             st.submit(ticks[t])
             if t == 2:
                 ex.predict_batch(ms, Batch.from_pcm([audio[:2 * fs]]), nd=0)       # other traffic: workspaces move
+            if t != 2:
+                again = rogue.score(rogue_feats)                                     # other traffic between submit and collect
+                if not (np.array_equal(again[0], rogue_want[0]) and np.array_equal(again[1], rogue_want[1])):
+                    msg += " [graph=%d: the delivering call in between changed its answer]" % graph
             got.append(st.collect())
         got.append(st.collect())
         for t in range(n_ticks):

@@ -886,6 +886,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "debug_em_small_absent_workgroup") {
         if (value != 0 && value != 1) fail("debug_em_small_absent_workgroup must be 0 or 1");
         set_em_small_test_absent((int)value);                       // test hook (tests/test_gpu_em_small.py): a workgroup of the whole-fit kernel stays away from a barrier
+    } else if (k == "debug_verify_clean_counters") {
+        if (value != 0 && value != 1) fail("debug_verify_clean_counters must be 0 or 1");
+        score_options().verify_clean_counters = (int)value;        // test hook (tests/test_gpu_interleave.py): checked in score_device
     } else if (k == "debug_helper_max_models") {
         if (value < 0) fail("debug_helper_max_models must be >= 0 (0: the default)");
         fork_proxy_set_max_models(value);                           // test hook (tests/test_gpu_fork.py): applies in the helper, where it is forwarded

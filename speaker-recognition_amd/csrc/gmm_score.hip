@@ -561,7 +561,11 @@ struct ScoreWorkspace {
     DevBuf<int2> flush_list;             // (tile, model) pairs in the partial-product band (lse.hpp, gmm_flush.hip)
     size_t flush_min_cap = 0;            // set after an overflow: the next pass gets a list of that length
     // SCORE_HOST_DELIVER: the page-locked landing area, the last sequence number handed out, and whether the last pass's finalize
-    // left `clean_n` counters at `clean_p` cleared (nothing else writes them between passes)
+    // left `clean_n` counters at `clean_p` cleared.  Invariant: `clean_p` is set only by a delivering pass, and reset by every
+    // pass and by whatever else writes the counters -- a replayed serving graph (counters_written_elsewhere, stream.cpp),
+    // whose tick does not go through score_device.  A stale `clean_p` left a tick's exception counts in place for the next
+    // delivering pass: the shared-sigma engine indexed its exception lists with them, past their end.
+    // (Every other writer goes through score_device: multi.cpp's pieces, the hybrid halves, the re-runs of fetch_results, EM.)
     PinnedBuf<char> deliver;
     void *deliver_dev = nullptr;         // the device's view of it
     unsigned deliver_seq = 0;
@@ -569,6 +573,8 @@ struct ScoreWorkspace {
     size_t clean_n = 0;
 };
 static ScoreWorkspace &ws() { return per_device<ScoreWorkspace>(); }   // one per device, leaked on purpose
+
+void counters_written_elsewhere() { ws().clean_p = nullptr; }
 
 // What a scoring pass needs for the partial-product band (lse.hpp): the threshold its engine compares per-frame values
 // with, and the list gmm_finalize_kernel notes poisoned (tile, model) pairs in.  Nothing when the reference's clamp is off.
@@ -975,8 +981,17 @@ ScoreResult score_device(SRModelSet &set, SRBatch &feat, bool want_frame_ll, int
     const size_t n_counters = 4 + 2 * set.h2s.blocks.size();      // (shared-sigma engine: exception entries and items per block)
     w.counters.ensure(n_counters);
     // (a delivering finalize cleared them behind itself; only a delivering pass -- never one being captured into a graph -- relies on it)
-    if (!((flags & SCORE_HOST_DELIVER) && w.clean_p == w.counters.p && w.clean_n >= n_counters))
+    if (!((flags & SCORE_HOST_DELIVER) && w.clean_p == w.counters.p && w.clean_n >= n_counters)) {
         SR_HIP(hipMemsetAsync(w.counters.p, 0, n_counters * sizeof(int), ctx().stream));     // the pass's counters, all at once
+    } else if (score_options().verify_clean_counters) {
+        // test hook: what the skip assumes, read back before anything of this pass is launched (a delivering pass is never
+        // captured, so it may wait here); a stale exception count would index the shared-sigma engine's lists out of bounds
+        std::vector<int> h(n_counters);
+        SR_HIP(hipMemcpyAsync(h.data(), w.counters.p, n_counters * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        sync_stream();
+        for (size_t i = 0; i < n_counters; i++)
+            if (h[i] != 0) fail("pass counters not clear before a delivering pass: counter %zu of %zu is %d", i, n_counters, h[i]);
+    }
     w.clean_p = nullptr;
     FinalizeDelivery dl{nullptr, nullptr, 0, 0u};
     if ((flags & SCORE_HOST_DELIVER) && !want_frame_ll && !frame_ll_dst && host_deliverable((size_t)feat.n_utt, (size_t)S)) {

@@ -26,6 +26,8 @@ struct ScoreOptions {
     int h2s_force_exc = 0;     // testing: send every workgroup of the split-fp16 shared-sigma engine through its exception pass
     int flush_list_cap = 0;    // testing: capacity of the list of (tile, model) pairs in the partial-product band (0 = automatic);
                                // a pass that notes more re-runs with a list of the counted length
+    int verify_clean_counters = 0;  // testing: a delivering pass that skips the counters' clear reads them back first and fails
+                                    // unless every one is zero (sr_set_option("debug_verify_clean_counters", 1))
 };
 
 // The matrix-core engines are used when the expanded form is well conditioned in fp32 and the
@@ -160,6 +162,9 @@ struct ScoreResult {
 // Scores every utterance of `feat` against every model of `set`; leaves results on the device.
 // `frame_ll_dst`: device buffer [S][n_frames] the per-frame values go to instead of the workspace's own.
 ScoreResult score_device(SRModelSet &set, SRBatch &feat, bool want_frame_ll, int flags, float *frame_ll_dst = nullptr);
+// The current device's pass counters may be dirty: the next pass clears them itself.  Whatever writes them without going
+// through score_device -- a replayed serving graph (stream.cpp) -- calls this before it is enqueued.
+void counters_written_elsewhere();
 // Same, then copies what the caller asked for to host memory.
 void score_batch_set(SRModelSet &set, SRBatch &feat, double *sums_out, int *argmax_out,
                      float *frame_ll_out, int flags);

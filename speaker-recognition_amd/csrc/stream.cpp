@@ -226,6 +226,9 @@ int sr_stream_submit(SRStream *s, const int16_t *pcm) {
                 enqueue_tick(s, sl);
                 capture_tick(s, sl);
             } else {
+                // the replayed tick writes the pass counters without score_device seeing it: a delivering pass behind it must
+                // clear them first (a delivering ModelSet.score between submit and collect read this tick's exception counts)
+                counters_written_elsewhere();
                 SR_HIP(hipGraphLaunch(sl.exec, ctx().stream));
             }
         } else {

@@ -220,6 +220,20 @@ def test_bad_mfcc_parameters_rejected(built_lib):
         MfccExtractor(16000, win_length_ms=200)   # frame longer than the FFT
 
 
+def test_verify_clean_counters_option_host_side(built_lib):
+    """The test hook of tests/test_gpu_interleave.py is a host-side option: 0 and 1 are taken, anything else is refused with a
+    message naming it, and none of it needs a GPU."""
+    from speaker_recognition_amd import _lib
+    try:
+        for v in (1, 0, 1):
+            _lib.set_option("debug_verify_clean_counters", v)
+        for bad in (-1, 2, 7):
+            with pytest.raises(_lib.SRError, match="debug_verify_clean_counters must be 0 or 1"):
+                _lib.set_option("debug_verify_clean_counters", bad)
+    finally:
+        _lib.set_option("debug_verify_clean_counters", 0)
+
+
 def test_compute_fails_loudly_without_gpu(built_lib, oracle_built, gmm_golden):
     """No silent CPU path: with no HIP device every compute call raises."""
     from speaker_recognition_amd import _lib
