@@ -1099,12 +1099,14 @@ int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Pa
                 const double sdd = stats[(size_t)k * REC + DP + d];
                 const double mu_old = gmm.mean[(size_t)k * dim + d];
                 const double shift = sd / Nk[k];             // E_k[x] - mu_old
+                // no responsibility at all (raw N_k 0, the sums above exact zeros): the reference's E_k[x] = sum g x / 1e-6
+                // is 0, not the old mean (gmm.cc:396-412)
+                const double ex = stats[(size_t)k * REC + 2 * DP] == 0 ? 0.0 : mu_old + shift;
                 if (ubm) {                                   // update_means, gmmubm.cc:53-74
                     const double alpha = Nk[k] / (Nk[k] + relevance);
-                    gmm.mean[(size_t)k * dim + d] =
-                        alpha * (mu_old + shift) + (1 - alpha) * ubm->mean[(size_t)k * dim + d];
+                    gmm.mean[(size_t)k * dim + d] = alpha * ex + (1 - alpha) * ubm->mean[(size_t)k * dim + d];
                 } else {                                     // gmm.cc:396-412, :415-437
-                    gmm.mean[(size_t)k * dim + d] = mu_old + shift;
+                    gmm.mean[(size_t)k * dim + d] = ex;
                     // sum g (x - mu_new)^2 = sdd - 2 shift sd + shift^2 N = sdd - N shift^2
                     double var = sdd / Nk[k] - shift * shift;
                     if (var < 0) var = 0;

@@ -266,14 +266,17 @@ void e64_mstep_kernel(const E64Args a) {
         sd += p[d];
         sdd += p[D + d];
     }
-    if (nk == 0.0) nk = 1e-6;                                    // min_n_k, gmm.cc:502-509
+    const bool empty = nk == 0.0;
+    if (empty) nk = 1e-6;                                        // min_n_k, gmm.cc:502-509
     const double mu_old = a.mu[i];
     const double shift = sd / nk;                                // E_k[x] - mu_old
+    // no responsibility at all (raw N_k 0): the reference's E_k[x] = sum g x / 1e-6 is 0, not the old mean (gmm.cc:396-412)
+    const double ex = empty ? 0.0 : mu_old + shift;
     if (a.map) {                                                 // update_means, gmmubm.cc:53-74
         const double alpha = nk / (nk + a.relevance);
-        a.mu[i] = alpha * (mu_old + shift) + (1 - alpha) * a.ubm_mu[i];
+        a.mu[i] = alpha * ex + (1 - alpha) * a.ubm_mu[i];
     } else {                                                     // gmm.cc:396-437
-        a.mu[i] = mu_old + shift;
+        a.mu[i] = ex;
         double var = sdd / nk - shift * shift;                   // sum g (x - mu_new)^2 = sdd - N shift^2
         if (var < 0) var = 0;
         const double sg = fmax(a.min_sigma, sqrt(var));

@@ -18,8 +18,9 @@
 //   Sums: N_k, sum g (x - mu_k), sum g (x - mu_k)^2 about the CURRENT mean (the variance then needs no cancelling subtraction of large
 //     numbers; em.hip's M-step restated), each (mixture, dimension) added up over a workgroup's frames in frame order, the workgroups'
 //     partial sums in workgroup order: the same bits on every run.
-//   M-step: N_k = 0 -> 1e-6 (:502-509); weights N_k / n normalised by their sum (:388-394); mean, then the variance about the NEW mean
-//     (:396-437) floored at sqrt(min_covar); MAP (gmmubm.cc:53-74): means only, relevance 16.
+//   M-step: N_k = 0 -> 1e-6 (:502-509) and E_k[x] = 0 (the reference's sum g x / N_k); weights N_k / n normalised by their sum
+//     (:388-394); mean, then the variance about the NEW mean (:396-437) floored at sqrt(min_covar); MAP (gmmubm.cc:53-74): means only,
+//     relevance 16.
 //   Stop rule (:622-650): after every second iteration the total log-likelihood under the updated model -- which is the denominator
 //     pass of the NEXT iteration's E-step, so it costs nothing: the next E-step is computed, its total compared, and on "too small an
 //     increment" that iteration's M-step is not applied.
@@ -352,11 +353,13 @@ void em_small_fit_kernel(const EmSmallArgs a) {
             const double sd = s_tot[k * REC + d], sdd = s_tot[k * REC + D + d];
             const double nk = s_nk[k], mu_old = s_mu[i];
             const double shift = sd / nk;                           // E_k[x] - mu_old
+            // no responsibility at all (raw N_k 0): the reference's E_k[x] = sum g x / 1e-6 is 0, not the old mean (gmm.cc:396-412)
+            const double ex = s_tot[k * REC + 2 * D] == 0.0 ? 0.0 : mu_old + shift;
             if (a.map) {                                            // update_means, gmmubm.cc:53-74
                 const double alpha = nk / (nk + a.relevance);
-                s_mu[i] = alpha * (mu_old + shift) + (1 - alpha) * a.init[K + 2 * K * D + i];
+                s_mu[i] = alpha * ex + (1 - alpha) * a.init[K + 2 * K * D + i];
             } else {                                                // gmm.cc:396-437
-                s_mu[i] = mu_old + shift;
+                s_mu[i] = ex;
                 double var = sdd / nk - shift * shift;              // sum g (x - mu_new)^2 = sdd - N shift^2
                 if (var < 0) var = 0;
                 s_sg[i] = fmax(a.min_sigma, sqrt(var));

@@ -329,3 +329,35 @@ def test_oracle_zero_weight_mixture_adds_nothing(oracle_built):
     b = go.score_batch(p, X, go.MODE_FASTEXP)
     c = go.score_batch(p, X, 1)
     assert np.max(np.abs(a - c)) < 1e-9 and np.max(np.abs(a - b) / np.maximum(1, np.abs(b))) < 1e-4
+
+
+
+def test_oracle_mixture_without_responsibility_closed_forms(oracle_built):
+    """A mixture that no frame reaches (N_k == 0, replaced by 1e-6, gmm.cc:502-509) has its moments recomputed from
+    scratch: EM mean sum g x / N_k = 0 and sigma the floor sqrt(min_covar) (gmm.cc:396-437), weight (1e-6 / n) over the
+    weights' sum; MAP mean 0 + (1 - alpha) ubm_mean with alpha = 1e-6 / (1e-6 + 16) (gmmubm.cc:53-74).  A weight of
+    exactly 0 takes the same path (w p = 0).  The GPU trainers' degenerate-data tests (tests/test_gpu_em_degenerate.py)
+    rest on these forms."""
+    go = oracle_built
+    rng = np.random.default_rng(41)
+    K, D, n = 5, 4, 300
+    mu = rng.normal(3, 2, (K, D))
+    X = (mu[rng.integers(0, 3, n)] + rng.normal(0, 0.7, (n, D))).astype(np.float32).astype(np.float64)
+    mu[3] += 1000.0                                              # out of reach
+    w = np.full(K, 1.0 / (K - 1))
+    w[4] = 0.0                                                   # no weight
+    start = go.GMMParams(w, mu, np.full((K, D), 0.9))
+    for mc in (1e-3, 0.01, 0.25):
+        p = go.em_iteration(start, X, min_covar=mc)
+        assert np.all(p.mean[3:] == 0.0) and np.all(p.sigma[3:] == np.sqrt(mc)), mc
+        wsum = 1.0 + 2e-6 / n                                    # the live N_k / n add up to 1 (each frame's responsibilities do)
+        assert np.all(np.abs(p.weights[3:] - 1e-6 / n / wsum) <= 1e-9 * p.weights[3:]), (mc, p.weights)
+        assert abs(np.sum(p.weights) - 1.0) < 1e-12 and np.all(np.isfinite(p.mean[:3])) and np.all(p.sigma[:3] > np.sqrt(mc)), mc
+    ubm = go.GMMParams(np.full(K, 1.0 / K), mu, np.full((K, D), 0.9))
+    alpha = 1e-6 / (1e-6 + 16.0)
+    for _ in range(2):                                           # (the second iteration starts from the first's means)
+        q = go.em_iteration(ubm, X, map_relevance=16.0, ubm=ubm)
+        assert np.array_equal(q.mean[3], ubm.mean[3] * (1 - alpha))
+        assert np.all(np.abs(q.mean[3] - ubm.mean[3]) > 5e-5)    # alpha ubm: the size of the error keeping the old mean makes
+        assert np.array_equal(q.weights, ubm.weights) and np.array_equal(q.sigma, ubm.sigma)
+        assert np.all(np.abs(q.mean[[0, 1, 2, 4]] - ubm.mean[[0, 1, 2, 4]]) < 10.0)
