@@ -365,6 +365,20 @@ SRFullSet *sr_fullset_create(SRFullGMM *const *models, int S);
  * (first maximum wins), frame_ll_out [S][n_rows] fp32 or NULL.  sums_out / argmax_out may be NULL. */
 int sr_fullset_score_batch(SRFullSet *set, SRBatch *batch, double *sums_out, int *argmax_out, float *frame_ll_out);
 void sr_fullset_free(SRFullSet *set);
+/* The fused decision on resident PCM: MFCC (+ the extractor's LPC columns, sr_mfcc_set_lpc, nd must then be 0; or + nd orders of
+ * deltas) -> scoring -> per-utterance sums and argmax on the device (fullcov_finalize_kernel) -> one copy back.  The extractor's
+ * output width must equal the set's D.  sums_out [U][S]: the bits of sr_fullset_score_batch on the same features.
+ * argmax_out [U]: the first maximum of sums / frames (float64, as skgmm.GMMSet.predict), -1 for an utterance without frames
+ * (sums 0) -- unlike sr_fullset_score_batch's, which compares the plain sums and gives 0 there.  Either pointer may be NULL. */
+int sr_fullset_predict_pcm_batch(SRMfcc *m, SRFullSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out);
+/* sr_stream_create for a full-covariance set: the same sr_stream_submit / _collect / _free, results as
+ * sr_fullset_predict_pcm_batch's.  flags: 0 or SR_STREAM_GRAPH (any other bit fails). */
+SRStream *sr_stream_create_full(SRMfcc *m, SRFullSet *set, int n_windows, int64_t window_samples, int nd, int flags);
+/* sr_multi_create for full-covariance models: every slot packs its own SRFullSet replica; n_lpc is 0 or an instantiated LPC order
+ * (10, 12, 15, 16, 20: mix_feature's columns, nd 0 then).  sr_multi_predict_pcm's results are sr_fullset_predict_pcm_batch's, bit
+ * for bit, for any slot count and any cut into pieces (its flags are ignored); the other sr_multi_* calls work as for diagonal sets. */
+SRMulti *sr_multi_create_full(SRFullGMM *const *models, int n_models, double fs, double win_length_ms, double win_shift_ms, int fft,
+                              int n_filters, int n_ceps, double pre_emph, int n_lpc, int n_slots);
 
 #ifdef __cplusplus
 }

@@ -245,16 +245,27 @@ class ServingStream:
     """Double-buffered fixed-shape serving session (sr_stream_*): ``n_windows`` windows of
     ``window_samples`` int16 samples per tick; ``submit`` queues a tick (H2D on its own HIP stream,
     overlapping the previous tick's kernels), ``collect`` returns the oldest tick's decisions.
-    ``graph=True`` replays each tick's kernels and result copies as one captured hipGraph."""
+    ``graph=True`` replays each tick's kernels and result copies as one captured hipGraph.
+    ``models`` is a diagonal ``ModelSet`` or a full-covariance ``skgmm.FullSet`` (chosen by type; ``clamp_compat`` does not
+    apply to the latter, whose ticks give ``FullSet.predict_pcm``'s results)."""
 
-    def __init__(self, extractor: MfccExtractor, models: ModelSet, n_windows: int, window_samples: int,
+    def __init__(self, extractor: MfccExtractor, models, n_windows: int, window_samples: int,
                  nd: int = 0, clamp_compat: bool = True, graph: bool = False):
+        from .skgmm import FullSet
         self._keep = (extractor, models)
         self.n_windows, self.window_samples, self.n_models = int(n_windows), int(window_samples), len(models)
-        h = lib().sr_stream_create(extractor._h, models._h, self.n_windows, self.window_samples, int(nd),
-                                   (_lib.SR_CLAMP_COMPAT if clamp_compat else 0) | (_lib.SR_STREAM_GRAPH if graph else 0))
+        if isinstance(models, FullSet):
+            h = lib().sr_stream_create_full(extractor._h, models._h, self.n_windows, self.window_samples, int(nd),
+                                            _lib.SR_STREAM_GRAPH if graph else 0)
+            what = "sr_stream_create_full"
+        elif isinstance(models, ModelSet):
+            h = lib().sr_stream_create(extractor._h, models._h, self.n_windows, self.window_samples, int(nd),
+                                       (_lib.SR_CLAMP_COMPAT if clamp_compat else 0) | (_lib.SR_STREAM_GRAPH if graph else 0))
+            what = "sr_stream_create"
+        else:
+            raise TypeError("models must be a core.ModelSet or an skgmm.FullSet (got %s)" % type(models).__name__)
         if not h:
-            raise SRError("sr_stream_create failed: %s" % _lib.last_error())
+            raise SRError("%s failed: %s" % (what, _lib.last_error()))
         self._h = C.c_void_p(h)
 
     def submit(self, pcm) -> None:
@@ -296,6 +307,26 @@ class MultiPredictor:
         self._h = C.c_void_p(h)
         self.n_models = len(self._keep)
         self.slot_seconds = None
+
+    @classmethod
+    def from_full(cls, gmms, fs, n_slots=0, n_lpc=15, win_length_ms=32, win_shift_ms=16, FFT_SIZE=2048, n_filters=50,
+                  n_ceps=13, pre_emphasis_coef=0.95) -> "MultiPredictor":
+        """The same predictor over full-covariance models (``skgmm.GMM``): every slot packs its own ``FullSet`` replica, and
+        its features are the MFCC + LPC-``n_lpc`` columns (mix_feature; ``nd`` must be 0 then) or, with ``n_lpc=0``, the MFCC
+        with ``nd`` orders of deltas.  Results are ``FullSet.predict_pcm``'s, bit for bit, for any slot count; an utterance
+        without frames gets argmax -1.  ``clamp_compat`` does not apply."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._keep = list(gmms)
+        arr = (C.c_void_p * len(self._keep))(*[g.handle().value for g in self._keep])
+        h = lib().sr_multi_create_full(arr, len(self._keep), float(fs), float(win_length_ms), float(win_shift_ms), int(FFT_SIZE),
+                                       int(n_filters), int(n_ceps), float(pre_emphasis_coef), int(n_lpc), int(n_slots))
+        if not h:
+            raise SRError("sr_multi_create_full failed: %s" % _lib.last_error())
+        self._h = C.c_void_p(h)
+        self.n_models = len(self._keep)
+        self.slot_seconds = None
+        return self
 
     @property
     def n_slots(self) -> int:

@@ -1025,6 +1025,15 @@ int sr_fullset_score_batch(SRFullSet *set, SRBatch *batch, double *sums_out, int
     SR_CATCH(-1)
 }
 
+int sr_fullset_predict_pcm_batch(SRMfcc *m, SRFullSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out) {
+    SR_TRY
+    if (!m || !set || !pcm) fail("null argument");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_fullset_predict_pcm_batch");
+    fullset_predict_pcm(*m, *set, *pcm, nd, sums_out, argmax_out);
+    return 0;
+    SR_CATCH(-1)
+}
+
 void sr_fullset_free(SRFullSet *set) { delete set; }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 // tiles), and shared by the workgroup's 4 waves: 4 T 32 frames per staged copy.  The per-utterance sums are formed by a second
 // kernel from the per-frame values in an order fixed by the utterance alone (lane j of a wave adds frames j, j + 64, ... of the
 // utterance in float64, then a butterfly), so the bits do not depend on tiling or on the batch around the utterance.
+// fullcov_finalize_kernel forms the same sums and, behind them, every utterance's argmax on the device: the serving paths (the
+// fused PCM call, the serving stream, the multi-GPU predictor) bring a decision back in one copy, with no host work in between.
 //
 // Training (float64, the whole fit on the device; em_f64.hip's pattern): an iteration is seven launches -- log densities,
 // log-sum-exp + responsibilities, the mean (lower bound), nk + means, the covariance sums by frame chunks, the per-mixture
@@ -22,6 +24,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -139,6 +142,58 @@ void fullcov_sum_kernel(const float *__restrict__ fll, long n, const int64_t *__
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) sums[(size_t)u * S + m] = s;
+}
+
+// the first maximum in numpy's sense: (a, ia) beats (b, ib) when it is larger, NaN where b is not, or equal with a lower index
+__device__ inline bool fc_better(double a, int ia, double b, int ib) {
+    if (a != a) return b == b || ia < ib;
+    if (b != b) return false;
+    return a > b || (a == b && ia < ib);
+}
+
+// The whole decision on the device: a workgroup per utterance, its waves over the models (wave w: models w, w + FC_FIN_WAVES, ...).
+// Every (utterance, model) sum is formed exactly as fullcov_sum_kernel forms it -- lane j adds frames j, j + 64, ... in float64,
+// then the butterfly 32 ... 1 -- so the bits are the same on every path.  argmax[u] is the first maximum of sums[u][m] / n_u
+// (float64 division, what skgmm.GMMSet.predict computes on the host); an utterance without frames gets sums 0 and argmax -1.
+constexpr int FC_FIN_WAVES = 8;
+__global__ __launch_bounds__(64 * FC_FIN_WAVES)
+void fullcov_finalize_kernel(const float *__restrict__ fll, long n, const int64_t *__restrict__ off, int U, int S,
+                             double *__restrict__ sums, int *__restrict__ argmax) {
+    __shared__ double s_val[FC_FIN_WAVES];
+    __shared__ int s_idx[FC_FIN_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.x;
+    const int64_t b = off[u], e = off[u + 1];
+    const double n_u = (double)(e - b);
+    double best = 0.0;
+    int best_m = -1;
+    for (int m = wave; m < S; m += FC_FIN_WAVES) {
+        const float *row = fll + (size_t)m * n;
+        double s = 0.0;
+        for (int64_t i = b + lane; i < e; i += 64) s += (double)row[i];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) sums[(size_t)u * S + m] = s;
+        const double v = s / n_u;
+        if (best_m < 0 || fc_better(v, m, best, best_m)) {
+            best = v;
+            best_m = m;
+        }
+    }
+    if (lane == 0) {
+        s_val[wave] = best;
+        s_idx[wave] = best_m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double bv = 0.0;
+        int bm = -1;
+        for (int w = 0; w < FC_FIN_WAVES; w++)
+            if (s_idx[w] >= 0 && (bm < 0 || fc_better(s_val[w], s_idx[w], bv, bm))) {
+                bv = s_val[w];
+                bm = s_idx[w];
+            }
+        argmax[u] = e > b ? bm : -1;
+    }
 }
 
 // ---------------------------------------------------------------- training (float64)
@@ -520,12 +575,79 @@ void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S) {
     sync_stream();
 }
 
-void fullset_score(SRFullSet &set, SRBatch &b, double *sums, int *argmax, float *frame_ll) {
+namespace {
+
+void fullset_check(SRFullSet &set, SRBatch &b) {
     if (b.kind != SRBatch::FEATURES) fail("full-covariance scoring needs a feature batch");
     if (b.dim != set.D) fail("batch has %d dims, the models %d", b.dim, set.D);
     ensure_device();
     if (set.device != current_device()) fail("model set lives on device %d, the calling thread is on device %d", set.device, current_device());
     b.bind_device();
+}
+
+// the scoring kernel into set.fll [S][n] (the caller has sized it)
+void fullset_launch_score(SRFullSet &set, const SRBatch &b, hipStream_t st) {
+    const long n = b.n_rows;
+    const int S = set.S;
+    if (set.D <= 32) {
+        const unsigned gx = (unsigned)((n + 4 * 4 * 32 - 1) / (4 * 4 * 32));
+        hipLaunchKernelGGL((fullcov_score_kernel<16, 4>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
+                           set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
+    } else {
+        const unsigned gx = (unsigned)((n + 4 * 2 * 32 - 1) / (4 * 2 * 32));
+        hipLaunchKernelGGL((fullcov_score_kernel<32, 2>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
+                           set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
+    }
+}
+
+}  // namespace
+
+void fullset_reserve(SRFullSet &set, int64_t n_rows, int n_utt) {
+    set.fll.ensure((size_t)set.S * std::max<int64_t>(1, n_rows));
+    set.res.ensure((size_t)std::max(1, n_utt) * set.S + ((size_t)std::max(1, n_utt) + 1) / 2);
+}
+
+const double *fullset_score_device(SRFullSet &set, SRBatch &b) {
+    fullset_check(set, b);
+    const long n = b.n_rows;
+    const int U = b.n_utt, S = set.S;
+    fullset_reserve(set, n, U);
+    hipStream_t st = ctx().stream;
+    ScopedKernelTimer timer(T_SCORE);
+    if (n > 0) fullset_launch_score(set, b, st);
+    if (U > 0)
+        hipLaunchKernelGGL(fullcov_finalize_kernel, dim3((unsigned)U), dim3(64 * FC_FIN_WAVES), 0, st, set.fll.p, n, b.d_offsets.p, U, S,
+                           set.res.p, reinterpret_cast<int *>(set.res.p + (size_t)U * S));
+    SR_HIP(hipGetLastError());
+    return set.res.p;
+}
+
+void fullset_predict_pcm(SRMfcc &m, SRFullSet &set, SRBatch &pcm, int nd, double *sums, int *argmax) {
+    ensure_device();
+    if (set.device != current_device()) fail("model set lives on device %d, the calling thread is on device %d", set.device, current_device());
+    if (nd < 0 || nd > 2) fail("delta order must be 0, 1 or 2");
+    if (m.n_lpc > 0 && nd != 0) fail("LPC columns (mix_feature) come without deltas: use nd = 0");
+    const int dim = m.n_ceps * (nd + 1) + m.n_lpc;
+    if (dim != set.D)
+        fail("the extractor yields %d columns (%d cepstra x %d + %d LPC), the models have %d dims", dim, m.n_ceps, nd + 1, m.n_lpc, set.D);
+    struct Workspace {
+        SRBatch feat;            // reused across calls: a serving loop allocates nothing
+    };
+    SRBatch &feat = per_device<Workspace>().feat;
+    mfcc_extract_batch(m, pcm, nd, 1, feat);
+    const int U = feat.n_utt, S = set.S;
+    const double *res = fullset_score_device(set, feat);
+    // sums and the argmax values behind them: one copy
+    const size_t n_sums = (size_t)U * S, bytes = n_sums * sizeof(double) + (size_t)U * sizeof(int);
+    set.h_res.ensure(n_sums + ((size_t)U + 1) / 2 + 1);
+    if (U > 0) SR_HIP(hipMemcpyAsync(set.h_res.p, res, bytes, hipMemcpyDeviceToHost, ctx().stream));
+    sync_stream();
+    if (sums) std::copy(set.h_res.p, set.h_res.p + n_sums, sums);
+    if (argmax) std::memcpy(argmax, set.h_res.p + n_sums, (size_t)U * sizeof(int));
+}
+
+void fullset_score(SRFullSet &set, SRBatch &b, double *sums, int *argmax, float *frame_ll) {
+    fullset_check(set, b);
     const long n = b.n_rows;
     const int U = b.n_utt, S = set.S;
     set.fll.ensure((size_t)S * std::max(1L, n));
@@ -533,15 +655,7 @@ void fullset_score(SRFullSet &set, SRBatch &b, double *sums, int *argmax, float 
     hipStream_t st = ctx().stream;
     if (n > 0) {
         ScopedKernelTimer timer(T_SCORE);
-        if (set.D <= 32) {
-            const unsigned gx = (unsigned)((n + 4 * 4 * 32 - 1) / (4 * 4 * 32));
-            hipLaunchKernelGGL((fullcov_score_kernel<16, 4>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
-                               set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
-        } else {
-            const unsigned gx = (unsigned)((n + 4 * 2 * 32 - 1) / (4 * 2 * 32));
-            hipLaunchKernelGGL((fullcov_score_kernel<32, 2>), dim3(gx, S), dim3(256), 0, st, b.data.p, n, set.D, set.ns, set.nrb, set.P.p,
-                               set.mu.p, set.c.p, set.d_kbeg.p, set.fll.p);
-        }
+        fullset_launch_score(set, b, st);
         if (U > 0)
             hipLaunchKernelGGL(fullcov_sum_kernel, dim3((unsigned)(((long)U * S + 3) / 4)), dim3(256), 0, st, set.fll.p, n, b.d_offsets.p, U, S,
                                set.sums.p);

@@ -4,6 +4,7 @@
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "mfcc.hpp"
 
 #include "../../include/pygmm_hip.h"
 
@@ -27,6 +28,9 @@ struct SRFullSet {
     sr::DevBuf<int> d_kbeg;
     sr::DevBuf<float> fll;           // [S][n] per-frame log-likelihoods of the last call
     sr::DevBuf<double> sums;         // [U][S]
+    // the device-side decision (fullcov_finalize_kernel): sums [U][S], then argmax [U] as int right behind them -- one copy back
+    sr::DevBuf<double> res;
+    sr::PinnedBuf<double> h_res;     // sr_fullset_predict_pcm_batch's landing place for that copy
 };
 
 namespace sr {
@@ -34,5 +38,12 @@ constexpr int FULL_MAX_D = 64;
 void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out);
 void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S);
 void fullset_score(SRFullSet &set, SRBatch &batch, double *sums, int *argmax, float *frame_ll);
+// Launches only (capturable): scoring + finalize of a feature batch on the calling thread's stream.  Returns set.res: sums [U][S]
+// with int argmax [U] right behind them.  fullset_reserve sizes the set's workspaces up front (a pipeline of pieces reserves for
+// its largest piece, so that no piece reallocates -- a hipFree -- under the kernels of the one before).
+const double *fullset_score_device(SRFullSet &set, SRBatch &feat);
+void fullset_reserve(SRFullSet &set, int64_t n_rows, int n_utt);
+// MFCC (+ LPC columns or deltas) -> scoring -> finalize -> one copy back (sr_fullset_predict_pcm_batch)
+void fullset_predict_pcm(SRMfcc &m, SRFullSet &set, SRBatch &pcm, int nd, double *sums, int *argmax);
 std::vector<int> kmeans_labels(const float *X, long n, int dim, int K, long seed);     // kmeans_init.hip
 }  // namespace sr

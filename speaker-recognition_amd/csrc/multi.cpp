@@ -13,10 +13,15 @@
 // A slot is bound to device `slot % visible devices`, so asking for more slots than GPUs is legal:
 // the surplus slots share a GPU (serialised by that device's lock) -- how the threading is tested
 // on a single-GPU box.
+//
+// sr_multi_create_full builds the same predictor over full-covariance models (SRFullGMM): every slot holds an SRFullSet replica,
+// and a piece runs features (MFCC + LPC columns or deltas) -> full scoring -> fullcov_finalize_kernel -> one copy of its sums
+// with the argmax values behind them.  That log-sum-exp is exact: nothing of a full piece is resolved or scored again afterwards.
 #include "../../include/pygmm_hip.h"
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "gmm_full.hpp"
 #include "gmm_model.hpp"
 #include "mfcc.hpp"
 #include "score.hpp"
@@ -65,7 +70,8 @@ struct SRMulti {
     };
     struct Slot {
         int device = 0;
-        std::unique_ptr<SRModelSet> set;
+        std::unique_ptr<SRModelSet> set;    // diagonal models ...
+        std::unique_ptr<SRFullSet> fset;    // ... or full-covariance ones (sr_multi_create_full)
         Chunk chunk[MULTI_CHUNKS];
         std::vector<int64_t> offsets;
         std::vector<int> utts;              // global utterance indices, in slot order
@@ -83,6 +89,7 @@ struct SRMulti {
     std::unique_ptr<SRMfcc> mfcc;           // host tables shared; device tables per GPU inside
     std::deque<Slot> slots;                // (a slot owns page-locked buffers and events: not movable)
     int n_models = 0;
+    bool full = false;
 };
 
 namespace {
@@ -216,11 +223,21 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
         // link's seconds per frame.  configs[2]: 16.7 Mflop per frame / 700 TFLOP/s + MFCC 2.7 ns = 26.5 ns against 5.8 ns of
         // link: 4.6; configs[1]: 0.93.  The votes below correct a wrong guess.
         if (s.rho_samples == 0 || !(total > s.rho_samples / 2 && total < s.rho_samples * 2)) {
-            const SRModelSet &set = *s.set;
-            double mixtures = 0.0;                         // of all models together (padded to whole records of KB)
-            for (const ChunkDesc &cd : set.host.chunks) mixtures += (double)cd.n_records * KB;
-            const double flops = mixtures * (4.0 * set.host.dim + 6.0);          // per frame
-            const double rate = !set.h2s.params.empty() ? 700e12 : (!set.h2.params.empty() || !set.bx3.params.empty() || !set.shared.params.empty()) ? 350e12 : 60e12;
+            double flops = 0.0, rate = 0.0;
+            if (m->full) {
+                // K (2 D^2 + 3 D + 6) per frame-model, at what gmm_full.hip sustains (profiles/r07_full_cov.json: 99 TFLOP/s with one
+                // row block, D <= 32; 42 with two)
+                const SRFullSet &fs = *s.fset;
+                const double D = fs.D;
+                flops = (double)fs.kbeg[fs.S] * (2.0 * D * D + 3.0 * D + 6.0);
+                rate = fs.D <= 32 ? 99e12 : 42e12;
+            } else {
+                const SRModelSet &set = *s.set;
+                double mixtures = 0.0;                         // of all models together (padded to whole records of KB)
+                for (const ChunkDesc &cd : set.host.chunks) mixtures += (double)cd.n_records * KB;
+                flops = mixtures * (4.0 * set.host.dim + 6.0);          // per frame
+                rate = !set.h2s.params.empty() ? 700e12 : (!set.h2.params.empty() || !set.bx3.params.empty() || !set.shared.params.empty()) ? 350e12 : 60e12;
+            }
             const double dev_s = flops / rate + 2.7e-9;
             const double link_s = (double)m->mfcc->frame_shift * sizeof(int16_t) / 55e9;
             s.schedule = dev_s / link_s >= 3.5 ? 1 : 0;
@@ -247,6 +264,21 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             ch.u1 = std::max(ch.u0, std::min(ch.u1, U));
         }
         for (int c = 1; c < n_chunks; c++) s.chunk[c].u0 = s.chunk[c - 1].u1;      // contiguous cover
+        if (m->full) {
+            // the replica's workspaces sized for the largest piece before anything is queued: no piece reallocates (a hipFree,
+            // which waits for the device) under the kernels of the one before
+            int64_t rows = 0;
+            int utts = 0;
+            for (int c = 0; c < n_chunks; c++) {
+                int64_t r = 0;
+                for (int i = s.chunk[c].u0; i < s.chunk[c].u1; i++)
+                    r += std::max<int64_t>(0, mfcc_num_frames(*m->mfcc, s.offsets[i + 1] - s.offsets[i]) - nd);
+                rows = std::max(rows, r);
+                utts = std::max(utts, s.chunk[c].u1 - s.chunk[c].u0);
+            }
+            std::lock_guard<std::recursive_mutex> lock(api_mutex());
+            fullset_reserve(*s.fset, rows, utts);
+        }
         // ---- upload: every piece queued on the copy stream, an event behind it
         for (int c = 0; c < n_chunks; c++) {
             auto &ch = s.chunk[c];
@@ -300,6 +332,16 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             std::lock_guard<std::recursive_mutex> lock(api_mutex());
             SR_HIP(hipStreamWaitEvent(ctx().stream, ch.uploaded, 0));
             mfcc_extract_with(*m->mfcc, b, nd, 1, ch.feat, ch.scratch);
+            if (m->full) {
+                // sums and the argmax values right behind them, in one copy; no flags, no list (the log-sum-exp is exact)
+                const double *res = fullset_score_device(*s.fset, ch.feat);
+                SR_HIP(hipMemcpyAsync(ch.h_sums.p, res, (size_t)nu * S * sizeof(double) + (size_t)nu * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+                ch.h_arg = reinterpret_cast<int *>(ch.h_sums.p + (size_t)nu * S);
+                ch.tiles = nullptr;
+                ch.flush_cap = 0;
+                SR_HIP(hipEventRecord(ch.done, ctx().stream));
+                continue;
+            }
             const ScoreResult r = score_device(*s.set, ch.feat, false, flags);
             // (the pass's two counters and its sums + argmax lie side by side in the workspace: one copy each instead of two -- a copy
             // is ~8 us on the stream, and eight pieces' small operations are what keeps the call above max(copy, kernels))
@@ -438,6 +480,52 @@ SRMulti *sr_multi_create(GMM *const *models, int n_models, double fs, double win
     }
 }
 
+SRMulti *sr_multi_create_full(SRFullGMM *const *models, int n_models, double fs, double win_length_ms, double win_shift_ms, int fft_size,
+                              int n_filters, int n_ceps, double pre_emphasis, int n_lpc, int n_slots) {
+    try {
+        if (!models || n_models <= 0) fail("empty model list");
+        if (n_lpc != 0 && n_lpc != 10 && n_lpc != 12 && n_lpc != 15 && n_lpc != 16 && n_lpc != 20)
+            fail("LPC order %d is not instantiated (10, 12, 15, 16, 20; 0 = off)", n_lpc);
+        for (int i = 0; i < n_models; i++)
+            if (!models[i]) fail("null model handle in model list");
+        if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_multi_create_full");
+        const int visible = visible_devices();
+        if (visible <= 0) fail("no HIP device available; lib/pygmm.so has no CPU path");
+        if (n_slots <= 0) n_slots = visible;
+        if (n_slots > 64) fail("at most 64 slots");
+        auto m = std::make_unique<SRMulti>();
+        m->mfcc = std::make_unique<SRMfcc>(fs, win_length_ms, win_shift_ms, fft_size, n_filters, n_ceps, pre_emphasis);
+        m->mfcc->n_lpc = n_lpc;
+        m->n_models = n_models;
+        m->full = true;
+        m->slots.resize((size_t)n_slots);
+        const int prev = current_device();
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_slots; i++) {
+            m->slots[i].device = i % visible;
+            th.emplace_back([&, i]() {
+                auto &s = m->slots[i];
+                try {
+                    set_thread_device(s.device);
+                    std::lock_guard<std::recursive_mutex> lock(api_mutex());
+                    s.fset = std::make_unique<SRFullSet>();
+                    fullset_pack(*s.fset, models, n_models);
+                } catch (const std::exception &e) {
+                    s.error = e.what();
+                }
+            });
+        }
+        for (auto &t : th) t.join();
+        set_thread_device(prev);
+        for (auto &s : m->slots)
+            if (!s.error.empty()) fail("device %d: %s", s.device, s.error.c_str());
+        return m.release();
+    } catch (const std::exception &e) {
+        set_error("%s", e.what());
+        return nullptr;
+    }
+}
+
 void sr_multi_free(SRMulti *m) {
     if (!m || gpu_runtime_lost()) return;     // (a forked child leaves its parent's device state alone: common.hpp)
     const int prev = current_device();
@@ -447,6 +535,7 @@ void sr_multi_free(SRMulti *m) {
             std::lock_guard<std::recursive_mutex> lock(api_mutex());
             (void)hipSetDevice(s.device);
             s.set.reset();
+            s.fset.reset();
             for (auto &ch : s.chunk) {
                 ch.pcm.reset();
                 if (ch.uploaded) (void)hipEventDestroy(ch.uploaded);
@@ -504,6 +593,12 @@ int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_o
             if (sample_offsets[u + 1] < sample_offsets[u]) fail("sample_offsets must be non-decreasing");
         if (sample_offsets[n_utt] > 0 && !pcm) fail("null PCM pointer");
         if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_multi_predict_pcm");
+        if (m->full) {
+            if (nd < 0 || nd > 2) fail("delta order must be 0, 1 or 2");
+            if (m->mfcc->n_lpc > 0 && nd != 0) fail("LPC columns (mix_feature) come without deltas: use nd = 0");
+            const int dim = m->mfcc->n_ceps * (nd + 1) + m->mfcc->n_lpc, D = m->slots.front().fset->D;
+            if (dim != D) fail("the extractor yields %d columns, the models have %d dims", dim, D);
+        }
         // Slots that share a device are ONE queue on it (round 4): the device's lock would serialise their pieces anyway, in
         // an order nobody chose, with both slots' tails at the end.  The first slot of a device takes the work of all of them
         // (sr_set_option("multi_merge_same_device", 0): every slot its own share and thread -- what the tests of the threaded

@@ -7,11 +7,16 @@
 // slot into a hipGraph and replayed with one hipGraphLaunch: the tick is launch-bound at small
 // n_windows.  The graph holds raw pointers into the library's cached workspaces, so it is
 // re-captured whenever any of them was reallocated or rewritten since (g_devbuf_epoch).
+// sr_stream_create_full serves a full-covariance set (SRFullSet) instead: the tick is MFCC (+ LPC columns or deltas) -> scoring
+// -> fullcov_finalize_kernel -> one copy of the sums with the argmax values behind them.  Its log-sum-exp is exact (no saturation,
+// no partial-product band): nothing of such a tick is ever scored again at collect, and it touches none of the diagonal pass
+// counters.
 // (The reference's conversation loop -- gui.py:179-214 -- polls a 1.5 s window every 0.4 s; its
 // VAD front end is third-party and out of scope.)
 #include "../../include/pygmm_hip.h"
 
 #include "batch.hpp"
+#include "gmm_full.hpp"
 #include "mfcc.hpp"
 #include "score.hpp"
 
@@ -23,7 +28,8 @@
 
 struct SRStream {
     SRMfcc *mfcc = nullptr;
-    SRModelSet *set = nullptr;
+    SRModelSet *set = nullptr;           // a diagonal session ...
+    SRFullSet *fset = nullptr;           // ... or a full-covariance one: exactly one of the two is set
     int n_windows = 0, nd = 0, n_models = 0, flags = 0;
     int64_t window_samples = 0;
     hipStream_t copy_stream = nullptr;
@@ -74,6 +80,13 @@ void stream_destroy(SRStream *s) {
 // pinned buffers.  Launches only (every table is cached after the first pass over this shape).
 void enqueue_tick(SRStream *s, SRStream::Slot &sl) {
     mfcc_extract_batch(*s->mfcc, sl.pcm, s->nd, 1, sl.feat);
+    if (s->fset) {
+        // sums [n_windows][S] and the argmax values right behind them, as the slot's pinned buffer holds them: one copy
+        const double *res = fullset_score_device(*s->fset, sl.feat);
+        const size_t n_sums = (size_t)s->n_windows * s->n_models;
+        SR_HIP(hipMemcpyAsync(sl.h_sums, res, n_sums * sizeof(double) + (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        return;
+    }
     const ScoreResult r = score_device(*s->set, sl.feat, false, s->flags & 0xff);
     // (sl.h_oor is cleared by sr_stream_submit BEFORE anything of the tick is enqueued, not here: this function also runs under
     // stream capture right behind a plain pass of the same slot, and a host-side clear at that point races with the plain pass's
@@ -133,15 +146,22 @@ void capture_tick(SRStream *s, SRStream::Slot &sl) {
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-SRStream *sr_stream_create(SRMfcc *m, SRModelSet *set, int n_windows, int64_t window_samples, int nd,
-                           int flags) {
+SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windows, int64_t window_samples, int nd, int flags) {
     try {
         std::lock_guard<std::recursive_mutex> _api_lock(api_mutex());
         ensure_device();
-        if (!m || !set || n_windows <= 0 || window_samples <= 0) fail("bad arguments to sr_stream_create");
+        if (!m || !(set || fset) || n_windows <= 0 || window_samples <= 0) fail("bad arguments to sr_stream_create");
         if (mfcc_num_frames(*m, window_samples) - nd <= 0) fail("window of %lld samples yields no frames", (long long)window_samples);
+        if (fset) {
+            if (fset->device != current_device())
+                fail("model set lives on device %d, the calling thread is on device %d", fset->device, current_device());
+            if (nd < 0 || nd > 2) fail("delta order must be 0, 1 or 2");
+            if (m->n_lpc > 0 && nd != 0) fail("LPC columns (mix_feature) come without deltas: use nd = 0");
+            const int dim = m->n_ceps * (nd + 1) + m->n_lpc;
+            if (dim != fset->D) fail("the extractor yields %d columns, the models have %d dims", dim, fset->D);
+        }
         // owned by a guard until every step below has succeeded (pinned buffers, events and the
         // copy stream are released by stream_destroy on any failure)
         std::unique_ptr<SRStream, void (*)(SRStream *)> guard(new SRStream(), stream_destroy);
@@ -149,11 +169,12 @@ SRStream *sr_stream_create(SRMfcc *m, SRModelSet *set, int n_windows, int64_t wi
         s->device = current_device();
         s->mfcc = m;
         s->set = set;
+        s->fset = fset;
         s->n_windows = n_windows;
         s->window_samples = window_samples;
         s->nd = nd;
         s->flags = flags;
-        s->n_models = set->host.n_models;
+        s->n_models = fset ? fset->S : set->host.n_models;
         SR_HIP(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
         const size_t n_samp = (size_t)n_windows * window_samples;
         for (auto &sl : s->slot) {
@@ -180,7 +201,8 @@ SRStream *sr_stream_create(SRMfcc *m, SRModelSet *set, int n_windows, int64_t wi
             // one synchronous pass per slot builds every table / workspace for this shape, so the
             // steady state launches kernels only
             mfcc_extract_batch(*m, sl.pcm, nd, 1, sl.feat);
-            (void)score_device(*set, sl.feat, false, flags & 0xff);
+            if (fset) (void)fullset_score_device(*fset, sl.feat);
+            else (void)score_device(*set, sl.feat, false, flags & 0xff);
             sync_stream();
         }
         return guard.release();
@@ -188,6 +210,27 @@ SRStream *sr_stream_create(SRMfcc *m, SRModelSet *set, int n_windows, int64_t wi
         set_error("%s", e.what());
         return nullptr;
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+SRStream *sr_stream_create(SRMfcc *m, SRModelSet *set, int n_windows, int64_t window_samples, int nd,
+                           int flags) {
+    return stream_create(m, set, nullptr, n_windows, window_samples, nd, flags);
+}
+
+SRStream *sr_stream_create_full(SRMfcc *m, SRFullSet *set, int n_windows, int64_t window_samples, int nd, int flags) {
+    try {
+        if (flags & ~SR_STREAM_GRAPH) fail("sr_stream_create_full accepts SR_STREAM_GRAPH only (flags 0x%x)", flags);
+        if (!m || !set) fail("bad arguments to sr_stream_create_full");
+        if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_stream_create_full");
+    } catch (const std::exception &e) {
+        set_error("%s", e.what());
+        return nullptr;
+    }
+    return stream_create(m, nullptr, set, n_windows, window_samples, nd, flags);
 }
 
 void sr_stream_free(SRStream *s) {
@@ -225,6 +268,9 @@ int sr_stream_submit(SRStream *s, const int16_t *pcm) {
                 // (re)build: one plain pass first so that every cache reflects this shape, then capture
                 enqueue_tick(s, sl);
                 capture_tick(s, sl);
+            } else if (s->fset) {
+                // (a full-covariance tick writes none of the diagonal pass counters)
+                SR_HIP(hipGraphLaunch(sl.exec, ctx().stream));
             } else {
                 // the replayed tick writes the pass counters without score_device seeing it: a delivering pass behind it must
                 // clear them first (a delivering ModelSet.score between submit and collect read this tick's exception counts)
@@ -256,7 +302,7 @@ int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *de
         s->in_flight.pop_front();
         auto &sl = s->slot[k];
         SR_HIP(hipEventSynchronize(sl.done));
-        if (sl.h_oor[0] != 0 || sl.h_oor[1] != 0) {
+        if (!s->fset && (sl.h_oor[0] != 0 || sl.h_oor[1] != 0)) {
             // a frame of this tick left the fp16 engine's range (-> the fp32-grade engines), or sits in the band where the
             // reference's partial-product flushes decide (-> resolved by fetch_results): its features are still in the
             // slot -- score them again, synchronously

@@ -110,12 +110,30 @@ class ModelInterface(object):
         """Extension: [(fs, signal), ...] -> labels, every utterance scored in one batch.  ``gpus`` != 1
         (0 = every visible GPU) shards the utterances over the GPUs of the node from this one process
         (core.MultiPredictor: a host thread and a model replica per GPU, no collective) -- for diagonal models on the
-        MFCC-only feature (``lpc=False``) on int16 audio of one sampling rate; anything else (full-covariance models among it)
-        takes the one-GPU path."""
+        MFCC-only feature (``lpc=False``), and for full-covariance models on either feature (``MultiPredictor.from_full``),
+        on int16 audio of one sampling rate; anything else takes the one-GPU path.
+        One difference on the sharded full-covariance route: an utterance of 5 frames' length or less, which the one-GPU path
+        refuses ("Signal too short!"), is scored when it yields at least one frame and gets ``None`` when it yields none (as on
+        the diagonal sharded route)."""
         items = list(items)
         rates = {fs for fs, _ in items}
-        if gpus != 1 and getattr(self, "covariance_type", "diag") == "diag" and not self.lpc and len(rates) == 1 and items and \
-                all(np.asarray(sig).dtype == np.int16 and np.asarray(sig).ndim == 1 for _, sig in items):
+        full = getattr(self, "covariance_type", "diag") == "full"
+        pcm_ok = len(rates) == 1 and items and all(np.asarray(sig).dtype == np.int16 and np.asarray(sig).ndim == 1 for _, sig in items)
+        if gpus != 1 and full and pcm_ok:
+            from .core import MultiPredictor
+            kw = dict(self.feature_kwargs)
+            order = kw.pop("n_lpc", 15)
+            fs = rates.pop()
+            # mix_feature's columns: MFCC + LPC-15 when lpc and not diff, else the MFCC with deltas when diff (feature/__init__.py)
+            n_lpc = order if self.lpc and not self.diff else 0
+            nd = self.nd if self.diff else 0
+            key = ("full", tuple((id(g), g._version) for g in self.gmmset.gmms), fs, int(gpus), n_lpc, tuple(sorted(kw.items())))
+            cached = getattr(self, "_multi", None)
+            if cached is None or cached[0] != key:
+                cached = self._multi = (key, MultiPredictor.from_full(self.gmmset.gmms, fs, n_slots=int(gpus), n_lpc=n_lpc, **kw))
+            _, winners = cached[1].predict([sig for _, sig in items], nd=nd)
+            return [None if w < 0 else self.gmmset.y[w] for w in winners]
+        if gpus != 1 and not full and not self.lpc and pcm_ok:
             from .core import MultiPredictor
             kw = dict(self.feature_kwargs)
             fs = rates.pop()

@@ -256,6 +256,28 @@ class FullSet(object):
                                                 _lib.as_fp(fll) if frame_ll else None), "sr_fullset_score_batch")
         return sums, arg, fll
 
+    def predict_pcm(self, extractor, pcm: Batch, nd=0, out=None):
+        """Fused decision on resident PCM (``core.MfccExtractor.predict_batch`` for full-covariance sets): MFCC (+ the
+        extractor's LPC columns, or ``nd`` orders of deltas) -> scoring -> per-utterance sums and argmax on the device -> one copy
+        back.  -> (sums float64[U, S], argmax int32[U]).  The sums are ``score``'s bits on the same features; argmax is the
+        first maximum of sums / frames (as ``GMMSet.predict``), -1 for an utterance too short to yield a frame.  ``out`` =
+        (float64[U, S], int32[U]) C-contiguous arrays to fill instead of fresh ones."""
+        U, S = pcm.n_utt, self.size
+        if out is None:
+            sums = np.zeros((U, S), dtype=np.float64)
+            arg = np.full(U, -1, dtype=np.int32)
+        else:
+            sums, arg = out
+            if sums.shape != (U, S) or sums.dtype != np.float64 or not sums.flags.c_contiguous or arg.shape != (U,) or \
+                    arg.dtype != np.int32 or not arg.flags.c_contiguous:
+                raise ValueError("out must be (float64[%d, %d], int32[%d]), C-contiguous" % (U, S, U))
+        _lib.check(lib().sr_fullset_predict_pcm_batch(extractor._h, self._h, pcm._h, int(nd), _lib.as_dp(sums), _lib.as_i32p(arg)),
+                   "sr_fullset_predict_pcm_batch")
+        return sums, arg
+
+    def __len__(self):
+        return self.size
+
     def __del__(self):
         try:
             if self._h is not None:
