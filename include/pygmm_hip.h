@@ -380,6 +380,21 @@ SRStream *sr_stream_create_full(SRMfcc *m, SRFullSet *set, int n_windows, int64_
 SRMulti *sr_multi_create_full(SRFullGMM *const *models, int n_models, double fs, double win_length_ms, double win_shift_ms, int fft,
                               int n_filters, int n_ceps, double pre_emph, int n_lpc, int n_slots);
 
+/* A serving session with the voice-activity front end of the reference's conversation loop (ModelInterface.filter, then predict,
+ * per window) on the device: per tick and window, LTSD of the window as an utterance of its own (sr_ltsd_compute's values), the
+ * double-threshold rule (a voiced run: a maximal run of analysis windows above lambda0 that holds one above lambda1; the float32
+ * LTSD value is compared with the float64 threshold), the voiced half-hops moved together, and -- when more than a third of the
+ * window is voiced and the voiced samples yield a frame -- the decision the fused call gives for the voiced samples as one
+ * utterance: sr_fullset_predict_pcm_batch's bits for a full-covariance set; for a diagonal set the sum of the per-frame values in
+ * a fixed order and its first maximum.  A window that is not scored has sums 0 and argmax -1.  Exactly one of `set` and `fullset`
+ * is given; nd must be 0; flags: SR_STREAM_GRAPH, and SR_CLAMP_COMPAT for a diagonal set; ltsd_window = int(0.04644 * fs);
+ * noise_amp [ltsd_window / 2 + 1] as sr_ltsd_noise_spectrum gives it.  Submit with sr_stream_submit; sr_stream_collect_vad is
+ * sr_stream_collect plus voiced_out [n_windows], each window's voiced samples (NULL: not wanted; non-NULL on a session without
+ * the front end fails). */
+SRStream *sr_stream_create_vad(SRMfcc *m, SRModelSet *set, SRFullSet *fullset, int n_windows, int64_t window_samples, int nd, int flags,
+                               int ltsd_window, int order, const float *noise_amp, double lambda0, double lambda1);
+int sr_stream_collect_vad(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ EXT_SYMBOLS = [
     "sr_mfma_peak_probe", "sr_mfma_streamed_probe", "sr_kmeans_fast_stats",
     "sr_fullgmm_create", "sr_fullgmm_fit", "sr_fullgmm_info", "sr_fullgmm_get", "sr_fullgmm_free", "sr_fullset_create",
     "sr_fullset_score_batch", "sr_fullset_free", "sr_fullset_predict_pcm_batch", "sr_stream_create_full", "sr_multi_create_full",
+    "sr_stream_create_vad", "sr_stream_collect_vad",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -175,6 +176,8 @@ def lib():
         "sr_fullset_predict_pcm_batch": (i32, [vp, vp, vp, i32, dp, C.POINTER(i32)]),
         "sr_stream_create_full": (vp, [vp, vp, i32, i64, i32, i32]),
         "sr_multi_create_full": (vp, [C.POINTER(vp), i32, dbl, dbl, dbl, i32, i32, i32, dbl, i32, i32]),
+        "sr_stream_create_vad": (vp, [vp, vp, vp, i32, i64, i32, i32, i32, i32, fp, dbl, dbl]),
+        "sr_stream_collect_vad": (i32, [vp, dp, C.POINTER(i32), C.POINTER(i32), dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

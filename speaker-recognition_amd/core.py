@@ -241,20 +241,52 @@ class MfccExtractor:
             pass
 
 
+def vad_thresholds(lambda0, lambda1):
+    """The float64 thresholds the device compares a float32 LTSD value with so that it decides as ``filters.ltsd.voiced_runs``
+    does under the numpy in use: ``ltsds > lambda0`` (an array against a Python float) and ``np.max(...) > lambda1`` (a float32
+    scalar against one) compare in whatever type numpy promotes to -- float32 for both since NEP 50, float32 and float64 before --
+    and a comparison in float32 is the comparison in float64 against the threshold rounded to float32."""
+    t0 = np.result_type(np.zeros(1, np.float32), float(lambda0))
+    t1 = np.result_type(np.float32(0), float(lambda1))
+    return float(t0.type(lambda0)), float(t1.type(lambda1))
+
+
 class ServingStream:
     """Double-buffered fixed-shape serving session (sr_stream_*): ``n_windows`` windows of
     ``window_samples`` int16 samples per tick; ``submit`` queues a tick (H2D on its own HIP stream,
     overlapping the previous tick's kernels), ``collect`` returns the oldest tick's decisions.
     ``graph=True`` replays each tick's kernels and result copies as one captured hipGraph.
     ``models`` is a diagonal ``ModelSet`` or a full-covariance ``skgmm.FullSet`` (chosen by type; ``clamp_compat`` does not
-    apply to the latter, whose ticks give ``FullSet.predict_pcm``'s results)."""
+    apply to the latter, whose ticks give ``FullSet.predict_pcm``'s results).
+    ``vad``: an initialised ``filters.VAD`` (or ``filters.ltsd.LTSD_VAD``) of the extractor's sampling rate puts the reference's
+    voice-activity front end in front of every window, on the device (sr_stream_create_vad): a window is scored on its voiced
+    samples alone, as ``ModelInterface.filter`` + the fused call would score it, and only if more than a third of it is voiced --
+    otherwise its sums are 0 and its argmax -1.  ``collect`` returns what it always did; the voiced sample counts of the tick
+    collected last are in ``last_voiced`` (``collect_vad`` returns them as a fourth value).  ``nd`` must be 0 then."""
 
     def __init__(self, extractor: MfccExtractor, models, n_windows: int, window_samples: int,
-                 nd: int = 0, clamp_compat: bool = True, graph: bool = False):
+                 nd: int = 0, clamp_compat: bool = True, graph: bool = False, vad=None):
         from .skgmm import FullSet
         self._keep = (extractor, models)
         self.n_windows, self.window_samples, self.n_models = int(n_windows), int(window_samples), len(models)
-        if isinstance(models, FullSet):
+        self.vad, self.last_voiced = vad is not None, None
+        if vad is not None:
+            if not isinstance(models, (FullSet, ModelSet)):
+                raise TypeError("models must be a core.ModelSet or an skgmm.FullSet (got %s)" % type(models).__name__)
+            det = getattr(vad, "ltsd", vad)             # filters.VAD wraps the detector
+            if getattr(det, "noise_amp", None) is None:
+                raise ValueError("vad is not initialised: init_noise / init_params_by_noise first")
+            if float(det.fs) != float(extractor.fs):
+                raise ValueError("the VAD was initialised at %g Hz, the extractor works at %g Hz" % (det.fs, extractor.fs))
+            lam0, lam1 = vad_thresholds(det.lambda0, det.lambda1)
+            na = np.ascontiguousarray(det.noise_amp, dtype=np.float32)
+            full = isinstance(models, FullSet)
+            flags = (_lib.SR_STREAM_GRAPH if graph else 0) | (_lib.SR_CLAMP_COMPAT if clamp_compat and not full else 0)
+            h = lib().sr_stream_create_vad(extractor._h, None if full else models._h, models._h if full else None, self.n_windows,
+                                           self.window_samples, int(nd), flags, int(det.window_size), int(det.order), _lib.as_fp(na),
+                                           lam0, lam1)
+            what = "sr_stream_create_vad"
+        elif isinstance(models, FullSet):
             h = lib().sr_stream_create_full(extractor._h, models._h, self.n_windows, self.window_samples, int(nd),
                                             _lib.SR_STREAM_GRAPH if graph else 0)
             what = "sr_stream_create_full"
@@ -278,8 +310,21 @@ class ServingStream:
         sums = np.empty((self.n_windows, self.n_models), dtype=np.float64)
         arg = np.empty(self.n_windows, dtype=np.int32)
         ms = C.c_double(0)
-        check(lib().sr_stream_collect(self._h, _lib.as_dp(sums), _lib.as_i32p(arg), C.byref(ms)), "sr_stream_collect")
+        if self.vad:
+            voiced = np.empty(self.n_windows, dtype=np.int32)
+            check(lib().sr_stream_collect_vad(self._h, _lib.as_dp(sums), _lib.as_i32p(arg), _lib.as_i32p(voiced), C.byref(ms)),
+                  "sr_stream_collect_vad")
+            self.last_voiced = voiced
+        else:
+            check(lib().sr_stream_collect(self._h, _lib.as_dp(sums), _lib.as_i32p(arg), C.byref(ms)), "sr_stream_collect")
         return sums, arg, ms.value
+
+    def collect_vad(self):
+        """``collect`` of a session with ``vad=``: (sums, argmax, voiced samples per window, device ms)."""
+        if not self.vad:
+            raise SRError("not a voice-activity session: create the stream with vad=")
+        sums, arg, ms = self.collect()
+        return sums, arg, self.last_voiced, ms
 
     def __del__(self):
         try:

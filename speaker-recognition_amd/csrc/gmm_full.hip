@@ -155,15 +155,19 @@ __device__ inline bool fc_better(double a, int ia, double b, int ib) {
 // Every (utterance, model) sum is formed exactly as fullcov_sum_kernel forms it -- lane j adds frames j, j + 64, ... in float64,
 // then the butterfly 32 ... 1 -- so the bits are the same on every path.  argmax[u] is the first maximum of sums[u][m] / n_u
 // (float64 division, what skgmm.GMMSet.predict computes on the host); an utterance without frames gets sums 0 and argmax -1.
+// `cnt` (may be null; the serving stream's voice-activity front end): utterance u is the first cnt[u] rows of its range, the rest of
+// the range is padding -- the sums are those of an utterance of cnt[u] frames.  `plain` != 0: the argmax compares the sums
+// themselves (a diagonal set's decision, gmm_finalize_kernel's) instead of the per-frame means.
 constexpr int FC_FIN_WAVES = 8;
 __global__ __launch_bounds__(64 * FC_FIN_WAVES)
 void fullcov_finalize_kernel(const float *__restrict__ fll, long n, const int64_t *__restrict__ off, int U, int S,
-                             double *__restrict__ sums, int *__restrict__ argmax) {
+                             double *__restrict__ sums, int *__restrict__ argmax, const int *__restrict__ cnt, int plain) {
     __shared__ double s_val[FC_FIN_WAVES];
     __shared__ int s_idx[FC_FIN_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.x;
-    const int64_t b = off[u], e = off[u + 1];
-    const double n_u = (double)(e - b);
+    const int64_t b = off[u];
+    const int64_t e = cnt ? min(b + (int64_t)cnt[u], off[u + 1]) : off[u + 1];
+    const double n_u = plain ? 1.0 : (double)(e - b);
     double best = 0.0;
     int best_m = -1;
     for (int m = wave; m < S; m += FC_FIN_WAVES) {
@@ -617,9 +621,26 @@ const double *fullset_score_device(SRFullSet &set, SRBatch &b) {
     if (n > 0) fullset_launch_score(set, b, st);
     if (U > 0)
         hipLaunchKernelGGL(fullcov_finalize_kernel, dim3((unsigned)U), dim3(64 * FC_FIN_WAVES), 0, st, set.fll.p, n, b.d_offsets.p, U, S,
-                           set.res.p, reinterpret_cast<int *>(set.res.p + (size_t)U * S));
+                           set.res.p, reinterpret_cast<int *>(set.res.p + (size_t)U * S), (const int *)nullptr, 0);
     SR_HIP(hipGetLastError());
     return set.res.p;
+}
+
+void masked_finalize(const float *fll, long n, const int64_t *d_off, const int *d_cnt, int U, int S, bool plain, double *d_sums, int *d_argmax) {
+    if (U <= 0) return;
+    hipLaunchKernelGGL(fullcov_finalize_kernel, dim3((unsigned)U), dim3(64 * FC_FIN_WAVES), 0, ctx().stream, fll, n, d_off, U, S, d_sums,
+                       d_argmax, d_cnt, plain ? 1 : 0);
+    SR_HIP(hipGetLastError());
+}
+
+void fullset_score_device_masked(SRFullSet &set, SRBatch &b, const int *d_cnt, double *d_res) {
+    fullset_check(set, b);
+    const long n = b.n_rows;
+    const int U = b.n_utt, S = set.S;
+    set.fll.ensure((size_t)S * std::max(1L, n));
+    ScopedKernelTimer timer(T_SCORE);
+    if (n > 0) fullset_launch_score(set, b, ctx().stream);
+    masked_finalize(set.fll.p, n, b.d_offsets.p, d_cnt, U, S, false, d_res, reinterpret_cast<int *>(d_res + (size_t)U * S));
 }
 
 void fullset_predict_pcm(SRMfcc &m, SRFullSet &set, SRBatch &pcm, int nd, double *sums, int *argmax) {

@@ -42,6 +42,12 @@ void fullset_score(SRFullSet &set, SRBatch &batch, double *sums, int *argmax, fl
 // with int argmax [U] right behind them.  fullset_reserve sizes the set's workspaces up front (a pipeline of pieces reserves for
 // its largest piece, so that no piece reallocates -- a hipFree -- under the kernels of the one before).
 const double *fullset_score_device(SRFullSet &set, SRBatch &feat);
+// The serving stream's voice-activity front end: utterance u is the first d_cnt[u] rows (a device table) of its slot in `feat`.
+// Results go to the caller's d_res: sums [U][S], then argmax [U] as int.  An utterance with d_cnt[u] == 0 gets sums 0, argmax -1.
+void fullset_score_device_masked(SRFullSet &set, SRBatch &feat, const int *d_cnt, double *d_res);
+// fullcov_finalize_kernel over any per-frame values fll [S][n]: utterance u's sum over rows [d_off[u], d_off[u] + d_cnt[u]) in the
+// fixed order of that kernel; argmax of the means, or of the sums themselves when `plain` (a diagonal set's decision)
+void masked_finalize(const float *fll, long n, const int64_t *d_off, const int *d_cnt, int U, int S, bool plain, double *d_sums, int *d_argmax);
 void fullset_reserve(SRFullSet &set, int64_t n_rows, int n_utt);
 // MFCC (+ LPC columns or deltas) -> scoring -> finalize -> one copy back (sr_fullset_predict_pcm_batch)
 void fullset_predict_pcm(SRMfcc &m, SRFullSet &set, SRBatch &pcm, int nd, double *sums, int *argmax);

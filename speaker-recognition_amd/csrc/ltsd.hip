@@ -245,4 +245,134 @@ void ltsd_compute(SRBatch &pcm, int N, int order, const float *noise_amp, float 
     sync_stream();
 }
 
+// ---------------- the serving stream's front end (stream.cpp): decision + compaction, launch-only LTSD ----------------
+
+// The Schmitt rule of filters/ltsd.py:voiced_runs and the reference's one-third rule (interface.py:43-53) for ONE serving window per
+// workgroup, on the device: a voiced run is a maximal run of analysis windows with LTSD > lambda0 that holds one with LTSD > lambda1
+// (float32 value against the float64 threshold); the voiced samples are [s * half, (f + 1) * half) of every run (s, f), in order:
+// half-hop h of the window is voiced exactly when analysis window h is.  The voiced half-hops are copied to the front of the
+// window's slot in `dst` and the rest of the slot is zeroed; voiced[u] = L (always reported), frames[u] = T = the frames of L
+// samples when 3 L > W, else 0: the range every reduction behind this kernel takes (cmvn_delta_kernel, fullcov_finalize_kernel).
+// The marks are a few dozen values (42 analysis windows per second at 8 kHz): one lane walks the runs and numbers the voiced
+// half-hops, then all 256 threads move samples.
+constexpr int VADC_MAX_WN = 4096;        // analysis windows per serving window
+__global__ __launch_bounds__(256)
+void vad_compact_kernel(const int16_t *__restrict__ src, const float *__restrict__ ltsd, int wn, int64_t W, int half, double lambda0,
+                        double lambda1, int frame_len, int frame_shift, int16_t *__restrict__ dst, int *__restrict__ voiced,
+                        int *__restrict__ frames) {
+    __shared__ unsigned char s_above[VADC_MAX_WN];     // 1: above lambda0; 3: above lambda1 too
+    __shared__ int s_hop_dst[VADC_MAX_WN];             // destination half-hop of every voiced half-hop, -1: not voiced
+    __shared__ int s_n_hops;
+    const int u = blockIdx.x, tid = threadIdx.x;
+    const float *lv = ltsd + (size_t)u * wn;
+    for (int i = tid; i < wn; i += 256) {
+        const double v = (double)lv[i];
+        s_above[i] = v > lambda0 ? (v > lambda1 ? 3 : 1) : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0, i = 0;
+        while (i < wn) {
+            if (!s_above[i]) {
+                s_hop_dst[i++] = -1;
+                continue;
+            }
+            int j = i, strong = 0;
+            while (j < wn && s_above[j]) strong |= s_above[j++] & 2;
+            for (int h = i; h < j; h++) s_hop_dst[h] = strong ? n++ : -1;
+            i = j;
+        }
+        s_n_hops = n;
+    }
+    __syncthreads();
+    const int64_t L = (int64_t)s_n_hops * half;
+    const int16_t *sp = src + (size_t)u * W;
+    int16_t *dp = dst + (size_t)u * W;
+    // (half is odd at 8 kHz -- 185 -- so a half-hop's source and destination are not aligned alike: 2-byte accesses, consecutive
+    // lanes on consecutive samples)
+    const int64_t covered = (int64_t)wn * half;           // < W by the definition of wn
+    for (int64_t i = tid; i < covered; i += 256) {
+        const int h = (int)(i / half);
+        const int d = s_hop_dst[h];
+        if (d >= 0) dp[(int64_t)d * half + (i - (int64_t)h * half)] = sp[i];
+    }
+    for (int64_t i = L + tid; i < W; i += 256) dp[i] = 0;
+    if (tid == 0) {
+        voiced[u] = (int)L;
+        int T = 0;
+        if (3 * L > W && L > 5 * (int64_t)frame_len) T = (int)((L - frame_len) / frame_shift + 1);     // mfcc_num_frames
+        frames[u] = T;
+    }
+}
+
+struct LtsdSession {
+    int N = 0, order = 0, n_utt = 0, wn = 0;
+    int64_t W = 0;
+    double lambda0 = 0, lambda1 = 0;
+    DevBuf<float> amp, ltsd, inv_noise;
+    DevBuf<int64_t> win_off;
+    const float *window = nullptr;
+    const float2 *ring = nullptr;
+};
+
+void ltsd_session_check(int64_t W, int N, int order) {
+    if (N < 4 || N > LTSD_MAX_N) fail("LTSD window of %d samples is outside 4..%d", N, LTSD_MAX_N);
+    if (order < 0 || order > 64) fail("LTSD order %d is outside 0..64", order);
+    const int64_t wn = ltsd_num_windows(W, N);
+    if (wn < 1) fail("window of %lld samples is too short for one LTSD analysis window of %d", (long long)W, N);
+    if (wn <= 2 * order)
+        fail("window of %lld samples has %lld LTSD analysis windows: order %d needs more than %d", (long long)W, (long long)wn, order, 2 * order);
+    if (wn > VADC_MAX_WN) fail("window of %lld samples has %lld LTSD analysis windows, more than %d", (long long)W, (long long)wn, VADC_MAX_WN);
+}
+
+LtsdSession *ltsd_session_new(int n_utt, int64_t W, int N, int order, const float *noise_amp, double lambda0, double lambda1) {
+    ltsd_session_check(W, N, order);
+    ensure_device();
+    const int64_t wn = ltsd_num_windows(W, N);
+    std::unique_ptr<LtsdSession> s(new LtsdSession());
+    s->N = N;
+    s->order = order;
+    s->n_utt = n_utt;
+    s->wn = (int)wn;
+    s->W = W;
+    s->lambda0 = lambda0;
+    s->lambda1 = lambda1;
+    LtsdPlan &pl = plan_for(N);
+    s->window = pl.window.p;
+    s->ring = pl.ring.p;
+    const int NB = N / 2 + 1;
+    std::vector<float> inv(NB);
+    for (int k = 0; k < NB; k++) {
+        const double p = (double)noise_amp[k] * (double)noise_amp[k];
+        inv[k] = (float)(1.0 / p);                   // as ltsd_compute
+    }
+    std::vector<int64_t> win_off(n_utt + 1);
+    for (int u = 0; u <= n_utt; u++) win_off[u] = (int64_t)u * wn;
+    s->inv_noise.upload(inv.data(), inv.size());
+    s->win_off.upload(win_off.data(), win_off.size());
+    s->amp.alloc((size_t)n_utt * wn * NB);
+    s->ltsd.alloc((size_t)n_utt * wn);
+    sync_stream();
+    return s.release();
+}
+
+void ltsd_session_delete(LtsdSession *s) { delete s; }
+
+// LTSD of every serving window of `pcm` (int16, n_utt windows of W samples), the decision and the compaction into `dst`: launches only
+void ltsd_session_enqueue(LtsdSession &s, const SRBatch &pcm, int frame_len, int frame_shift, int16_t *dst, int *d_voiced, int *d_frames) {
+    if (pcm.kind != SRBatch::PCM16 || pcm.n_utt != s.n_utt || pcm.n_rows != (int64_t)s.n_utt * s.W) fail("LTSD session: batch of another shape");
+    const int N = s.N, NB = N / 2 + 1, shift = N / 2;
+    const int64_t nw = (int64_t)s.n_utt * s.wn;
+    const size_t lds = (size_t)N * (sizeof(float2) + sizeof(float4));
+    auto kern = ltsd_amp_kernel<int16_t>;
+    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nw + LTSD_WB - 1) / LTSD_WB)), dim3(256), lds, ctx().stream, pcm.pcm16.p, pcm.d_offsets.p,
+                       s.win_off.p, s.n_utt, nw, N, shift, s.window, s.ring, s.amp.p, NB);
+    hipLaunchKernelGGL(ltsd_reduce_kernel, dim3((unsigned)nw), dim3(256), 0, ctx().stream, s.amp.p, s.win_off.p, s.n_utt, NB, N, s.order,
+                       s.inv_noise.p, s.ltsd.p);
+    hipLaunchKernelGGL(vad_compact_kernel, dim3((unsigned)s.n_utt), dim3(256), 0, ctx().stream, pcm.pcm16.p, s.ltsd.p, s.wn, s.W, shift,
+                       s.lambda0, s.lambda1, frame_len, frame_shift, dst, d_voiced, d_frames);
+    SR_HIP(hipGetLastError());
+}
+
 }  // namespace sr

@@ -642,12 +642,15 @@ constexpr int CMVN_THREADS = 1024;    // frames of an utterance go round-robin t
 __global__ __launch_bounds__(CMVN_THREADS)
 void cmvn_delta_kernel(const float *__restrict__ raw, const int64_t *__restrict__ raw_off,
                        const int64_t *__restrict__ out_off, int n_ceps, int nd, int cmvn,
-                       float *__restrict__ out, int out_stride) {
+                       float *__restrict__ out, int out_stride, const int *__restrict__ valid) {
     const int u = blockIdx.x;
     const int64_t r0 = raw_off[u];
-    const int64_t T = raw_off[u + 1] - r0;
+    // `valid` (the serving stream's voice-activity front end, nd == 0): only the first valid[u] rows of the utterance's slot are
+    // frames -- the statistics are theirs alone, in the order an utterance of that many frames gives -- and the rows behind them
+    // become zeros
+    const int64_t T = valid ? min((int64_t)valid[u], raw_off[u + 1] - r0) : raw_off[u + 1] - r0;
     const int64_t o0 = out_off[u];
-    const int64_t To = out_off[u + 1] - o0;
+    const int64_t To = valid ? T : out_off[u + 1] - o0;
     __shared__ double red[CMVN_THREADS];
     __shared__ double s_mean[64], s_inv[64];
     const int tid = threadIdx.x;
@@ -707,6 +710,8 @@ void cmvn_delta_kernel(const float *__restrict__ raw, const int64_t *__restrict_
                 }
             }
         }
+        if (valid)
+            for (int64_t t = To + stripe; t < out_off[u + 1] - o0; t += n_stripes) out[(o0 + t) * out_stride + c] = 0.0f;
     }
 }
 
@@ -877,13 +882,14 @@ MfccScratch *mfcc_scratch_new() { return new MfccScratch(); }
 void mfcc_scratch_delete(MfccScratch *s) { delete s; }
 
 // PCM batch -> feature batch.  `out` is reused when it is large enough (serving loop).
-void mfcc_extract_batch(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out) {
-    mfcc_extract_with(m, pcm, nd, cmvn, out, &per_device<MfccScratch>());     // (the device's own: leaked on purpose, no hipFree at exit)
+void mfcc_extract_batch(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, const int *d_valid_rows) {
+    mfcc_extract_with(m, pcm, nd, cmvn, out, &per_device<MfccScratch>(), d_valid_rows);     // (the device's own: leaked on purpose, no hipFree at exit)
 }
 
-void mfcc_extract_with(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, MfccScratch *scratch) {
+void mfcc_extract_with(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, MfccScratch *scratch, const int *d_valid_rows) {
     ensure_device();
     if (!scratch) fail("null feature workspace");
+    if (d_valid_rows && nd != 0) fail("a device-side frame count comes without deltas: use nd = 0");
     const int u0 = 0, u1 = pcm.n_utt;
     if (pcm.kind != SRBatch::PCM16 && pcm.kind != SRBatch::PCMF32) fail("MFCC needs a PCM batch");
     pcm.bind_device();
@@ -1042,7 +1048,7 @@ void mfcc_extract_with(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, 
     if (U > 0 && out.n_rows > 0) {
         ScopedKernelTimer t(T_CMVN);
         hipLaunchKernelGGL(cmvn_delta_kernel, dim3(U), dim3(CMVN_THREADS), 0, ctx().stream, w.raw.p,
-                           w.raw_off.p, out.d_offsets.p, m.n_ceps, nd, cmvn, out.data.p, out.dim);
+                           w.raw_off.p, out.d_offsets.p, m.n_ceps, nd, cmvn, out.data.p, out.dim, d_valid_rows);
         SR_HIP(hipGetLastError());
     }
     if (m.n_lpc > 0 && NF > 0)   // mix_feature: LPC columns next to the cepstra (same frames, nd == 0)

@@ -25,14 +25,16 @@ struct SRMfcc {
 
 namespace sr {
 int64_t mfcc_num_frames(const SRMfcc &m, int64_t n_samples);
-void mfcc_extract_batch(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out);
+// d_valid_rows (device, [n_utt], nd == 0 only): utterance u has that many frames, not the mfcc_num_frames of its slot -- CMVN takes
+// its statistics over them alone and writes zeros into the slot's other rows (the serving stream's voice-activity front end)
+void mfcc_extract_batch(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, const int *d_valid_rows = nullptr);
 // The feature stage's device workspace (raw cepstra + their frame offsets).  mfcc_extract_batch uses the calling device's own;
 // a caller that alternates between batches of different shapes (the pieces of sr_multi_predict_pcm) keeps one per shape so that
 // the cached offset table is not re-uploaded -- and the stream not synchronised -- on every call.
 struct MfccScratch;
 MfccScratch *mfcc_scratch_new();
 void mfcc_scratch_delete(MfccScratch *s);
-void mfcc_extract_with(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, MfccScratch *scratch);
+void mfcc_extract_with(SRMfcc &m, SRBatch &pcm, int nd, int cmvn, SRBatch &out, MfccScratch *scratch, const int *d_valid_rows = nullptr);
 void mfcc_set_force_generic(bool on);
 void mfcc_set_precision(int mode);       // 2: float64 spectrum / ln / DCT for every frame (default), 0: fp32 throughout
 int mfcc_precision();
@@ -43,5 +45,14 @@ int64_t ltsd_num_windows(int64_t n_samples, int N);
 void ltsd_noise_spectrum(SRBatch &noise, int N, float *avg_amp_out);
 void ltsd_compute(SRBatch &pcm, int N, int order, const float *noise_amp, float *ltsd_out,
                   int64_t *win_offsets_out);
+// The serving stream's voice-activity front end (stream.cpp): every table of a fixed shape -- n_utt windows of W samples -- is
+// prepared once; ltsd_session_enqueue only launches: the two LTSD kernels, then vad_compact_kernel, which applies the Schmitt rule
+// and the one-third rule per window, moves the voiced samples to the front of the window's slot in `dst` (zeros behind them) and
+// writes d_voiced[u] = voiced samples, d_frames[u] = frames to score (0: not scored).
+struct LtsdSession;
+void ltsd_session_check(int64_t W, int N, int order);            // host only: fails on a shape the front end cannot serve
+LtsdSession *ltsd_session_new(int n_utt, int64_t W, int N, int order, const float *noise_amp, double lambda0, double lambda1);
+void ltsd_session_delete(LtsdSession *s);
+void ltsd_session_enqueue(LtsdSession &s, const SRBatch &pcm, int frame_len, int frame_shift, int16_t *dst, int *d_voiced, int *d_frames);
 
 }  // namespace sr

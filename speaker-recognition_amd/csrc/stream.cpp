@@ -11,8 +11,16 @@
 // -> fullcov_finalize_kernel -> one copy of the sums with the argmax values behind them.  Its log-sum-exp is exact (no saturation,
 // no partial-product band): nothing of such a tick is ever scored again at collect, and it touches none of the diagonal pass
 // counters.
-// (The reference's conversation loop -- gui.py:179-214 -- polls a 1.5 s window every 0.4 s; its
-// VAD front end is third-party and out of scope.)
+// sr_stream_create_vad puts the reference's voice-activity front end in front of either tick (its conversation loop --
+// gui.py:179-214 -- is ModelInterface.filter, then predict, per polled window): ltsd_amp_kernel -> ltsd_reduce_kernel ->
+// vad_compact_kernel (ltsd.hip: Schmitt rule, one-third rule, voiced samples to the front of the window's slot in a second PCM
+// buffer, voiced length L and frame count T to device tables) -> the feature kernels over the fixed slots -> CMVN over each slot's
+// first T rows (zeros behind them) -> scoring of every row -> fullcov_finalize_kernel over each slot's first T rows -> one copy of
+// sums, argmax and voiced counts.  Launches only: no sample comes back, no offset is rebuilt on the host, so the tick replays from a
+// graph like the others.  A full-covariance VAD tick is final as it arrives.  A diagonal one runs the scoring pass for its
+// per-frame values and sums them with that same kernel (the engines' own per-utterance sums cover the padding rows too and are
+// not used); when the pass's flags come back set, collect re-scores the slot's features synchronously as below, resolves the
+// partial-product band on the per-frame values (flush_resolve overwrites them) and sums again.
 #include "../../include/pygmm_hip.h"
 
 #include "batch.hpp"
@@ -21,6 +29,7 @@
 #include "score.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -30,6 +39,7 @@ struct SRStream {
     SRMfcc *mfcc = nullptr;
     SRModelSet *set = nullptr;           // a diagonal session ...
     SRFullSet *fset = nullptr;           // ... or a full-covariance one: exactly one of the two is set
+    sr::LtsdSession *vad = nullptr;      // the voice-activity front end (sr_stream_create_vad), or null
     int n_windows = 0, nd = 0, n_models = 0, flags = 0;
     int64_t window_samples = 0;
     hipStream_t copy_stream = nullptr;
@@ -39,6 +49,11 @@ struct SRStream {
         int *h_argmax = nullptr;         // pinned [n_windows]
         int *h_oor = nullptr;            // pinned: the fp16 engines' saturation flag of this tick
         SRBatch pcm, feat;
+        // a VAD session: the compacted windows, and the tick's results as one block -- sums [n_windows][S], argmax [n_windows],
+        // voiced samples [n_windows] (copied back together), then the frame counts [n_windows] the reductions read
+        SRBatch vpcm;
+        sr::DevBuf<double> d_res;
+        int *h_voiced = nullptr;         // pinned, behind h_argmax in the same allocation
         hipEvent_t h2d_done = nullptr, done = nullptr, t_submit = nullptr;
         hipGraphExec_t exec = nullptr;   // SR_STREAM_GRAPH: the captured tick
         long exec_epoch = -1;
@@ -73,12 +88,45 @@ void stream_destroy(SRStream *s) {
         if (sl.exec) (void)hipGraphExecDestroy(sl.exec);
     }
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
+    ltsd_session_delete(s->vad);
     delete s;
 }
 
 // The device side of one tick on the library's stream: kernels + result copies into the slot's
 // pinned buffers.  Launches only (every table is cached after the first pass over this shape).
+int *vad_argmax(SRStream *s, SRStream::Slot &sl) { return reinterpret_cast<int *>(sl.d_res.p + (size_t)s->n_windows * s->n_models); }
+int *vad_frames(SRStream *s, SRStream::Slot &sl) { return vad_argmax(s, sl) + 2 * (size_t)s->n_windows; }
+
+// a diagonal VAD tick's decision from the per-frame values of a pass over the slot's features: each window's first T rows
+void vad_sum_frames(SRStream *s, SRStream::Slot &sl, const ScoreResult &r) {
+    if (!r.d_frame_ll) fail("serving stream: the scoring pass left no per-frame values");
+    masked_finalize(r.d_frame_ll, (long)sl.feat.n_rows, sl.feat.d_offsets.p, vad_frames(s, sl), s->n_windows, s->n_models, true, sl.d_res.p,
+                    vad_argmax(s, sl));
+}
+
+void enqueue_vad_tick(SRStream *s, SRStream::Slot &sl) {
+    int *const d_voiced = vad_argmax(s, sl) + s->n_windows, *const d_frames = vad_frames(s, sl);
+    ltsd_session_enqueue(*s->vad, sl.pcm, s->mfcc->frame_len, s->mfcc->frame_shift, sl.vpcm.pcm16.p, d_voiced, d_frames);
+    mfcc_extract_batch(*s->mfcc, sl.vpcm, 0, 1, sl.feat, d_frames);
+    if (s->fset) {
+        fullset_score_device_masked(*s->fset, sl.feat, d_frames, sl.d_res.p);
+    } else {
+        const ScoreResult r = score_device(*s->set, sl.feat, true, s->flags & 0xff);
+        // (the flags as in a plain tick, below: cleared by sr_stream_submit, written by these copies only)
+        if (r.d_oor && r.d_flush_count == r.d_oor + 1) {
+            SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        } else {
+            if (r.d_oor) SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+            if (r.d_flush_count) SR_HIP(hipMemcpyAsync(sl.h_oor + 1, r.d_flush_count, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        }
+        vad_sum_frames(s, sl, r);
+    }
+    const size_t n_sums = (size_t)s->n_windows * s->n_models;
+    SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, n_sums * sizeof(double) + 2 * (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+}
+
 void enqueue_tick(SRStream *s, SRStream::Slot &sl) {
+    if (s->vad) return enqueue_vad_tick(s, sl);
     mfcc_extract_batch(*s->mfcc, sl.pcm, s->nd, 1, sl.feat);
     if (s->fset) {
         // sums [n_windows][S] and the argmax values right behind them, as the slot's pinned buffer holds them: one copy
@@ -148,7 +196,14 @@ void capture_tick(SRStream *s, SRStream::Slot &sl) {
 
 namespace {
 
-SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windows, int64_t window_samples, int nd, int flags) {
+struct VadParams {
+    int ltsd_window, order;
+    const float *noise_amp;
+    double lambda0, lambda1;
+};
+
+SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windows, int64_t window_samples, int nd, int flags,
+                        const VadParams *vp = nullptr) {
     try {
         std::lock_guard<std::recursive_mutex> _api_lock(api_mutex());
         ensure_device();
@@ -177,12 +232,14 @@ SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windo
         s->n_models = fset ? fset->S : set->host.n_models;
         SR_HIP(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
         const size_t n_samp = (size_t)n_windows * window_samples;
+        if (vp) s->vad = ltsd_session_new(n_windows, window_samples, vp->ltsd_window, vp->order, vp->noise_amp, vp->lambda0, vp->lambda1);
         for (auto &sl : s->slot) {
             SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_pcm), n_samp * sizeof(int16_t), hipHostMallocDefault));
             // sums and, right behind them, the argmax values: as the device keeps them (score_device), one copy per tick
             const size_t n_sums = (size_t)n_windows * s->n_models;
-            SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_sums), n_sums * sizeof(double) + (size_t)n_windows * sizeof(int), hipHostMallocDefault));
+            SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_sums), n_sums * sizeof(double) + (size_t)n_windows * sizeof(int) * (vp ? 2 : 1), hipHostMallocDefault));
             sl.h_argmax = reinterpret_cast<int *>(sl.h_sums + n_sums);
+            if (vp) sl.h_voiced = sl.h_argmax + n_windows;
             SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_oor), 2 * sizeof(int), hipHostMallocDefault));
             sl.h_oor[0] = sl.h_oor[1] = 0;
             SR_HIP(hipEventCreate(&sl.h2d_done));
@@ -198,6 +255,22 @@ SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windo
             SR_HIP(hipMemsetAsync(sl.pcm.pcm16.p, 0, n_samp * sizeof(int16_t), ctx().stream));
             sl.pcm.d_offsets.upload(sl.pcm.offsets.data(), sl.pcm.offsets.size());
             sync_stream();
+            if (vp) {
+                sl.vpcm.bind_device();
+                sl.vpcm.kind = SRBatch::PCM16;
+                sl.vpcm.n_utt = n_windows;
+                sl.vpcm.n_rows = (int64_t)n_samp;
+                sl.vpcm.offsets = sl.pcm.offsets;
+                sl.vpcm.pcm16.alloc(n_samp);
+                sl.vpcm.d_offsets.upload(sl.vpcm.offsets.data(), sl.vpcm.offsets.size());
+                sl.d_res.alloc(n_sums + (3 * (size_t)n_windows + 1) / 2);
+                SR_HIP(hipMemsetAsync(sl.d_res.p, 0, sl.d_res.n * sizeof(double), ctx().stream));
+                sync_stream();
+                enqueue_vad_tick(s, sl);      // (the same synchronous pass, through the front end)
+                sync_stream();
+                sl.h_oor[0] = sl.h_oor[1] = 0;
+                continue;
+            }
             // one synchronous pass per slot builds every table / workspace for this shape, so the
             // steady state launches kernels only
             mfcc_extract_batch(*m, sl.pcm, nd, 1, sl.feat);
@@ -231,6 +304,26 @@ SRStream *sr_stream_create_full(SRMfcc *m, SRFullSet *set, int n_windows, int64_
         return nullptr;
     }
     return stream_create(m, nullptr, set, n_windows, window_samples, nd, flags);
+}
+
+SRStream *sr_stream_create_vad(SRMfcc *m, SRModelSet *set, SRFullSet *fullset, int n_windows, int64_t window_samples, int nd, int flags,
+                               int ltsd_window, int order, const float *noise_amp, double lambda0, double lambda1) {
+    try {
+        if (!m || !noise_amp || (set == nullptr) == (fullset == nullptr))
+            fail("bad arguments to sr_stream_create_vad (an extractor, a noise spectrum and exactly one of the two model sets)");
+        if (n_windows <= 0 || window_samples <= 0) fail("bad arguments to sr_stream_create_vad (%d windows of %lld samples)", n_windows, (long long)window_samples);
+        if (nd != 0) fail("a voice-activity session serves nd = 0 only (deltas over a device-side length are not built): got nd = %d", nd);
+        if (fullset && (flags & ~SR_STREAM_GRAPH)) fail("sr_stream_create_vad accepts SR_STREAM_GRAPH only with a full-covariance set (flags 0x%x)", flags);
+        if (set && (flags & ~(SR_STREAM_GRAPH | SR_CLAMP_COMPAT))) fail("sr_stream_create_vad accepts SR_CLAMP_COMPAT and SR_STREAM_GRAPH (flags 0x%x)", flags);
+        if (!std::isfinite(lambda0) || !std::isfinite(lambda1)) fail("LTSD thresholds must be finite (lambda0 %g, lambda1 %g)", lambda0, lambda1);
+        ltsd_session_check(window_samples, ltsd_window, order);
+        if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_stream_create_vad");
+    } catch (const std::exception &e) {
+        set_error("%s", e.what());
+        return nullptr;
+    }
+    const VadParams vp{ltsd_window, order, noise_amp, lambda0, lambda1};
+    return stream_create(m, set, fullset, n_windows, window_samples, 0, flags, &vp);
 }
 
 void sr_stream_free(SRStream *s) {
@@ -291,12 +384,13 @@ int sr_stream_submit(SRStream *s, const int16_t *pcm) {
     }
 }
 
-int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *device_ms) {
+static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms) {
     try {
         std::lock_guard<std::recursive_mutex> _api_lock(api_mutex());
         if (!s) fail("null stream");
         if (s->device != current_device()) fail("stream lives on device %d, the calling thread is on device %d", s->device, current_device());
         ensure_device();
+        if (voiced_out && !s->vad) fail("not a voice-activity session: no voiced counts (sr_stream_create_vad)");
         if (s->in_flight.empty()) fail("nothing in flight");
         const int k = s->in_flight.front();
         s->in_flight.pop_front();
@@ -307,15 +401,30 @@ int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *de
             // reference's partial-product flushes decide (-> resolved by fetch_results): its features are still in the
             // slot -- score them again, synchronously
             const int fl = (s->flags & 0xff) | (sl.h_oor[0] != 0 ? SCORE_PRECISE : 0);
-            ScoreResult r = score_device(*s->set, sl.feat, false, fl);
-            if (!fetch_results(*s->set, sl.feat, fl, r, sl.h_sums, sl.h_argmax, nullptr)) {
-                r = score_device(*s->set, sl.feat, false, fl | SCORE_PRECISE);
-                fetch_results(*s->set, sl.feat, fl | SCORE_PRECISE, r, sl.h_sums, sl.h_argmax, nullptr);
+            if (s->vad) {
+                // per-frame values again; fetch_results without host destinations resolves the band ON THE DEVICE (flush_resolve
+                // overwrites the per-frame values of the noted pairs), then the same sum over each window's first T rows
+                ScoreResult r = score_device(*s->set, sl.feat, true, fl);
+                if (!fetch_results(*s->set, sl.feat, fl, r, nullptr, nullptr, nullptr)) {
+                    r = score_device(*s->set, sl.feat, true, fl | SCORE_PRECISE);
+                    fetch_results(*s->set, sl.feat, fl | SCORE_PRECISE, r, nullptr, nullptr, nullptr);
+                }
+                vad_sum_frames(s, sl, r);
+                const size_t n_sums = (size_t)s->n_windows * s->n_models;
+                SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, n_sums * sizeof(double) + (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+                sync_stream();
+            } else {
+                ScoreResult r = score_device(*s->set, sl.feat, false, fl);
+                if (!fetch_results(*s->set, sl.feat, fl, r, sl.h_sums, sl.h_argmax, nullptr)) {
+                    r = score_device(*s->set, sl.feat, false, fl | SCORE_PRECISE);
+                    fetch_results(*s->set, sl.feat, fl | SCORE_PRECISE, r, sl.h_sums, sl.h_argmax, nullptr);
+                }
             }
             sl.h_oor[0] = sl.h_oor[1] = 0;
         }
         if (sums_out) std::memcpy(sums_out, sl.h_sums, (size_t)s->n_windows * s->n_models * sizeof(double));
         if (argmax_out) std::memcpy(argmax_out, sl.h_argmax, (size_t)s->n_windows * sizeof(int));
+        if (voiced_out) std::memcpy(voiced_out, sl.h_voiced, (size_t)s->n_windows * sizeof(int));
         if (device_ms) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, sl.t_submit, sl.done);
@@ -327,6 +436,14 @@ int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *de
         set_error("%s", e.what());
         return -1;
     }
+}
+
+int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *device_ms) {
+    return stream_collect(s, sums_out, argmax_out, nullptr, device_ms);
+}
+
+int sr_stream_collect_vad(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms) {
+    return stream_collect(s, sums_out, argmax_out, voiced_out, device_ms);
 }
 
 }  // extern "C"

@@ -10,7 +10,9 @@ signal = concatenation of the intervals (:59-64).
 What the reference leaves to its (unavailable) fork of pyssp and this defines: the decision rule
 that turns LTSD values and the two thresholds into window intervals -- here a double-threshold
 (Schmitt) rule: a voiced interval is a maximal run of windows with LTSD > lambda0 that contains at
-least one window with LTSD > lambda1.  Parity unpinned."""
+least one window with LTSD > lambda1.  Parity unpinned.
+The serving stream applies the same rule on the device, per window, in front of the feature stage
+(``core.ServingStream(..., vad=)``, csrc/ltsd.hip ``vad_compact_kernel``): ``voiced_runs`` stays the definition."""
 import numpy as np
 
 from .. import _lib

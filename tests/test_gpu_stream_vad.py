@@ -1,0 +1,365 @@
+"""The serving stream with the voice-activity front end on the device (sr_stream_create_vad, ServingStream(vad=)): LTSD ->
+Schmitt rule -> one-third rule -> compaction -> MFCC (+ LPC) -> CMVN over the voiced frames -> scoring -> decision, per window,
+launches only (csrc/ltsd.hip vad_compact_kernel, stream.cpp).
+
+Yardstick 1 is the library's own host chain in the same process: ``VAD.filter`` per window, the one-third rule of
+``ModelInterface.filter``, then the fused call on the voiced samples as one utterance.  Both sides take their LTSD values from the
+same two kernels, so no decision can flip: voiced counts and scored / not scored are equal for every window, a full-covariance
+set's sums and argmax are equal bit for bit, a diagonal set's sums agree within the project's gate of 1e-4 per frame
+(|a - b| <= 1e-4 max(T, |b|): the engine may differ between a 61-row slot and a compacted utterance).
+
+Yardstick 2 is the float64 oracle chain (oracle/ltsd_oracle.py -> the rules in numpy -> oracle/mfcc_oracle.py (+ lpc_oracle) ->
+tests/fullcov_oracle.py / gmm_oracle.score_batch).  The VAD leg is "parity unpinned": pyssp, which the reference calls, is absent,
+so the oracle restates the published measure (as tests/test_gpu_vad.py says); windows with an oracle LTSD value within 1e-3
+relative of a threshold are skipped (at most 5 %).  Sums: 1e-4 per frame, summed: |a - b| <= 1e-4 max(T, |b|)."""
+import numpy as np
+import pytest
+
+import fullcov_oracle as fo
+
+pytestmark = pytest.mark.gpu
+FS, WIN, STEP = 8000, 8000, 4000
+
+
+def scene(seed=11):
+    """bench.py:block_stream's scene with bursts and gaps of irregular length: (windows [n][WIN] int16, noise int16)"""
+    from speaker_recognition_amd import synth
+    audio = synth.synth_speech(3, 40.0, FS)
+    rng = np.random.default_rng(seed)
+    gate = np.zeros(len(audio), bool)
+    t, on = 0, True
+    while t < len(audio):
+        d = int(rng.uniform(0.15, 1.2) * FS)
+        gate[t:t + d] = on
+        t, on = t + d, not on
+    frng = np.random.default_rng(5)
+    floor = frng.normal(0, 60, len(audio)).astype(np.int16)
+    sc = (np.where(gate, audio // 2, 0) + floor).astype(np.int16)
+    noise = frng.normal(0, 60, 3 * FS).astype(np.int16)
+    n = (len(sc) - WIN) // STEP
+    return np.stack([sc[i * STEP:i * STEP + WIN] for i in range(n)]), noise
+
+
+def make_vad(noise):
+    from speaker_recognition_amd.filters import VAD
+    vad = VAD()
+    vad.init_noise(FS, noise)
+    return vad
+
+
+def full_setup(n_lpc, S, K, seed=0):
+    from speaker_recognition_amd import skgmm, synth
+    from speaker_recognition_amd.core import MfccExtractor
+    ex = MfccExtractor(FS, n_lpc=n_lpc)
+    X = np.concatenate([ex.extract(synth.synth_speech(9 * s, 2.0, FS, seed=500 + s)) for s in range(S)])
+    rng = np.random.default_rng(seed)
+    D = X.shape[1]
+    cov0 = np.cov(X.T) + 1e-3 * np.eye(D)
+    cov = 0.5 * cov0 + 0.05 * np.diag(np.diag(cov0))
+    gmms = []
+    for _ in range(S):
+        mu = X[rng.choice(len(X), K, replace=False)] + 0.1 * rng.standard_normal((K, D))
+        w = rng.uniform(0.5, 1.5, K)
+        gmms.append(skgmm.GMM.from_arrays(w / w.sum(), mu, np.repeat(cov[None], K, axis=0)))
+    return ex, gmms, skgmm.FullSet(gmms)
+
+
+def diag_setup(S=20, K=256):
+    from speaker_recognition_amd import synth
+    from speaker_recognition_amd.core import MfccExtractor, ModelSet
+    from speaker_recognition_amd.pygmm import GMM
+    raw = [synth.synth_gmm(K, 13, 7 + s) for s in range(S)]
+    return MfccExtractor(FS), raw, ModelSet([GMM.from_arrays(*m) for m in raw])
+
+
+def host_chain(vad, ex, models, windows, clamp_compat=True):
+    """yardstick 1 -> (sums [n][S], argmax [n], voiced [n], frames [n], runs per window)"""
+    from speaker_recognition_amd.core import Batch, ModelSet
+    n, S = len(windows), len(models)
+    sums, arg = np.zeros((n, S)), np.full(n, -1, np.int32)
+    voiced, frames, n_runs = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for i, chunk in enumerate(windows):
+        v, runs = vad.filter(FS, chunk)
+        voiced[i], n_runs[i] = len(v), len(runs)
+        if len(v) > len(chunk) / 3 and ex.num_frames(len(v)) > 0:
+            frames[i] = ex.num_frames(len(v))
+            b = Batch.from_pcm([np.ascontiguousarray(v, dtype=np.int16)])
+            if isinstance(models, ModelSet):
+                s, a = ex.predict_batch(models, b, nd=0, clamp_compat=clamp_compat)
+            else:
+                s, a = models.predict_pcm(ex, b)
+            sums[i], arg[i] = s[0], a[0]
+    return sums, arg, voiced, frames, n_runs
+
+
+def run_stream(st, windows, n_win):
+    """every window through the stream, n_win per tick (the last tick padded with silence), two ticks in flight"""
+    n = len(windows)
+    ticks = []
+    for t0 in range(0, n, n_win):
+        blk = np.zeros((n_win, WIN), np.int16)
+        blk[:min(n_win, n - t0)] = windows[t0:t0 + n_win]
+        ticks.append(blk)
+    out = []
+    st.submit(ticks[0])
+    for t in range(len(ticks)):
+        if t + 1 < len(ticks):
+            st.submit(ticks[t + 1])
+        out.append(st.collect_vad()[:3])
+    return (np.concatenate([o[0] for o in out])[:n], np.concatenate([o[1] for o in out])[:n], np.concatenate([o[2] for o in out])[:n])
+
+
+def check_scene(voiced, frames, n_runs):
+    """what the tests rely on"""
+    n = len(voiced)
+    scored = frames > 0
+    assert len(set(voiced[voiced > 0].tolist())) >= 5, sorted(set(voiced.tolist()))
+    assert scored.sum() >= n / 5 and (~scored).sum() >= n / 5, (int(scored.sum()), n)
+    assert np.any((voiced > 0) & (3 * voiced <= WIN)), "no window that is voiced but rejected by the one-third rule"
+    assert np.any(n_runs >= 2), "no window with two separate runs"
+
+
+@pytest.mark.parametrize("n_lpc,S,K", [(15, 20, 32), (0, 5, 8)])
+def test_full_covariance_stream_equals_the_host_chain_bit_for_bit(n_lpc, S, K):
+    from speaker_recognition_amd.core import ServingStream
+    windows, noise = scene()
+    vad = make_vad(noise)
+    ex, gmms, fset = full_setup(n_lpc, S, K, seed=3 + n_lpc)
+    want_s, want_a, want_v, frames, n_runs = host_chain(vad, ex, fset, windows)
+    check_scene(want_v, frames, n_runs)
+    res = {}
+    for graph in (False, True):
+        for n_win in (1, 6, 64):
+            if graph and n_win == 64:
+                continue
+            st = ServingStream(ex, fset, n_win, WIN, graph=graph, vad=vad)
+            s, a, v = res[(graph, n_win)] = run_stream(st, windows, n_win)
+            print("full n_lpc=%d graph=%s n_win=%d: voiced mismatches %d, argmax mismatches %d, sums max |d| %.3g" % (
+                n_lpc, graph, n_win, int(np.sum(v != want_v)), int(np.sum(a != want_a)), float(np.max(np.abs(s - want_s)))))
+            assert np.array_equal(v, want_v), (graph, n_win)
+            assert np.array_equal(a, want_a), (graph, n_win)
+            assert np.array_equal(s, want_s), (graph, n_win, float(np.max(np.abs(s - want_s))))
+            assert np.all(s[frames == 0] == 0.0) and np.all(a[frames == 0] == -1) and np.all(a[frames > 0] >= 0)
+            del st
+
+
+@pytest.mark.parametrize("clamp_compat", [True, False])
+def test_diagonal_stream_matches_the_host_chain(clamp_compat):
+    from speaker_recognition_amd.core import ServingStream
+    windows, noise = scene()
+    vad = make_vad(noise)
+    ex, raw, ms = diag_setup()
+    want_s, want_a, want_v, frames, n_runs = host_chain(vad, ex, ms, windows, clamp_compat)
+    check_scene(want_v, frames, n_runs)
+    T = frames.astype(np.float64)
+    bound = 1e-4 * np.maximum(T[:, None], np.abs(want_s))
+    top2 = np.sort(want_s, axis=1)[:, -2:]
+    decided = (top2[:, 1] - top2[:, 0]) > 2.0 * bound.max(axis=1)            # (sums: the per-frame means times T on both sides)
+    left_out = int(np.sum((frames > 0) & ~decided))
+    assert left_out <= 0.02 * len(windows), "%d windows left out of the argmax check" % left_out
+    first = {}
+    for graph in (False, True):
+        for n_win in (1, 6, 64):
+            if graph and n_win == 64:
+                continue
+            st = ServingStream(ex, ms, n_win, WIN, clamp_compat=clamp_compat, graph=graph, vad=vad)
+            s, a, v = run_stream(st, windows, n_win)
+            ratio = np.abs(s - want_s) / np.where(bound > 0, bound, 1.0)      # (bound 0: a window that is not scored, sums 0)
+            print("diag clamp=%s graph=%s n_win=%d: voiced mismatches %d, worst |d| / bound %.3g, argmax mismatches %d (left out %d)" % (
+                clamp_compat, graph, n_win, int(np.sum(v != want_v)), float(ratio[frames > 0].max()),
+                int(np.sum((a != want_a) & ((frames == 0) | decided))), left_out))
+            assert np.array_equal(v, want_v), (graph, n_win)
+            assert np.array_equal(a >= 0, frames > 0)
+            assert np.all(s[frames == 0] == 0.0) and np.all(a[frames == 0] == -1)
+            assert np.all(ratio[frames > 0] <= 1.0), (graph, n_win, float(ratio[frames > 0].max()))
+            assert np.array_equal(a[decided | (frames == 0)], want_a[decided | (frames == 0)]), (graph, n_win)
+            # graph = plain, bit for bit (across windows per tick the dispatcher may take another engine: the gate above)
+            first.setdefault(n_win, (s, a))
+            assert np.array_equal(s, first[n_win][0]) and np.array_equal(a, first[n_win][1]), (graph, n_win)
+            del st
+
+
+def test_graph_equals_plain_over_ticks_of_different_content_and_two_in_flight():
+    from speaker_recognition_amd.core import ServingStream
+    windows, noise = scene()
+    vad = make_vad(noise)
+    n_win, n_ticks = 6, 8
+    ticks = [windows[t * n_win:(t + 1) * n_win] for t in range(n_ticks)]
+    for kind in ("full", "diag"):
+        ex, _, models = full_setup(15, 6, 8, seed=1) if kind == "full" else diag_setup(6, 64)
+        serial = []
+        st = ServingStream(ex, models, n_win, WIN, vad=vad)
+        for t in ticks:
+            st.submit(t)
+            serial.append(st.collect_vad()[:3])
+        assert len({tuple(r[2].tolist()) for r in serial}) >= 6            # replayed ticks see lengths the captured one did not
+        for graph in (False, True):
+            st = ServingStream(ex, models, n_win, WIN, graph=graph, vad=vad)
+            got = []
+            for t in range(0, n_ticks, 2):                                   # submit, submit, collect, collect
+                st.submit(ticks[t])
+                st.submit(ticks[t + 1])
+                got.append(st.collect_vad()[:3])
+                got.append(st.collect_vad()[:3])
+            for t in range(n_ticks):
+                for x, y in zip(got[t], serial[t]):
+                    assert np.array_equal(x, y), (kind, graph, t)
+            # collect() keeps its three values; the counts are in last_voiced
+            st.submit(ticks[0])
+            out = st.collect()
+            assert len(out) == 3 and np.array_equal(out[0], serial[0][0]) and np.array_equal(st.last_voiced, serial[0][2])
+
+
+def test_all_silence_tick_and_interleaving_with_a_plain_stream():
+    from speaker_recognition_amd import _lib
+    from speaker_recognition_amd.core import Batch, ServingStream
+    windows, noise = scene()
+    vad = make_vad(noise)
+    n_win = 6
+    silence = np.random.default_rng(9).normal(0, 60, (n_win, WIN)).astype(np.int16)       # the floor alone
+    _lib.set_option("debug_verify_clean_counters", 1)
+    try:
+        for kind in ("full", "diag"):
+            ex, _, models = full_setup(0, 4, 8, seed=2) if kind == "full" else diag_setup(6, 64)
+            for graph in (False, True):
+                sv = ServingStream(ex, models, n_win, WIN, graph=graph, vad=vad)
+                sp = ServingStream(ex, models, n_win, WIN, graph=graph)
+                tick = windows[12:12 + n_win]
+                sv.submit(tick)
+                ref = sv.collect_vad()[:3]
+                assert np.any(ref[1] >= 0)
+                b = Batch.from_pcm(list(tick))
+                plain = models.predict_pcm(ex, b) if kind == "full" else ex.predict_batch(models, b)
+                for _ in range(3):
+                    sv.submit(silence)
+                    sp.submit(tick)
+                    s, a, v, _ms = sv.collect_vad()
+                    assert np.all(a == -1) and np.all(s == 0.0) and np.all(3 * v <= WIN), (kind, graph, v)
+                    ps, pa, _ms = sp.collect()
+                    # a stream without vad= gives exactly what it gave before
+                    assert np.array_equal(ps, plain[0]) and np.array_equal(pa, plain[1]), (kind, graph)
+                    if kind == "diag":
+                        ex.predict_batch(models, b)                          # a delivering pass between the ticks
+                    sv.submit(tick)
+                    got = sv.collect_vad()[:3]
+                    for x, y in zip(got, ref):
+                        assert np.array_equal(x, y), (kind, graph)
+                with pytest.raises(_lib.SRError, match="not a voice-activity session"):
+                    sp.collect_vad()
+    finally:
+        _lib.set_option("debug_verify_clean_counters", 0)
+
+
+def test_creation_checks_and_model_interface_chain():
+    from speaker_recognition_amd import _lib, synth
+    from speaker_recognition_amd.core import MfccExtractor, ServingStream
+    from speaker_recognition_amd.filters import VAD
+    from speaker_recognition_amd.interface import ModelInterface
+    windows, noise = scene()
+    ex, _, ms = diag_setup(3, 16)
+    with pytest.raises(ValueError, match="not initialised"):
+        ServingStream(ex, ms, 2, WIN, vad=VAD())
+    vad = make_vad(noise)
+    with pytest.raises(_lib.SRError, match="nd = 0 only"):
+        ServingStream(ex, ms, 2, WIN, nd=1, vad=vad)
+    with pytest.raises(_lib.SRError, match="order 5 needs more"):
+        ServingStream(ex, ms, 2, 1900, vad=vad)
+    with pytest.raises(ValueError, match="Hz"):
+        ServingStream(MfccExtractor(16000), ms, 2, 16000, vad=vad)
+    # init_noise -> ServingStream(vad=iface.vad), both covariance types, on the interface's own models
+    for cov in ("diag", "full"):
+        m = ModelInterface(covariance_type=cov, lpc=False, verbose=False, gmm_order=8)
+        for s in range(3):
+            m.enroll("spk%d" % s, FS, synth.synth_speech(9 * s, 6.0, FS, seed=100 + s))
+        m.train()
+        m.init_noise(FS, noise)
+        if cov == "full":
+            from speaker_recognition_amd import skgmm
+            models = skgmm.FullSet(m.gmmset.gmms)
+        else:
+            from speaker_recognition_amd.core import ModelSet
+            models = ModelSet(m.gmmset.gmms)
+        st = ServingStream(ex, models, 4, WIN, vad=m.vad)
+        st.submit(windows[12:16])
+        s, a, v, _ms = st.collect_vad()
+        for i, chunk in enumerate(windows[12:16]):
+            kept = m.filter(FS, chunk)
+            assert v[i] == len(m.vad.filter(FS, chunk)[0])
+            assert (a[i] >= 0) == (len(kept) > 0 and ex.num_frames(len(kept)) > 0)
+
+
+def _oracle_windows(windows, noise):
+    """rules 1-4 in float64 numpy -> (voiced samples per window or None when a value is near a threshold, thresholds)"""
+    from oracle import ltsd_oracle as lo
+    N = lo.window_size(FS)
+    na, lam0, lam1 = lo.thresholds(noise, N)
+    half = N // 2
+    out = []
+    for chunk in windows:
+        l = lo.ltsd(chunk, na, N)
+        if np.any(np.abs(l - lam0) <= 1e-3 * abs(lam0)) or np.any(np.abs(l - lam1) <= 1e-3 * abs(lam1)):
+            out.append(None)
+            continue
+        above, i, keep = l > lam0, 0, []
+        while i < len(l):
+            if not above[i]:
+                i += 1
+                continue
+            j = i
+            while j + 1 < len(l) and above[j + 1]:
+                j += 1
+            if l[i:j + 1].max() > lam1:
+                keep.append(chunk[i * half:(j + 1) * half])
+            i = j + 1
+        out.append(np.concatenate(keep) if keep else np.zeros(0, np.int16))
+    return out
+
+
+@pytest.mark.parametrize("kind", ["full", "diag"])
+def test_against_the_float64_oracle_chain(kind, oracle_built):
+    """The VAD leg is "parity unpinned" (pyssp is absent: the oracle restates the published LTSD measure)."""
+    from oracle import lpc_oracle, mfcc_oracle as mo
+    from speaker_recognition_amd.core import ServingStream
+    go = oracle_built
+    windows, noise = scene()
+    windows = windows[:40]
+    vad = make_vad(noise)
+    ov = _oracle_windows(windows, noise)
+    skipped = sum(v is None for v in ov)
+    assert skipped <= 0.05 * len(windows), skipped
+    if kind == "full":
+        ex, gmms, models = full_setup(15, 6, 8, seed=7)
+    else:
+        ex, raw, models = diag_setup(20, 256)
+    st = ServingStream(ex, models, len(windows), WIN, clamp_compat=False, vad=vad)
+    st.submit(windows)
+    s, a, v, _ms = st.collect_vad()
+    worst, left_out, n_scored = 0.0, 0, 0
+    for i, vo in enumerate(ov):
+        if vo is None:
+            continue
+        assert v[i] == len(vo), (i, int(v[i]), len(vo))
+        scored = 3 * len(vo) > WIN and len(vo) > 5 * ex.FRAME_LEN
+        assert (a[i] >= 0) == scored, i
+        if not scored:
+            continue
+        n_scored += 1
+        f = mo.extract(FS, vo)
+        if kind == "full":
+            f = np.hstack([f, lpc_oracle.extract(FS, vo)])
+            want = np.array([fo.score_samples(f, g.weights_, g.means_, g.precisions_cholesky_).sum() for g in gmms])
+        else:
+            want = np.array([go.score_batch(go.GMMParams(*[np.asarray(p, np.float64) for p in m]), f, go.MODE_FAST,
+                                            clamp_compat=False).sum() for m in raw])
+        bound = 1e-4 * np.maximum(len(f), np.abs(want))
+        worst = max(worst, float(np.max(np.abs(s[i] - want) / bound)))
+        top2 = np.sort(want / len(f))[-2:]
+        if top2[1] - top2[0] > 2.0 * bound.max() / len(f):
+            assert a[i] == int(np.argmax(want)), i
+        else:
+            left_out += 1
+    print("oracle chain (%s): %d scored, %d skipped near a threshold, %d left out of the argmax check, worst |d| / bound %.3g" % (
+        kind, n_scored, skipped, left_out, worst))
+    assert n_scored >= 10
+    assert left_out == 0, "%d windows left out of the argmax check" % left_out
+    assert worst <= 1.0, worst
