@@ -706,12 +706,7 @@ static void predict_unpipelined(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd
     mfcc_extract_batch(*m, *pcm, nd, 1, *feat_ws);
     // (small result sets land in host memory by themselves: SCORE_HOST_DELIVER, score.hpp)
     const int deliver = (sums_out && argmax_out && host_deliverable((size_t)pcm->n_utt, (size_t)set->host.n_models)) ? SCORE_HOST_DELIVER : 0;
-    const ScoreResult r = score_device(*set, *feat_ws, false, flags | deliver);
-    if (!fetch_results(*set, *feat_ws, flags, r, sums_out, argmax_out, nullptr)) {
-        // a frame left the fp16 engine's range: score the batch again on the fp32-grade engines
-        const ScoreResult r2 = score_device(*set, *feat_ws, false, flags | SCORE_PRECISE);
-        fetch_results(*set, *feat_ws, flags | SCORE_PRECISE, r2, sums_out, argmax_out, nullptr);
-    }
+    score_resolved(*set, *feat_ws, false, flags, deliver, sums_out, argmax_out, nullptr);
 }
 
 }  // extern "C"

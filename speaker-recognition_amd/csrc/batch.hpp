@@ -38,7 +38,7 @@ struct TileTable {
     StagedUpload<int> stage_begin;
 };
 
-void ensure_work_table(TileTable &tt, bool pack_tails);   // gmm_score.hip
+void ensure_work_table(TileTable &tt, bool pack_tails);   // gmm_score_host.cpp
 
 }  // namespace sr
 

@@ -288,26 +288,7 @@ __device__ __forceinline__ void h2s_close_block_packed(const H2sArgs &a, const S
     }
 }
 
-// Workgroup shapes: waves per workgroup x 32-frame column tiles per wave x images per LDS stage.
-//   <4,1>   three workgroups per CU, each with its own copy of the stream (small batches)
-//   <12,1>  one workgroup per CU, three waves per SIMD sharing one copy
-// Tried and measured slower than <4,1> (profiles/r02_h2s_stalls.txt; the code is in commits 401bc2d and f5a34fe):
-// two column tiles per wave (COLS = 2: half the LDS fragment reads, 2 waves per SIMD) -4 %; 8 waves x 2 column
-// tiles -5 %; 8 waves with the two waves of a SIMD held in anti-phase by a workgroup barrier per phase (one
-// chains while the other runs its epilogue) -3 % with one image per phase, -5 % with two.
-__host__ __device__ constexpr int h2s_waves_per_eu(int kqf, int klf, int cols, int waves, bool ms = false) {
-    // The 4-wave shape at three workgroups per CU (168 registers) kept its quadratic-half frame fragments in scratch from
-    // kqf + klf = 10 up (156 .. 364 bytes per lane, one reload inside the image loop = an s_waitcnt vmcnt(0) on the LDS-DMA
-    // stream).  Since round 4 it only serves batches below ~2000 frames (score_device: everything larger takes a 12-wave
-    // shape) -- a handful of workgroups, latency-bound, where a third workgroup per CU buys nothing: two per CU, 256 registers,
-    // nothing in scratch.
-    // (the model-split shape carries a few registers more: at three workgroups per CU its 3 + 3 and 4 + 4 forms spilled 24 / 52 bytes)
-    // (since the 4-wave shapes stream four images per stage their LDS admits two workgroups per CU at most, and their batches --
-    // below ~2000 frames -- never need more: two per CU for every chain length; the third one's 168-register budget was
-    // what spilled, last in <4,4> once the exception lists became per block)
-    (void)kqf; (void)klf; (void)cols; (void)ms;
-    return waves > 4 ? waves / 4 : 2;
-}
+// (the workgroup shapes and h2s_waves_per_eu: score_shapes.hpp)
 // the quadratic-half frame fragments in LDS instead of registers: every 12-wave shape (round 3), and the 4-wave shape of the long
 // chains (round 4: with them in registers it spilled 76 bytes per lane even at 256 registers)
 __host__ __device__ constexpr bool h2s_bq_in_lds(int kqf, int klf, int waves) { return waves > 4 || kqf + klf >= 9; }
@@ -547,7 +528,7 @@ __device__ __forceinline__ void h2p_for(F &&f) {
 // soon as their chain has issued (the compiler places the vmcnt waits: plain loads into registers), 2 x 4 waves x 8 KB in flight
 // per CU.  Same arithmetic in the same order as the LDS form (a (frame, model) value is formed by one lane over the mixture
 // tiles in order): same bits.
-constexpr int H2M_MAX_KLF = 9;        // two register sets of fragments fit up to here (D <= 45); the longest chains keep the LDS form
+// (H2M_MAX_KLF, score_shapes.hpp: two register sets of fragments fit up to there)
 template <int KQF, int KLF>
 __global__ __launch_bounds__(256, 2)
 void gmm_score_h2m_kernel(const H2sArgs a) {
@@ -1276,10 +1257,6 @@ void gmm_score_h2s_online_kernel(const H2sArgs a) {
     }
 }
 
-// LDS the pipelined kernel takes: its ring of two stages of four images plus the 12 waves' quadratic-half fragments
-__host__ __device__ constexpr bool h2p_fits(int kqf, int klf) { return klf >= 2 && kqf <= klf && (2 * 4 * klf + 12 * kqf) * 1024 <= 160 * 1024; }
-
-
 template <int KQF, int KLF, int COLS, int WAVES, bool PIN = false, bool MS = false>
 static int launch_h2s(const H2sLaunch &l) {
     constexpr bool BQ_LDS = h2s_bq_in_lds(KQF, KLF, WAVES);
@@ -1375,13 +1352,6 @@ static int launch_h2s(const H2sLaunch &l) {
     hipLaunchKernelGGL((gmm_score_h2s_online_kernel<KQF, KLF>), dim3((unsigned)(l.n_blocks * gy)), dim3(256), 0, ctx().stream, a);
     return n_launches;
 }
-
-// workgroups resident per CU, and 32-frame tiles per workgroup, of shape `shape` (0: 4 waves; 1: 12 waves; 2: 12 waves, pipelined;
-// 3: 4 waves on one tile, the block's models split between them)
-int h2s_resident_per_cu(int kqf, int klf, int shape) { return (shape == 0 || shape == 3) ? h2s_waves_per_eu(kqf, klf, 1, 4, shape == 3) : 1; }
-int h2s_tiles_per_wg(int shape) { return shape == 0 ? 4 : shape == 3 ? 1 : 12; }
-bool h2s_pipelined_available(int kqf, int klf) { return h2p_fits(kqf, klf); }
-bool h2s_msplit_direct(int kqf, int klf) { (void)kqf; return klf <= H2M_MAX_KLF; }
 
 // returns the number of launches of the main kernel the pass was cut into
 int launch_score_h2_shared(const H2sLaunch &l, int KQF, int KLF) {

@@ -210,8 +210,6 @@ static void dispatch_split_ft(const MfmaLaunch &a, int FT) {
     fail("split engine: %d column tiles per wave not instantiated for %d contraction steps", FT, KS);
 }
 
-int split_max_ft(int ks) { return ks <= 6 ? 2 : 1; }
-
 template <typename SC>
 static void dispatch_split(const MfmaLaunch &a, int KS, int FT) {
     switch (KS) {

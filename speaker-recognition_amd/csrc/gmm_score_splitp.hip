@@ -45,21 +45,7 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-// Workgroup shapes: 16 or 12 waves = one workgroup per CU (one copy of the stream for all of them); 8 waves = two per CU: twice the
-// stream, but one workgroup's frame prologue (~500 vector instructions per wave, no MFMA) runs under the other's chains -- what short
-// streams want (one 256-mixture model: 8 chunks per prologue).
-// chunks per LDS stage: an even count (the two accumulators alternate statically), three stages within the workgroup's share of LDS
-__host__ __device__ constexpr int splitp_stage_chunks(int ks, int parts, int waves) { return waves > 8 && ks * parts <= 10 ? 4 : 2; }
-__host__ __device__ constexpr int splitp_lds_bytes(int ks, int parts, int waves) {
-    return 3 * splitp_stage_chunks(ks, parts, waves) * ks * parts * 1024 + waves * 16 * 33 * 4;
-}
-__host__ __device__ constexpr bool splitp_fits(int ks, int parts, int waves) {
-    // 4 waves per SIMD (16 waves, or two workgroups of 8) leave 128 registers: resident frame fragments of up to 10 x 4 beside the
-    // two accumulators (ks * parts = 12: 12 bytes of scratch, 14: 64, 16: 116 -- build/gmm_score_splitp.resources); 12 waves have 168
-    if (waves != 12 && ks * parts > 10) return false;
-    return splitp_lds_bytes(ks, parts, waves) <= (160 * 1024 - 512) / (waves > 8 ? 1 : 2);
-}
-
+// (the workgroup shapes and what fits them -- splitp_fits: score_shapes.hpp)
 // (The parts-off measurement builds of round 4 -- the kernel with its log-sum-exp update, model close, LDS-DMA, fragment reads or
 // MFMAs compiled out, profiles/r04_splitp.txt -- were macro hooks in this file until round 6; `git show 951632a:` has them.)
 constexpr int SLAB_M = 16;          // models per slab flush
@@ -383,21 +369,6 @@ bool dispatch_splitp_waves(const MfmaLaunch &l, int waves, int chunks_per_model)
 }
 
 }  // namespace
-
-// workgroups of that shape a CU holds
-int splitp_resident_per_cu(int waves) { return waves > 8 ? 1 : 2; }
-
-// 32-frame tiles a workgroup of the wide shape takes (= its waves)
-int splitp_waves(int scheme, int ks, int want) {
-    // (instantiated for the two-part fp16 scheme: what the dispatcher takes for every well-conditioned set; the bf16x3 fallback
-    // keeps the 4-wave kernel -- 28 more variants of this file cost a minute and a half of build time)
-    const int parts = 2;
-    if (scheme != SPLIT_F16X2) return 0;
-    if (ks < 2 || ks > 8) return 0;
-    for (int w : {want, 16, 12, 8})
-        if ((w == 16 || w == 12 || w == 8) && splitp_fits(ks, parts, w)) return w;
-    return 0;
-}
 
 // `l.tiles` = the batch's 32-frame tiles.  false: no such variant (the caller takes gmm_score_split_kernel).
 // `chunks_per_model`: the 32-mixture chunks of EVERY model of the set (sets of models of different orders take the 4-wave kernel).

@@ -335,7 +335,7 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             if (m->full) {
                 // sums and the argmax values right behind them, in one copy; no flags, no list (the log-sum-exp is exact)
                 const double *res = fullset_score_device(*s.fset, ch.feat);
-                SR_HIP(hipMemcpyAsync(ch.h_sums.p, res, (size_t)nu * S * sizeof(double) + (size_t)nu * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+                SR_HIP(hipMemcpyAsync(ch.h_sums.p, res, results_bytes(nu, S), hipMemcpyDeviceToHost, ctx().stream));
                 ch.h_arg = reinterpret_cast<int *>(ch.h_sums.p + (size_t)nu * S);
                 ch.tiles = nullptr;
                 ch.flush_cap = 0;
@@ -345,21 +345,18 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             const ScoreResult r = score_device(*s.set, ch.feat, false, flags);
             // (the pass's two counters and its sums + argmax lie side by side in the workspace: one copy each instead of two -- a copy
             // is ~8 us on the stream, and eight pieces' small operations are what keeps the call above max(copy, kernels))
-            const bool flags_together = r.d_oor && r.d_flush_count == r.d_oor + 1;
-            if (flags_together) SR_HIP(hipMemcpyAsync(ch.h_flags.p, r.d_oor, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-            else if (r.d_oor) SR_HIP(hipMemcpyAsync(ch.h_flags.p, r.d_oor, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+            copy_pass_flags(r, ch.h_flags.p, ctx().stream);
             ch.tiles = r.tiles;
             ch.flush_cap = 0;
             if (r.d_flush_count) {
                 // frames in the band of the reference's partial-product flushes are the NORMAL case on some workloads (synthetic
                 // speech against random models: ~2 k pairs per 10 M frames): keep what resolving them needs, a few MB device to device
-                if (!flags_together) SR_HIP(hipMemcpyAsync(ch.h_flags.p + 1, r.d_flush_count, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
                 ch.d_list.ensure((size_t)std::max(1, r.flush_cap));
                 ch.flush_cap = r.flush_cap;
                 SR_HIP(hipMemcpyAsync(ch.d_list.p, r.d_flush_list, (size_t)r.flush_cap * sizeof(int2), hipMemcpyDeviceToDevice, ctx().stream));
             }
             if ((const void *)r.d_argmax == (const void *)(r.d_sums + (size_t)nu * S)) {
-                SR_HIP(hipMemcpyAsync(ch.h_sums.p, r.d_sums, (size_t)nu * S * sizeof(double) + (size_t)nu * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+                SR_HIP(hipMemcpyAsync(ch.h_sums.p, r.d_sums, results_bytes(nu, S), hipMemcpyDeviceToHost, ctx().stream));
                 ch.h_arg = reinterpret_cast<int *>(ch.h_sums.p + (size_t)nu * S);
             } else {
                 SR_HIP(hipMemcpyAsync(ch.h_sums.p, r.d_sums, (size_t)nu * S * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
@@ -386,12 +383,8 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
                 // a frame saturated the fp16 engine, or the list overflowed: this piece again, synchronously, from its features
                 std::lock_guard<std::recursive_mutex> lock(api_mutex());
                 const int fl = flags | (ch.h_flags.p[0] != 0 ? SCORE_PRECISE : 0);
-                ScoreResult r = score_device(*s.set, ch.feat, false, fl);
                 ch.h_arg = ch.h_argmax.p;
-                if (!fetch_results(*s.set, ch.feat, fl, r, ch.h_sums.p, ch.h_argmax.p, nullptr)) {
-                    r = score_device(*s.set, ch.feat, false, fl | SCORE_PRECISE);
-                    fetch_results(*s.set, ch.feat, fl | SCORE_PRECISE, r, ch.h_sums.p, ch.h_argmax.p, nullptr);
-                }
+                score_resolved(*s.set, ch.feat, false, fl, 0, ch.h_sums.p, ch.h_argmax.p, nullptr);
             }
             // the piece's rows go straight to the caller's arrays (runs of neighbouring utterances as one copy)
             for (int i = ch.u0; i < ch.u1;) {

@@ -3,50 +3,10 @@
 
 #include "batch.hpp"
 #include "gmm_model.hpp"
+#include "score_plan.hpp"
 
 namespace sr {
 
-struct ScoreOptions {
-    int frames_per_lane = 0;   // 0 = auto; 1, 2 or 4 frames resident per lane
-    int model_groups = 0;      // 0 = auto; workgroups per frame tile along the model axis
-    int packed = 0;            // -1 = scalar v_fma_f32; 0 (auto) / 1 = v_pk_fma_f32, two frames per VGPR pair
-    int engine = 0;            // 0 = auto; 1 = vector-ALU 2-FMA kernel; (2 = the fp32 matrix-core kernel of round 1, removed);
-                               // 3 = split-bf16 (3 parts, 6 products) matrix-core kernel;
-                               // 4 = split-bf16, shared-sigma form (sets whose models share sigma and weights)
-                               // 5 = split-fp16 (2 parts, 3 products) matrix-core kernel;
-                               // 6 = split-fp16, shared-sigma form
-    int mfma_ft = 0;           // 32-frame column tiles per wave in the 4-wave generic split kernels (0 = one)
-    int h2s_shape = 0;         // workgroup shape of the split-fp16 shared-sigma engine: 0 = automatic; 1 = 4 waves (three
-                               // workgroups per CU); 2 = 12 waves (one per CU, one copy of the stream in LDS); 3 = 12 waves with the
-                               // image loop software-pipelined inside each wave (gmm_score_h2p_kernel)
-    int split_shape = 0;       // workgroup shape of the generic split-fp16 engine: 0 = automatic; 1 = 4 waves (gmm_score_split_kernel);
-                               // 16 / 12 / 8 = gmm_score_splitp_kernel with that many waves (one 32-frame tile each, log-sum-exp pipelined
-                               // under the next chunk's MFMAs; 16 and 12: one workgroup per CU, 8: two)
-    int h2s_pack_tails = 1;    // 0: the pipelined shared-sigma kernel takes one tile per wave even when it is a ragged tail (A/B, tests)
-    int h2s_force_exc = 0;     // testing: send every workgroup of the split-fp16 shared-sigma engine through its exception pass
-    int flush_list_cap = 0;    // testing: capacity of the list of (tile, model) pairs in the partial-product band (0 = automatic);
-                               // a pass that notes more re-runs with a list of the counted length
-    int verify_clean_counters = 0;  // testing: a delivering pass that skips the counters' clear reads them back first and fails
-                                    // unless every one is zero (sr_set_option("debug_verify_clean_counters", 1))
-};
-
-// The matrix-core engines are used when the expanded form is well conditioned in fp32 and the
-// 32-mixture tiles are not mostly padding; otherwise the 2-FMA vector kernel (direct form).
-constexpr double MFMA_MAX_AMP = 2000.0;      // max_k sum_d (mu'_d/sigma_d)^2
-constexpr double MFMA_MAX_PAD_WASTE = 0.25;
-// The two-part fp16 engines carry 22 significand bits per operand (error ~4x an fp32 FMA chain's per
-// term, scripts/emulate_split.py) and fp16's 5-bit exponent: offered when the cancellation is
-// moderate, every dimension's sigmas stay within a factor the gradual-underflow error analysis
-// covers (HISTORY.md 2.1), and the scaled coefficients fit fp16.
-constexpr double F16_MAX_AMP = 1000.0;
-// Hybrid form: a set the expanded form is ill conditioned for (amp above the limits) because of FEW of its mixtures
-// -- collapsed components at the sigma floor, outlier catchers -- is cut in two: those mixtures (at most
-// HYBRID_MAX_BAD_FRACTION of them) run on the direct-form vector engine, the rest on the matrix cores.
-constexpr double HYBRID_MAX_BAD_FRACTION = 0.25;
-constexpr double F16_MAX_SIGMA_RATIO = 256.0;
-constexpr double F16_MAX_COEF = 30000.0;
-// internal scoring flag (beside SR_CLAMP_COMPAT): keep to the fp32-grade engines (EM, serving stream)
-constexpr int SCORE_PRECISE = 0x200;
 // internal: leave the partial-product band alone (the two halves of a hybrid set: their merge looks at the merged value)
 constexpr int SCORE_NO_FLUSH = 0x400;
 // Small result sets of callers that fetch them right away (fetch_results): gmm_finalize_kernel's last workgroup writes sums, argmax
@@ -66,6 +26,35 @@ struct DeliverHeader {
     int pad;
 };
 
+// The vector-ALU engine, the hybrid sets' merge and the finalize: kernels and launch code in gmm_score.hip.
+struct ScoreArgs {
+    const float *X;            // [n_frames][dim] row-major fp32
+    const TileDesc *tiles;
+    const float4 *params;
+    const float *center;       // [DP] subtracted from every frame (PackedModels::center)
+    const ChunkDesc *chunks;
+    const int *group_chunk_begin;  // [G+1]
+    double *partial;           // [n_tiles][S][4]  per-wave partial sums
+    float *frame_ll;           // [S][n_frames] or nullptr
+    int64_t n_frames;
+    int dim;
+    int n_models;
+    int clamp;
+    int n_groups, n_tiles;
+    float band_hi;             // below it a frame goes to the partial-product path (lse.hpp); -inf: never
+};
+void launch_score_vector(const ScoreArgs &a, int DP, int F, bool packed);      // DP <= MAX_REG_DIM: gmm_score_kernel<DP, F, packed>
+void launch_score_wide(const ScoreArgs &a, int DP);                            // wider rows: gmm_score_wide_kernel
+struct FinalizeDelivery {      // SCORE_HOST_DELIVER; host == nullptr: off
+    DeliverHeader *host;
+    int *counters;             // the pass's counters: [0] saturation flag, [1] flush count, [2] this kernel's ticket, [4 ...]
+    int n_counters;
+    unsigned seq;
+};
+void launch_finalize(const double *partial, const TileTable &tt, int n_utt, int n_models, int per_tile, double *sums, int *argmax,
+                     int2 *flush_list, int *flush_count, int flush_cap, const FinalizeDelivery &dl);
+void launch_merge(const float *a, const float *b, const TileTable &tt, int n_models, int64_t n_frames, int clamp, double *partial,
+                  float *out, float band_hi);
 struct MfmaLaunch {
     const float *X;
     const TileDesc *tiles;
@@ -120,25 +109,10 @@ struct H2sLaunch {
     float band_hi = -__builtin_inff();
 };
 int launch_score_h2_shared(const H2sLaunch &a, int KQF, int KLF);
-int h2s_resident_per_cu(int kqf, int klf, int shape);   // workgroups the kernel variant keeps resident per CU
-int h2s_tiles_per_wg(int shape);                        // 32-frame tiles a workgroup of that shape takes
-bool h2s_msplit_direct(int kqf, int klf);               // shape 3 runs as gmm_score_h2m_kernel (images straight into registers) for these chain lengths
-bool h2s_pipelined_available(int kqf, int klf);         // shape 2 (12 waves, image loop software-pipelined inside each wave) exists for these chain lengths
-// Minimum set size for the shared-sigma engine (blocks of SHARED_SB models; smaller sets would be
-// mostly phantom models).
-constexpr int SHARED_MIN_MODELS = 12;
-constexpr int H2S_WIDE_SHAPE = 1;       // the one-workgroup-per-CU shape
-constexpr int H2S_MSPLIT_SHAPE = 3;     // four waves on ONE tile, the block's models split between them: the smallest batches (round 4)
-constexpr int H2S_PIPELINED_SHAPE = 2;  // the same with the image loop pipelined inside each wave: what the dispatcher takes for large batches
 void launch_score_split(const MfmaLaunch &a, int scheme, int KS, int FT);   // a.params = the split image
-int split_max_ft(int ks);
 // gmm_score_splitp.hip: the same engines as ONE wide workgroup per CU (12 or 16 waves, a 32-frame tile each, the chunk's log-sum-exp
-// pipelined under the next chunk's MFMAs); `a.tiles` = 32-frame tiles.  splitp_waves: waves per workgroup of the variant that exists
-// for this layout (`want` = 0, 12 or 16), 0 = none.
-int splitp_waves(int scheme, int ks, int want);
-int splitp_resident_per_cu(int waves);
+// pipelined under the next chunk's MFMAs); `a.tiles` = 32-frame tiles; `waves` from splitp_waves_f16x2 (score_shapes.hpp).
 bool launch_score_splitp(const MfmaLaunch &a, int scheme, int KS, int waves, int chunks_per_model);
-ScoreOptions &score_options();
 const char *last_score_kernel();   // name of the kernel variant the last scoring call launched
 
 // Device-resident results of the last scoring call (valid until the next one).
@@ -173,6 +147,31 @@ void score_batch_set(SRModelSet &set, SRBatch &feat, double *sums_out, int *argm
 // with SCORE_PRECISE).
 bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult &r, double *sums_out,
                    int *argmax_out, float *frame_ll_out);
+// score_device + fetch_results; when the fp16 engine reported saturated frames, the whole batch again on the fp32-grade engines.
+// `flags`: what the first pass and both fetches run with; `deliver`: SCORE_HOST_DELIVER or 0, for the first pass only.
+// Returns the pass whose results stand.
+inline ScoreResult score_resolved(SRModelSet &set, SRBatch &feat, bool want_frame_ll, int flags, int deliver, double *sums_out, int *argmax_out,
+                           float *frame_ll_out) {
+    const ScoreResult r = score_device(set, feat, want_frame_ll, flags | deliver);
+    if (fetch_results(set, feat, flags, r, sums_out, argmax_out, frame_ll_out)) return r;
+    const ScoreResult r2 = score_device(set, feat, want_frame_ll, flags | SCORE_PRECISE);
+    fetch_results(set, feat, flags | SCORE_PRECISE, r2, sums_out, argmax_out, frame_ll_out);
+    return r2;
+}
+// The pass's saturation flag and partial-product count -> h_flags[0], [1] (page-locked), left in flight on `stream`: one copy when
+// the two counters are adjacent (the workspace keeps them side by side), else one each.
+inline void copy_pass_flags(const ScoreResult &r, int h_flags[2], hipStream_t stream) {
+    if (r.d_oor && r.d_flush_count == r.d_oor + 1) {
+        SR_HIP(hipMemcpyAsync(h_flags, r.d_oor, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    } else {
+        if (r.d_oor) SR_HIP(hipMemcpyAsync(h_flags, r.d_oor, sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (r.d_flush_count) SR_HIP(hipMemcpyAsync(h_flags + 1, r.d_flush_count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    }
+}
+// bytes of U x S sums with `ints_per_utt` ints per utterance (the argmax; the VAD tick's second value) right behind them: one copy
+inline size_t results_bytes(size_t n_utt, size_t n_models, size_t ints_per_utt = 1) {
+    return n_utt * n_models * sizeof(double) + ints_per_utt * n_utt * sizeof(int);
+}
 // gmm_flush.hip: the frames of the noted (tile, model) pairs again with the reference's own linear-domain arithmetic;
 // adds the tiles' sums to `d_sums`, redoes the argmax of the utterances touched, overwrites the per-frame values
 void flush_resolve(SRModelSet &set, SRBatch &feat, const TileTable &tt, const int2 *d_list, int count, double *d_sums,
@@ -194,9 +193,6 @@ void upload_model_set(SRModelSet &s);
 std::shared_ptr<SRModelSet> single_model_set(const GMM *g);
 // the split-bf16 layout of a set that carries one (s.bx3), on the device: lazily, as every matrix-core layout (em.hip reads it too)
 void ensure_bx3_layout(SRModelSet &s);
-bool split_bf16_in_range(const SRModelSet &s);       // what score_device asks before it takes that engine
-// Packs the layouts a set needs (all of them for small sets; for large ones the vector layout plus
-// the one the dispatcher will pick, or the one forced by score_engine at creation time).
-void pack_model_set(SRModelSet &s, const std::vector<const GMM *> &models);
+inline bool split_bf16_in_range(const SRModelSet &s) { return mfma_ok(s.bx3); }      // what the dispatcher asks before it takes that engine (em.hip)
 
 }  // namespace sr

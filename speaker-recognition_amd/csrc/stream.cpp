@@ -104,6 +104,20 @@ void vad_sum_frames(SRStream *s, SRStream::Slot &sl, const ScoreResult &r) {
                     vad_argmax(s, sl));
 }
 
+// the diagonal pass of a tick, plain or VAD: the scoring launches and the copies of its two flags, left in flight
+ScoreResult score_tick(SRStream *s, SRStream::Slot &sl, bool want_frame_ll) {
+    const ScoreResult r = score_device(*s->set, sl.feat, want_frame_ll, s->flags & 0xff);
+    // (sl.h_oor is cleared by sr_stream_submit BEFORE anything of the tick is enqueued, not here: this function also runs under
+    // stream capture right behind a plain pass of the same slot, and a host-side clear at that point races with the plain pass's
+    // copies below -- when the device won, the tick's "frames in the partial-product band" flag was lost and the tick came back
+    // unresolved: one failure in ~10 runs of the full GPU suite, round 3)
+    // [1]: (tile, model) pairs in the band where the reference's partial-product flushes decide (lse.hpp): resolved at collect.
+    // (Round 4: the workspace keeps the two counters, and the argmax values behind the sums, side by side -- one copy each; a
+    // copy is ~4.5 us on the stream, a tenth of a single window's decision.)
+    copy_pass_flags(r, sl.h_oor, ctx().stream);
+    return r;
+}
+
 void enqueue_vad_tick(SRStream *s, SRStream::Slot &sl) {
     int *const d_voiced = vad_argmax(s, sl) + s->n_windows, *const d_frames = vad_frames(s, sl);
     ltsd_session_enqueue(*s->vad, sl.pcm, s->mfcc->frame_len, s->mfcc->frame_shift, sl.vpcm.pcm16.p, d_voiced, d_frames);
@@ -111,18 +125,9 @@ void enqueue_vad_tick(SRStream *s, SRStream::Slot &sl) {
     if (s->fset) {
         fullset_score_device_masked(*s->fset, sl.feat, d_frames, sl.d_res.p);
     } else {
-        const ScoreResult r = score_device(*s->set, sl.feat, true, s->flags & 0xff);
-        // (the flags as in a plain tick, below: cleared by sr_stream_submit, written by these copies only)
-        if (r.d_oor && r.d_flush_count == r.d_oor + 1) {
-            SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-        } else {
-            if (r.d_oor) SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-            if (r.d_flush_count) SR_HIP(hipMemcpyAsync(sl.h_oor + 1, r.d_flush_count, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-        }
-        vad_sum_frames(s, sl, r);
+        vad_sum_frames(s, sl, score_tick(s, sl, true));
     }
-    const size_t n_sums = (size_t)s->n_windows * s->n_models;
-    SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, n_sums * sizeof(double) + 2 * (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+    SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, results_bytes(s->n_windows, s->n_models, 2), hipMemcpyDeviceToHost, ctx().stream));
 }
 
 void enqueue_tick(SRStream *s, SRStream::Slot &sl) {
@@ -131,27 +136,13 @@ void enqueue_tick(SRStream *s, SRStream::Slot &sl) {
     if (s->fset) {
         // sums [n_windows][S] and the argmax values right behind them, as the slot's pinned buffer holds them: one copy
         const double *res = fullset_score_device(*s->fset, sl.feat);
-        const size_t n_sums = (size_t)s->n_windows * s->n_models;
-        SR_HIP(hipMemcpyAsync(sl.h_sums, res, n_sums * sizeof(double) + (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        SR_HIP(hipMemcpyAsync(sl.h_sums, res, results_bytes(s->n_windows, s->n_models), hipMemcpyDeviceToHost, ctx().stream));
         return;
     }
-    const ScoreResult r = score_device(*s->set, sl.feat, false, s->flags & 0xff);
-    // (sl.h_oor is cleared by sr_stream_submit BEFORE anything of the tick is enqueued, not here: this function also runs under
-    // stream capture right behind a plain pass of the same slot, and a host-side clear at that point races with the plain pass's
-    // copies below -- when the device won, the tick's "frames in the partial-product band" flag was lost and the tick came back
-    // unresolved: one failure in ~10 runs of the full GPU suite, round 3)
-    // [1]: (tile, model) pairs in the band where the reference's partial-product flushes decide (lse.hpp): resolved at collect.
-    // (Round 4: the workspace keeps the two counters, and the argmax values behind the sums, side by side -- one copy each; a
-    // copy is ~4.5 us on the stream, a tenth of a single window's decision.)
-    if (r.d_oor && r.d_flush_count == r.d_oor + 1) {
-        SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-    } else {
-        if (r.d_oor) SR_HIP(hipMemcpyAsync(sl.h_oor, r.d_oor, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-        if (r.d_flush_count) SR_HIP(hipMemcpyAsync(sl.h_oor + 1, r.d_flush_count, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-    }
+    const ScoreResult r = score_tick(s, sl, false);
     const size_t n_sums = (size_t)s->n_windows * s->n_models;
     if ((const void *)r.d_argmax == (const void *)(r.d_sums + n_sums)) {
-        SR_HIP(hipMemcpyAsync(sl.h_sums, r.d_sums, n_sums * sizeof(double) + (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+        SR_HIP(hipMemcpyAsync(sl.h_sums, r.d_sums, results_bytes(s->n_windows, s->n_models), hipMemcpyDeviceToHost, ctx().stream));
     } else {
         SR_HIP(hipMemcpyAsync(sl.h_sums, r.d_sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
         SR_HIP(hipMemcpyAsync(sl.h_argmax, r.d_argmax, (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
@@ -237,7 +228,7 @@ SRStream *stream_create(SRMfcc *m, SRModelSet *set, SRFullSet *fset, int n_windo
             SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_pcm), n_samp * sizeof(int16_t), hipHostMallocDefault));
             // sums and, right behind them, the argmax values: as the device keeps them (score_device), one copy per tick
             const size_t n_sums = (size_t)n_windows * s->n_models;
-            SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_sums), n_sums * sizeof(double) + (size_t)n_windows * sizeof(int) * (vp ? 2 : 1), hipHostMallocDefault));
+            SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_sums), results_bytes(n_windows, s->n_models, vp ? 2 : 1), hipHostMallocDefault));
             sl.h_argmax = reinterpret_cast<int *>(sl.h_sums + n_sums);
             if (vp) sl.h_voiced = sl.h_argmax + n_windows;
             SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_oor), 2 * sizeof(int), hipHostMallocDefault));
@@ -404,21 +395,11 @@ static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *v
             if (s->vad) {
                 // per-frame values again; fetch_results without host destinations resolves the band ON THE DEVICE (flush_resolve
                 // overwrites the per-frame values of the noted pairs), then the same sum over each window's first T rows
-                ScoreResult r = score_device(*s->set, sl.feat, true, fl);
-                if (!fetch_results(*s->set, sl.feat, fl, r, nullptr, nullptr, nullptr)) {
-                    r = score_device(*s->set, sl.feat, true, fl | SCORE_PRECISE);
-                    fetch_results(*s->set, sl.feat, fl | SCORE_PRECISE, r, nullptr, nullptr, nullptr);
-                }
-                vad_sum_frames(s, sl, r);
-                const size_t n_sums = (size_t)s->n_windows * s->n_models;
-                SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, n_sums * sizeof(double) + (size_t)s->n_windows * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+                vad_sum_frames(s, sl, score_resolved(*s->set, sl.feat, true, fl, 0, nullptr, nullptr, nullptr));
+                SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, results_bytes(s->n_windows, s->n_models), hipMemcpyDeviceToHost, ctx().stream));
                 sync_stream();
             } else {
-                ScoreResult r = score_device(*s->set, sl.feat, false, fl);
-                if (!fetch_results(*s->set, sl.feat, fl, r, sl.h_sums, sl.h_argmax, nullptr)) {
-                    r = score_device(*s->set, sl.feat, false, fl | SCORE_PRECISE);
-                    fetch_results(*s->set, sl.feat, fl | SCORE_PRECISE, r, sl.h_sums, sl.h_argmax, nullptr);
-                }
+                score_resolved(*s->set, sl.feat, false, fl, 0, sl.h_sums, sl.h_argmax, nullptr);
             }
             sl.h_oor[0] = sl.h_oor[1] = 0;
         }

@@ -1,12 +1,14 @@
-// Host-side checks of csrc/gmm_model.cpp (model packers, text format, tail packing, the MFCC kernels' mel sweep starts), built by tests/test_host_sanitizers.py with -fsanitize=address,undefined (and once
+// Host-side checks of csrc/gmm_model.cpp and csrc/score_plan.cpp (the dispatcher's decisions: mode "plan"; model packers, text format, tail packing, the MFCC kernels' mel sweep starts), built by tests/test_host_sanitizers.py with -fsanitize=address,undefined (and once
 // with -fsanitize=thread): the model packers (every layout, threaded and not), the text parser on mutated model texts, and
 // the printf / strtod-free number conversions against libc.  Test infrastructure: not part of lib/pygmm.so.
 #include "gmm_model.hpp"
+#include "score_plan.hpp"
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <stdexcept>
 
@@ -19,7 +21,11 @@ void fail(const char *fmt, ...) {                      // the library's throws s
     va_end(a);
     throw std::runtime_error(b);
 }
+// (an SRModelSet's device buffers stay empty here; their destructors still name these)
+bool gpu_runtime_lost() { return false; }
+std::atomic<long> g_devbuf_epoch{0};
 }  // namespace sr
+extern "C" hipError_t hipFree(void *) { return hipSuccess; }
 using namespace sr;
 
 static std::vector<GMM> make_set(int S, int K, int D, bool shared, unsigned seed) {
@@ -237,7 +243,117 @@ static int check_mel_starts() {
     return 0;
 }
 
+// ---- mode "plan": the dispatcher's decisions (csrc/score_plan.cpp) on sets packed by the library's own pack_model_set ----
+// Models: deterministic doubles from splitmix64 of (seed, index), means in [-3, 3), sigmas in [0.5, 1.5).  Kinds: 0 independent
+// models; 1 a UBM and MAP-like copies (shared sigma and weights, means moved by < 0.05); 2 orders K and K / 2 alternating;
+// 3 every sigma x 0.01 (ill conditioned: amp > 2000); 4 mixture 0 of every model x 0.01 (a few ill-conditioned mixtures: hybrid).
+// Expected values: the decisions of the commit BEFORE the plan existed (c90fed6), recorded from a scratch build of it whose
+// score_device printed, at the end of its selection, {engine, F, FT, h2s_shape, splitp_w, split_cpm, frames per tile, partials per
+// tile, saturation flag}, G and sum_g gcb[g] * (g + 1) -- run on an MI355X (n_cu = 256) over these very sets (built through
+// sr_gmm_from_arrays from the same integers) and batches of n_utt utterances of utt_len zero frames.  A hybrid set has two
+// rows: its vector half, then its matrix half.
+static std::vector<double> unit(uint64_t seed, size_t n) {
+    std::vector<double> u(n);
+    for (size_t i = 0; i < n; i++) {
+        uint64_t z = (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull + seed;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        u[i] = (double)(z >> 11) * (1.0 / 9007199254740992.0);
+    }
+    return u;
+}
+struct PlanSet { int S, K, D, kind; };
+static std::vector<GMM> make_plan_set(const PlanSet &ps) {
+    std::vector<GMM> ms(ps.S);
+    for (int s = 0; s < ps.S; s++) {
+        GMM &g = ms[s];
+        const int K = (ps.kind == 2 && s % 2 == 1) ? ps.K / 2 : ps.K, D = ps.D;
+        const int src = ps.kind == 1 ? 0 : s;
+        const size_t n = (size_t)K * D;
+        g.nr_mixtures = K;
+        g.dim = D;
+        g.weights.assign(K, 1.0 / K);
+        g.mean = unit(1000 + 2 * src, n);
+        g.sigma = unit(1001 + 2 * src, n);
+        for (auto &v : g.mean) v = (v - 0.5) * 6.0;
+        for (auto &v : g.sigma) v = 0.5 + v;
+        if (ps.kind == 1 && s > 0) {
+            const auto sh = unit(5000 + s, n);
+            for (size_t i = 0; i < n; i++) g.mean[i] = g.mean[i] + 0.1 * (sh[i] - 0.5);
+        }
+        if (ps.kind == 3) for (auto &v : g.sigma) v = v * 0.01;
+        if (ps.kind == 4) for (int d = 0; d < D; d++) g.sigma[d] = g.sigma[d] * 0.01;
+    }
+    return ms;
+}
+struct PlanCase {
+    const char *name;
+    int set, n_utt, utt_len;
+    int opt[6];            // engine, h2s_shape, split_shape, frames_per_lane, model_groups, mfma_ft (as sr_set_option takes them)
+    int flags, n_plans;
+    struct { int v[9]; int G; long long gsum; } want[2];
+    const char *fail;      // the error a forced engine must raise, or nullptr
+};
+#include "plan_table.inc"
+
+static int check_plan() {
+    const int n_cu = 256;
+    int bad = 0, last_set = -1;
+    std::unique_ptr<SRModelSet> set;
+    for (const PlanCase &c : kPlanCases) {
+        if (c.set != last_set) {          // (plan_table.inc is grouped by set: one packed set at a time, each packed once)
+            const auto ms = make_plan_set(kPlanSets[c.set]);
+            std::vector<const GMM *> v;
+            for (auto &g : ms) v.push_back(&g);
+            set = std::make_unique<SRModelSet>();
+            pack_model_set(*set, v);
+            last_set = c.set;
+        }
+        ScoreOptions opt;
+        opt.engine = c.opt[0], opt.h2s_shape = c.opt[1], opt.split_shape = c.opt[2];
+        opt.frames_per_lane = c.opt[3], opt.model_groups = c.opt[4], opt.mfma_ft = c.opt[5];
+        const int64_t n_rows = (int64_t)c.n_utt * c.utt_len;
+        const bool hybrid = set->hy_good && opt.engine == 0;
+        if ((c.n_plans == 2) != hybrid) { printf("plan '%s': hybrid %d, recorded %d passes\n", c.name, (int)hybrid, c.n_plans); bad++; continue; }
+        for (int h = 0; h < (hybrid ? 2 : 1); h++) {
+            const SRModelSet &ss = !hybrid ? *set : h == 0 ? *set->hy_bad : *set->hy_good;
+            std::string err;
+            ScorePlan p;
+            std::vector<int> gcb;
+            try {
+                p = plan_score(ss, n_rows, c.n_utt, opt, c.flags, n_cu);
+                const int64_t n_tiles = (int64_t)c.n_utt * ((c.utt_len + p.tile_frames - 1) / p.tile_frames);
+                gcb = plan_groups(ss, p, (int)n_tiles, opt, n_cu);
+            } catch (const std::exception &e) {
+                err = e.what();
+            }
+            if (c.fail || !err.empty()) {
+                if (!c.fail || err != c.fail) { printf("plan '%s': error '%s', want '%s'\n", c.name, err.c_str(), c.fail ? c.fail : "(none)"); bad++; }
+                continue;
+            }
+            const auto &w = c.want[h];
+            const int got[9] = {(int)p.engine, p.F, p.FT, p.h2s_shape, p.splitp_w, p.split_cpm, p.tile_frames, p.per_tile, (int)p.writes_oor};
+            long long gsum = 0;
+            for (size_t g = 0; g < gcb.size(); g++) gsum += (long long)gcb[g] * (long long)(g + 1);
+            if (std::memcmp(got, w.v, sizeof got) != 0 || (int)gcb.size() - 1 != w.G || gsum != w.gsum) {
+                printf("plan '%s'[%d]: got {%d, %d, %d, %d, %d, %d, %d, %d, %d}, %d, %lld; want {%d, %d, %d, %d, %d, %d, %d, %d, %d}, %d, %lld\n", c.name, h,
+                       got[0], got[1], got[2], got[3], got[4], got[5], got[6], got[7], got[8], (int)gcb.size() - 1, gsum,
+                       w.v[0], w.v[1], w.v[2], w.v[3], w.v[4], w.v[5], w.v[6], w.v[7], w.v[8], w.G, w.gsum);
+                bad++;
+            }
+        }
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "plan") == 0) {
+        const int bad = check_plan();
+        if (bad) return printf("plan: %d cases differ\n", bad), 80;
+        printf("host checks ok\n");
+        return 0;
+    }
     const bool big = argc > 1 && std::strcmp(argv[1], "threads") == 0;     // sizes at which the packers go multi-threaded
     int rc = big ? check_packers(150, 1024, 39) : (check_packers(17, 37, 13) | check_packers(31, 64, 39));
     if (rc) return printf("packers: %d\n", rc), 10 + rc;

@@ -1,4 +1,4 @@
-"""csrc/gmm_model.cpp (text format, number conversions, every packer) under AddressSanitizer + UBSan, and the threaded
+"""csrc/gmm_model.cpp (text format, number conversions, every packer) and csrc/score_plan.cpp (the dispatcher) under AddressSanitizer + UBSan, and the threaded
 packers under ThreadSanitizer: tests/host/host_checks.cpp, built here with g++ (host code only, no GPU, no HIP runtime)."""
 import os
 import shutil
@@ -14,6 +14,7 @@ def _build_and_run(tmp_path, flags, args, env=None):
     exe = str(tmp_path / "host_checks")
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer", *flags, "-I", CSRC, "-I", "/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", os.path.join(ROOT, "tests", "host", "host_checks.cpp"), os.path.join(CSRC, "gmm_model.cpp"),
+           os.path.join(CSRC, "score_plan.cpp"),
            "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-2000:]
@@ -24,6 +25,14 @@ def _build_and_run(tmp_path, flags, args, env=None):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_model_host_code_under_asan_ubsan(tmp_path):
     _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], [],
+                   env={"ASAN_OPTIONS": "detect_leaks=1"})
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_score_plan_under_asan_ubsan(tmp_path):
+    """The dispatcher's decisions (engine, shapes, model groups) on sets packed by the library's own pack_model_set, against the
+    values recorded from the commit before the plan became a function of its own (tests/host/host_checks.cpp, mode "plan")."""
+    _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], ["plan"],
                    env={"ASAN_OPTIONS": "detect_leaks=1"})
 
 
