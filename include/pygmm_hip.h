@@ -295,6 +295,7 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *   "multi_numa_bind" 0: sr_multi slot threads leave their CPU affinity alone (default 1: bound to the cores of their GPU's NUMA
  *                    node, intersected with the mask the thread already has),
  *   "multi_merge_same_device" 0: slots that share a device get a host thread each (default 1: one queue per device).
+ *   "full_fit_batch_bytes" the workspace bound, in bytes (>= 1; default 1 GiB), of a group of speakers in sr_fullgmm_fit_batch.
  * The rest select kernel variants for A/B runs and tests. */
 int sr_set_option(const char *key, long value);
 /* Counters of the partial-product path since the library was loaded: resolve calls, (frame tile, model) pairs
@@ -353,6 +354,27 @@ SRFullGMM *sr_fullgmm_create(int K, int D, const double *weights, const double *
  * Cholesky meets a pivot <= 0 fails the fit with scikit-learn's message ("Fitting the mixture model failed because some
  * components have ill-defined empirical covariance ..."); the handle keeps its previous parameters then. */
 int sr_fullgmm_fit(SRFullGMM *g, const double *X, int64_t n, int D, const struct SRFullFitParams *params, struct SRFullFitStats *out);
+/* S >= 1 handles of one K and D fitted together: every EM iteration is one set of launches for the whole batch, the stop rule
+ * is applied per speaker on the device, and the host reads one small record per speaker and iteration.  X: the speakers' rows
+ * one after the other; row_offsets [S + 1] (speaker s owns rows row_offsets[s] .. row_offsets[s + 1]); params / out / status: [S].
+ * status[s]: 0 fitted, -1 failed (the handle keeps its previous parameters; sr_fullgmm_fit_batch_error(s) gives the reason, for a
+ * pivot <= 0 scikit-learn's "ill-defined empirical covariance" text).  Returns 0 when the call itself ran (even if speakers
+ * failed), -1 on a bad argument -- every argument is checked before the device is touched: S >= 1, offsets from 0 that do not
+ * decrease, one K and D, no handle twice, and per speaker what sr_fullgmm_fit checks -- or a device error (sr_last_error()).
+ * Every fitted speaker's parameters, n_iter, converged and lower_bound are the bits sr_fullgmm_fit gives for that speaker alone,
+ * whatever the batch around it.  Large batches are cut into groups of speakers whose workspace stays under
+ * sr_set_option("full_fit_batch_bytes", bytes) (default 1 GiB; a single speaker above it is a group of its own); the cut does
+ * not show in any result. */
+int sr_fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const int64_t *row_offsets, int D,
+                         const struct SRFullFitParams *params, struct SRFullFitStats *out, int *status);
+/* Why speaker s of the calling thread's last sr_fullgmm_fit_batch failed ("" when it did not, or s is out of range).  The pointer
+ * is valid until that thread's next sr_fullgmm_fit_batch. */
+const char *sr_fullgmm_fit_batch_error(int s);
+/* Counters since the library was loaded: sr_fullgmm_fit_batch calls that reached the device, the speakers they carried, and the
+ * batch iterations launched (one per set of E- and M-step launches, whatever the number of speakers in it).  Any pointer may be NULL. */
+void sr_full_fit_batch_stats(long *calls, long *speakers, long *iterations);
+/* The current value of the option "full_fit_batch_bytes". */
+long sr_full_fit_batch_bytes(void);
 /* K and D of a handle; 1 when it has parameters, 0 when not, -1 on error.  Either pointer may be NULL. */
 int sr_fullgmm_info(SRFullGMM *g, int *K, int *D);
 /* Copies the parameters out; any pointer may be NULL.  covariances: the last M-step's (zeros for a model built from arrays). */

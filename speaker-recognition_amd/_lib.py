@@ -35,6 +35,7 @@ EXT_SYMBOLS = [
     "sr_fullgmm_create", "sr_fullgmm_fit", "sr_fullgmm_info", "sr_fullgmm_get", "sr_fullgmm_free", "sr_fullset_create",
     "sr_fullset_score_batch", "sr_fullset_free", "sr_fullset_predict_pcm_batch", "sr_stream_create_full", "sr_multi_create_full",
     "sr_stream_create_vad", "sr_stream_collect_vad",
+    "sr_fullgmm_fit_batch", "sr_fullgmm_fit_batch_error", "sr_full_fit_batch_stats", "sr_full_fit_batch_bytes",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -167,6 +168,11 @@ def lib():
         "sr_hbm_copy_gbps": (i32, [C.c_size_t, i32, dp]),
         "sr_fullgmm_create": (vp, [i32, i32, dp, dp, dp]),
         "sr_fullgmm_fit": (i32, [vp, dp, i64, i32, C.POINTER(FullFitParams), C.POINTER(FullFitStats)]),
+        "sr_fullgmm_fit_batch": (i32, [C.POINTER(vp), i32, dp, C.POINTER(i64), i32, C.POINTER(FullFitParams), C.POINTER(FullFitStats),
+                                       C.POINTER(i32)]),
+        "sr_fullgmm_fit_batch_error": (C.c_char_p, [i32]),
+        "sr_full_fit_batch_stats": (None, [C.POINTER(C.c_long)] * 3),
+        "sr_full_fit_batch_bytes": (C.c_long, []),
         "sr_fullgmm_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "sr_fullgmm_get": (i32, [vp, dp, dp, dp, dp]),
         "sr_fullgmm_free": (None, [vp]),
@@ -289,6 +295,18 @@ def kmeans_fast_stats():
     v = [C.c_long(0) for _ in range(2)]
     lib().sr_kmeans_fast_stats(*[C.byref(x) for x in v])
     return tuple(int(x.value) for x in v)
+
+
+def full_fit_batch_stats():
+    """(sr_fullgmm_fit_batch calls that reached the device, speakers they carried, batch iterations launched)"""
+    v = [C.c_long(0) for _ in range(3)]
+    lib().sr_full_fit_batch_stats(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def full_fit_batch_bytes() -> int:
+    """The current value of the option ``full_fit_batch_bytes``."""
+    return int(lib().sr_full_fit_batch_bytes())
 
 
 def mfma_peak_probe(ms_target: float = 50.0):

@@ -887,6 +887,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "debug_helper_max_models") {
         if (value < 0) fail("debug_helper_max_models must be >= 0 (0: the default)");
         fork_proxy_set_max_models(value);                           // test hook (tests/test_gpu_fork.py): applies in the helper, where it is forwarded
+    } else if (k == "full_fit_batch_bytes") {
+        if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
+        set_full_fit_batch_bytes(value);
     } else if (k == "mfcc_generic") {
         mfcc_set_force_generic(value != 0);
     } else if (k == "mfcc_precision") {
@@ -973,6 +976,30 @@ int sr_fullgmm_fit(SRFullGMM *g, const double *X, int64_t n, int D, const SRFull
     return 0;
     SR_CATCH(-1)
 }
+
+namespace {
+thread_local std::vector<std::string> g_fit_batch_messages;      // of the calling thread's last sr_fullgmm_fit_batch
+}  // namespace
+
+int sr_fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
+                         SRFullFitStats *out, int *status) {
+    SR_TRY
+    g_fit_batch_messages.clear();
+    if (!models || !X || !row_offsets || !params || !out || !status) fail("null argument");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_fullgmm_fit_batch");
+    fullgmm_fit_batch(models, S, X, row_offsets, D, params, out, status, g_fit_batch_messages);
+    return 0;
+    SR_CATCH(-1)
+}
+
+const char *sr_fullgmm_fit_batch_error(int s) {
+    const auto &m = g_fit_batch_messages;
+    return s >= 0 && (size_t)s < m.size() ? m[(size_t)s].c_str() : "";
+}
+
+void sr_full_fit_batch_stats(long *calls, long *speakers, long *iterations) { full_fit_batch_stats(calls, speakers, iterations); }
+
+long sr_full_fit_batch_bytes(void) { return full_fit_batch_bytes(); }
 
 int sr_fullgmm_info(SRFullGMM *g, int *K, int *D) {
     SR_TRY

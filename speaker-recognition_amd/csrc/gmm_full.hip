@@ -20,12 +20,19 @@
 // stop rule.  The statistics run on the vector ALU in float64: at speaker size (K 32, D 28, ~5600 frames) the covariance GEMMs are
 // 8e7 FMAs per iteration, microseconds of arithmetic, while a measured iteration takes ~0.4 ms (K-wide per-mixture kernels, DESIGN
 // section 7); the fp64 MFMA (D = 28 padded to 32, the responsibility applied to an operand first) was therefore not tried.
+// A set of speakers of one K and D is fitted in the same launches (fullgmm_fit_batch): the kernels' bodies with a speaker axis, the
+// stop rule per speaker on the device, one 16-byte record per speaker read back per iteration -- and every speaker's bits those of
+// its single fit ("Batched training").
 #include "gmm_full.hpp"
 
+#include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <limits>
+#include <string>
 #include <vector>
 
 namespace sr {
@@ -219,13 +226,12 @@ struct FeArgs {
 };
 
 // weighted log densities: -1/2 (D ln 2 pi + |P^T (x - mu)|^2) + log det + ln w  (sklearn _estimate_log_gaussian_prob + _estimate_log_weights)
-__global__ __launch_bounds__(256)
-void fe_logprob_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_logprob(const FeArgs &a, const unsigned bx, const int k) {
     extern __shared__ double fe_lds[];
-    const int D = a.D, k = blockIdx.y, XS = D + 1;
+    const int D = a.D, XS = D + 1;
     double *sP = fe_lds, *sMu = sP + D * D, *sDiff = sMu + D, *sQ = sDiff + FE_FB * XS;
     const int tid = threadIdx.x, f = tid & (FE_FB - 1), g = tid / FE_FB;
-    const long f0 = (long)blockIdx.x * FE_FB;
+    const long f0 = (long)bx * FE_FB;
     for (int i = tid; i < D * D; i += 256) sP[i] = a.prec[(size_t)k * D * D + i];
     for (int i = tid; i < D; i += 256) sMu[i] = a.mu[(size_t)k * D + i];
     __syncthreads();
@@ -250,9 +256,8 @@ void fe_logprob_kernel(const FeArgs a) {
 }
 
 // a frame's log-sum-exp (max + log sum exp(a - max)) and its responsibilities exp(lp - lse), in place
-__global__ __launch_bounds__(256)
-void fe_lse_kernel(const FeArgs a) {
-    const long f = (long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void fe_lse(const FeArgs &a, const unsigned bx) {
+    const long f = (long)bx * 256 + threadIdx.x;
     if (f >= a.n) return;
     double *row = a.lp + (size_t)f * a.K;
     double m = -__builtin_inf();
@@ -277,8 +282,7 @@ __device__ double fe_block_sum(double v, double *red) {
     return t;
 }
 
-__global__ __launch_bounds__(256)
-void fe_bound_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_bound(const FeArgs &a) {
     __shared__ double red[256];
     double s = 0.0;
     for (long f = threadIdx.x; f < a.n; f += 256) s += a.lpn[f];
@@ -287,10 +291,9 @@ void fe_bound_kernel(const FeArgs a) {
 }
 
 // nk = sum resp + 10 eps, means = resp^T X / nk (the new means: the covariance below is formed around them)
-__global__ __launch_bounds__(256)
-void fe_means_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_means(const FeArgs &a, const int k) {
     __shared__ double red[256];
-    const int k = blockIdx.x, K = a.K, D = a.D;
+    const int K = a.K, D = a.D;
     double s = 0.0;
     for (long f = threadIdx.x; f < a.n; f += 256) s += a.lp[(size_t)f * K + k];
     const double nk = fe_block_sum(s, red) + 10.0 * DBL_EPSILON;
@@ -304,11 +307,10 @@ void fe_means_kernel(const FeArgs a) {
 }
 
 // sum over a chunk of frames of resp (x - mu)(x - mu)^T, the upper triangle, pair p = (i, j >= i) in row order
-__global__ __launch_bounds__(256)
-void fe_cov_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_cov(const FeArgs &a, const int k, const int c) {
     __shared__ double sDiff[FE_CB * (FULL_MAX_D + 1)];
     __shared__ double sR[FE_CB];
-    const int k = blockIdx.x, c = blockIdx.y, D = a.D, K = a.K, XS = D + 1, npairs = D * (D + 1) / 2;
+    const int D = a.D, K = a.K, XS = D + 1, npairs = D * (D + 1) / 2;
     int pi[FE_PQ], pj[FE_PQ];
     double acc[FE_PQ];
 #pragma unroll
@@ -350,11 +352,10 @@ void fe_cov_kernel(const FeArgs a) {
 }
 
 // covariance = chunk sums in order / nk + reg I; Cholesky L (a pivot <= 0 sets the failure flag); P = (L^-1)^T; log det = sum ln P_ii
-__global__ __launch_bounds__(64)
-void fe_chol_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_chol(const FeArgs &a, const int k) {
     __shared__ double sA[FULL_MAX_D * (FULL_MAX_D + 1)];
     __shared__ int bad;
-    const int k = blockIdx.x, D = a.D, XS = D + 1, npairs = D * (D + 1) / 2, t = threadIdx.x;
+    const int D = a.D, XS = D + 1, npairs = D * (D + 1) / 2, t = threadIdx.x;
     if (t == 0) bad = 0;
     const double nk = a.nk[k];
     double *cov = a.cov + (size_t)k * D * D, *P = a.prec + (size_t)k * D * D;
@@ -407,7 +408,7 @@ void fe_chol_kernel(const FeArgs a) {
 }
 
 // mode 0 (EM): w = nk / sum nk; mode 1 (k-means initialisation): w = nk / n.  Then ln w.
-__global__ void fe_weights_kernel(const FeArgs a, int mode) {
+__device__ __forceinline__ void fe_weights(const FeArgs &a, const int mode) {
     if (threadIdx.x != 0) return;
     double tot = 0.0;
     if (mode == 0)
@@ -421,7 +422,7 @@ __global__ void fe_weights_kernel(const FeArgs a, int mode) {
 }
 
 // explicit initialisation: ln w and log det from the given arrays
-__global__ void fe_derive_kernel(const FeArgs a) {
+__device__ __forceinline__ void fe_derive(const FeArgs &a) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.K) return;
     double ld = 0.0;
@@ -430,23 +431,184 @@ __global__ void fe_derive_kernel(const FeArgs a) {
     a.logw[k] = log(a.w[k]);
 }
 
+// ---- one model: the bodies above, the launch's own block coordinates
+__global__ __launch_bounds__(256) void fe_logprob_kernel(const FeArgs a) { fe_logprob(a, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void fe_lse_kernel(const FeArgs a) { fe_lse(a, blockIdx.x); }
+__global__ __launch_bounds__(256) void fe_bound_kernel(const FeArgs a) { fe_bound(a); }
+__global__ __launch_bounds__(256) void fe_means_kernel(const FeArgs a) { fe_means(a, blockIdx.x); }
+__global__ __launch_bounds__(256) void fe_cov_kernel(const FeArgs a) { fe_cov(a, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(64) void fe_chol_kernel(const FeArgs a) { fe_chol(a, blockIdx.x); }
+__global__ void fe_weights_kernel(const FeArgs a, int mode) { fe_weights(a, mode); }
+__global__ void fe_derive_kernel(const FeArgs a) { fe_derive(a); }
+
+// ---- a batch of S models of one K and D (fullgmm_fit_batch): the same bodies with a speaker axis.  A workgroup looks its speaker
+// up, leaves at once when that speaker has stopped (converged, at max_iter, or failed), and otherwise runs the body on the speaker's
+// view -- the FeArgs a fit of that speaker alone would pass -- so inside a speaker every sum is formed by the same threads in the
+// same order as in the single fit.  The frame-parallel kernels (densities, log-sum-exp, covariance chunks) take (speaker, block)
+// pairs from a work list built once per batch: frame counts are ragged, and a grid sized by the longest speaker would mostly idle.
+enum { FE_ACTIVE = 0, FE_CONVERGED = 1, FE_MAX_ITER = 2, FE_FAILED = 3 };
+
+struct FeSpk {                      // the per-speaker table (device memory)
+    long row0, n;                   // first row of the speaker in the group's X / lp / lpn, its frames
+    int n_chunks, chunk;            // the covariance chunking of a fit of n frames
+    long o_partial;                 // its slice of `partial`; the K-sized slices (w, logw, mu, prec, logdet, cov, nk) are s * their size
+    double reg, tol, prev;          // prev: the bound of the iteration before
+    int max_iter, state;            // state: FE_*
+    int given, pad;                 // given: the fit starts from the handle's parameters (else from k-means labels)
+};
+struct FeRec {                      // what the host reads after every iteration
+    double bound;
+    int state, n_iter;
+};
+struct FeBatch {
+    const double *X;
+    int D, K, S;
+    double *w, *logw, *mu, *prec, *logdet, *cov, *lp, *lpn, *nk, *partial, *head;      // head: [S][2] lower bound, failure flag
+    FeSpk *spk;
+    FeRec *rec;
+    const int2 *wl_lp, *wl_lse, *wl_cov;       // (speaker, block of FE_FB frames / block of 256 frames / covariance chunk)
+    int only;                       // 0: every active speaker; the start's launches: 1 the k-means speakers only, 2 the given ones
+};
+
+__device__ __forceinline__ bool fe_stopped(const FeBatch &b, const int s) {
+    const FeSpk &t = b.spk[s];
+    return t.state != FE_ACTIVE || (b.only != 0 && b.only != 1 + t.given);
+}
+
+__device__ __forceinline__ FeArgs fe_view(const FeBatch &b, const int s) {
+    const FeSpk &t = b.spk[s];
+    const size_t K = b.K, D = b.D, row0 = t.row0;
+    FeArgs a;
+    a.X = b.X + row0 * D;
+    a.n = t.n;
+    a.D = b.D;
+    a.K = b.K;
+    a.n_chunks = t.n_chunks;
+    a.chunk = t.chunk;
+    a.w = b.w + s * K;
+    a.logw = b.logw + s * K;
+    a.mu = b.mu + s * K * D;
+    a.prec = b.prec + s * K * D * D;
+    a.logdet = b.logdet + s * K;
+    a.cov = b.cov + s * K * D * D;
+    a.lp = b.lp + row0 * K;
+    a.lpn = b.lpn + row0;
+    a.nk = b.nk + s * K;
+    a.partial = b.partial + t.o_partial;
+    a.head = b.head + 2 * (size_t)s;
+    a.reg = t.reg;
+    return a;
+}
+
+__global__ __launch_bounds__(256) void fe_logprob_batch_kernel(const FeBatch b) {
+    const int2 wi = b.wl_lp[blockIdx.x];
+    if (fe_stopped(b, wi.x)) return;
+    fe_logprob(fe_view(b, wi.x), wi.y, blockIdx.y);
+}
+__global__ __launch_bounds__(256) void fe_lse_batch_kernel(const FeBatch b) {
+    const int2 wi = b.wl_lse[blockIdx.x];
+    if (fe_stopped(b, wi.x)) return;
+    fe_lse(fe_view(b, wi.x), wi.y);
+}
+__global__ __launch_bounds__(256) void fe_bound_batch_kernel(const FeBatch b) {
+    if (fe_stopped(b, blockIdx.x)) return;
+    fe_bound(fe_view(b, blockIdx.x));
+}
+__global__ __launch_bounds__(256) void fe_means_batch_kernel(const FeBatch b) {
+    if (fe_stopped(b, blockIdx.y)) return;
+    fe_means(fe_view(b, blockIdx.y), blockIdx.x);
+}
+__global__ __launch_bounds__(256) void fe_cov_batch_kernel(const FeBatch b) {
+    const int2 wi = b.wl_cov[blockIdx.x];
+    if (fe_stopped(b, wi.x)) return;
+    fe_cov(fe_view(b, wi.x), blockIdx.y, wi.y);
+}
+__global__ __launch_bounds__(64) void fe_chol_batch_kernel(const FeBatch b) {
+    if (fe_stopped(b, blockIdx.y)) return;
+    fe_chol(fe_view(b, blockIdx.y), blockIdx.x);
+}
+__global__ void fe_weights_batch_kernel(const FeBatch b, int mode) {
+    if (fe_stopped(b, blockIdx.x)) return;
+    fe_weights(fe_view(b, blockIdx.x), mode);
+}
+__global__ void fe_derive_batch_kernel(const FeBatch b) {
+    if (fe_stopped(b, blockIdx.y)) return;
+    fe_derive(fe_view(b, blockIdx.y));
+}
+
+// the k-means start: one-hot responsibilities from the labels (label: [rows of the group])
+__global__ __launch_bounds__(256) void fe_onehot_batch_kernel(const FeBatch b, const int *__restrict__ label) {
+    const int2 wi = b.wl_lse[blockIdx.x];
+    if (fe_stopped(b, wi.x)) return;            // (launched with b.only = 1: the k-means speakers)
+    const FeSpk &t = b.spk[wi.x];
+    const long f = (long)wi.y * 256 + threadIdx.x;
+    if (f >= t.n) return;
+    const int l = label[t.row0 + f];
+    double *row = b.lp + (size_t)(t.row0 + f) * b.K;
+    for (int k = 0; k < b.K; k++) row[k] = k == l ? 1.0 : 0.0;
+}
+
+// fullgmm_fit's stop rule, per speaker, behind the M-step of iteration `it`: a failure flag fails the speaker; else the E-step's
+// bound of this iteration against the one before decides (the M-step of the converging iteration has run, as there).
+// it == 0: the M-step of the k-means start, which can only fail.
+__global__ void fe_stop_batch_kernel(const FeBatch b, int it) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= b.S) return;
+    FeSpk &t = b.spk[s];
+    if (t.state != FE_ACTIVE) return;
+    FeRec &r = b.rec[s];
+    const double *head = b.head + 2 * (size_t)s;
+    r.n_iter = it;
+    if (head[1] != 0.0) {
+        t.state = r.state = FE_FAILED;
+        return;
+    }
+    if (it == 0) return;
+    const double lower = head[0];
+    r.bound = lower;
+    if (fabs(lower - t.prev) < t.tol) t.state = r.state = FE_CONVERGED;
+    else if (it >= t.max_iter) t.state = r.state = FE_MAX_ITER;
+    t.prev = lower;
+}
+
 struct FeWorkspace {
     DevBuf<double> X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head;
 };
 FeWorkspace &few() { return per_device<FeWorkspace>(); }
 
+struct FeBatchWorkspace {
+    DevBuf<double> X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head;
+    DevBuf<FeSpk> spk;
+    DevBuf<FeRec> rec;
+    DevBuf<int2> wl_lp, wl_lse, wl_cov;
+    DevBuf<int> label;
+    PinnedBuf<FeRec> h_rec;
+};
+
+// sr_set_option("full_fit_batch_bytes"): 1 GiB holds 100 speakers of 5600 x 28 at K 32 (5.5 MB each: X, lp, lpn, the chunk sums,
+// the parameters and tables) in one group with room to spare.  The workspace only grows and is kept for the next call, like the
+// library's other per-device workspaces: after a batch a process holds up to this much device memory.
+std::atomic<long> g_fit_batch_bytes{1L << 30};
+std::atomic<long> g_fit_batch_calls{0}, g_fit_batch_speakers{0}, g_fit_batch_iterations{0};
+
+// the argument checks of fullgmm_fit (no device work)
+void fe_check_args(const SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, const char *who) {
+    const int K = g.K;
+    if (D != g.D) fail("%sdata has %d columns, the model %d", who, D, g.D);
+    if (n < K) fail("%sExpected n_samples >= n_components but got n_components = %d, n_samples = %ld", who, K, n);
+    if (p.max_iter < 1) fail("%smax_iter must be >= 1 (got %d)", who, p.max_iter);
+    if (p.init_given && !g.trained) fail("%sinit_given: the handle has no parameters", who);
+    if (!(p.reg_covar >= 0.0) || !(p.tol >= 0.0)) fail("%stol and reg_covar must be >= 0", who);
+    if (p.seed < 0) fail("%sseed must be >= 0", who);
+    for (long e = 0; e < n * D; e++)
+        if (!std::isfinite(X[e])) fail("%sInput X contains NaN or infinity.", who);
+}
+
 }  // namespace
 
 void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out) {
     const int K = g.K;
-    if (D != g.D) fail("data has %d columns, the model %d", D, g.D);
-    if (n < K) fail("Expected n_samples >= n_components but got n_components = %d, n_samples = %ld", K, n);
-    if (p.max_iter < 1) fail("max_iter must be >= 1 (got %d)", p.max_iter);
-    if (p.init_given && !g.trained) fail("init_given: the handle has no parameters");
-    if (!(p.reg_covar >= 0.0) || !(p.tol >= 0.0)) fail("tol and reg_covar must be >= 0");
-    if (p.seed < 0) fail("seed must be >= 0");
-    for (long e = 0; e < n * D; e++)
-        if (!std::isfinite(X[e])) fail("Input X contains NaN or infinity.");
+    fe_check_args(g, X, n, D, p, "");
     ensure_device();
     auto &ws = few();
     const int npairs = D * (D + 1) / 2;
@@ -531,6 +693,232 @@ void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitPa
     ws.cov.download(g.covariances.data(), (size_t)K * D * D);
     sync_stream();
     g.trained = true;
+}
+
+void set_full_fit_batch_bytes(long bytes) { g_fit_batch_bytes.store(bytes); }
+long full_fit_batch_bytes() { return g_fit_batch_bytes.load(); }
+
+void full_fit_batch_stats(long *calls, long *speakers, long *iterations) {
+    if (calls) *calls = g_fit_batch_calls.load();
+    if (speakers) *speakers = g_fit_batch_speakers.load();
+    if (iterations) *iterations = g_fit_batch_iterations.load();
+}
+
+namespace {
+
+// speakers [s0, s1) of a batch: one set of launches per EM iteration, one download of the S records behind it
+void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
+                  SRFullFitStats *out, int *status, std::vector<std::string> &messages) {
+    const int S = s1 - s0, K = models[s0]->K, npairs = D * (D + 1) / 2;
+    const long r0 = (long)row_offsets[s0], rows = (long)row_offsets[s1] - r0;
+    auto &ws = per_device<FeBatchWorkspace>();
+    std::vector<FeSpk> spk((size_t)S);
+    std::vector<FeRec> rec((size_t)S);
+    std::vector<int2> wl_lp, wl_lse, wl_cov;
+    long o_partial = 0;
+    int max_iter = 0;
+    bool any_kmeans = false, any_given = false;
+    for (int i = 0; i < S; i++) {
+        const SRFullFitParams &p = params[s0 + i];
+        const long n = (long)(row_offsets[s0 + i + 1] - row_offsets[s0 + i]);
+        FeSpk &t = spk[i];
+        t.row0 = (long)row_offsets[s0 + i] - r0;
+        t.n = n;
+        t.n_chunks = (int)std::min<long>(32, (n + 255) / 256);         // (fullgmm_fit's chunking)
+        t.chunk = (int)((n + t.n_chunks - 1) / t.n_chunks);
+        t.o_partial = o_partial;
+        o_partial += (long)t.n_chunks * K * npairs;
+        t.reg = p.reg_covar;
+        t.tol = p.tol;
+        t.prev = -std::numeric_limits<double>::infinity();
+        t.max_iter = p.max_iter;
+        t.state = FE_ACTIVE;
+        t.given = p.init_given ? 1 : 0;
+        t.pad = 0;
+        rec[i] = FeRec{t.prev, FE_ACTIVE, 0};
+        max_iter = std::max(max_iter, p.max_iter);
+        (p.init_given ? any_given : any_kmeans) = true;
+        for (long b = 0; b < (n + FE_FB - 1) / FE_FB; b++) wl_lp.push_back(make_int2(i, (int)b));
+        for (long b = 0; b < (n + 255) / 256; b++) wl_lse.push_back(make_int2(i, (int)b));
+        for (int c = 0; c < t.n_chunks; c++) wl_cov.push_back(make_int2(i, c));
+    }
+    const size_t SK = (size_t)S * K;
+    ws.X.upload(X + (size_t)r0 * D, (size_t)rows * D);
+    ws.w.ensure(SK);
+    ws.logw.ensure(SK);
+    ws.mu.ensure(SK * D);
+    ws.prec.ensure(SK * D * D);
+    ws.logdet.ensure(SK);
+    ws.cov.ensure(SK * D * D);
+    ws.lp.ensure((size_t)rows * K);
+    ws.lpn.ensure((size_t)rows);
+    ws.nk.ensure(SK);
+    ws.partial.ensure((size_t)o_partial);
+    ws.head.ensure(2 * (size_t)S);
+    ws.spk.upload(spk.data(), spk.size());
+    ws.rec.upload(rec.data(), rec.size());
+    ws.wl_lp.upload(wl_lp.data(), wl_lp.size());
+    ws.wl_lse.upload(wl_lse.data(), wl_lse.size());
+    ws.wl_cov.upload(wl_cov.data(), wl_cov.size());
+    ws.h_rec.ensure((size_t)S);
+    FeBatch b{};
+    b.X = ws.X.p; b.D = D; b.K = K; b.S = S;
+    b.w = ws.w.p; b.logw = ws.logw.p; b.mu = ws.mu.p; b.prec = ws.prec.p; b.logdet = ws.logdet.p; b.cov = ws.cov.p;
+    b.lp = ws.lp.p; b.lpn = ws.lpn.p; b.nk = ws.nk.p; b.partial = ws.partial.p; b.head = ws.head.p;
+    b.spk = ws.spk.p; b.rec = ws.rec.p; b.wl_lp = ws.wl_lp.p; b.wl_lse = ws.wl_lse.p; b.wl_cov = ws.wl_cov.p;
+    hipStream_t st = ctx().stream;
+    SR_HIP(hipMemsetAsync(ws.head.p, 0, 2 * (size_t)S * sizeof(double), st));
+    const unsigned n_lp = (unsigned)wl_lp.size(), n_lse = (unsigned)wl_lse.size(), n_cov = (unsigned)wl_cov.size(), gs = (unsigned)((S + 63) / 64);
+    const size_t lds_lp = sizeof(double) * ((size_t)D * D + D + FE_FB * (D + 1) + 256);
+    auto mstep = [&](int weight_mode) {
+        hipLaunchKernelGGL(fe_means_batch_kernel, dim3(K, S), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(fe_cov_batch_kernel, dim3(n_cov, K), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(fe_chol_batch_kernel, dim3(K, S), dim3(64), 0, st, b);
+        hipLaunchKernelGGL(fe_weights_batch_kernel, dim3(S), dim3(64), 0, st, b, weight_mode);
+    };
+    auto read_records = [&]() {
+        SR_HIP(hipGetLastError());
+        SR_HIP(hipMemcpyAsync(ws.h_rec.p, ws.rec.p, (size_t)S * sizeof(FeRec), hipMemcpyDeviceToHost, st));
+        sync_stream();
+    };
+    // initialisation.  The given parameters go up first (whole arrays: a k-means speaker's slice is written by its M-step
+    // behind them); then the k-means speakers take their first M-step and the given ones their derive launch, each launch
+    // restricted to its kind by b.only.
+    std::vector<double> w0, mu0, prec0;
+    std::vector<int> label;
+    if (any_given) {
+        w0.assign(SK, 0.0);
+        mu0.assign(SK * D, 0.0);
+        prec0.assign(SK * D * D, 0.0);
+        for (int i = 0; i < S; i++) {
+            if (!params[s0 + i].init_given) continue;
+            const SRFullGMM &g = *models[s0 + i];
+            std::copy(g.weights.begin(), g.weights.end(), w0.begin() + (size_t)i * K);
+            std::copy(g.means.begin(), g.means.end(), mu0.begin() + (size_t)i * K * D);
+            std::copy(g.prec_chol.begin(), g.prec_chol.end(), prec0.begin() + (size_t)i * K * D * D);
+        }
+        ws.w.upload(w0.data(), w0.size());
+        ws.mu.upload(mu0.data(), mu0.size());
+        ws.prec.upload(prec0.data(), prec0.size());
+    }
+    if (any_kmeans) {
+        // sklearn's init_params='kmeans', speaker by speaker in batch order (kmeans_labels is host-sequenced)
+        label.assign((size_t)rows, 0);
+        std::vector<float> Xf;
+        for (int i = 0; i < S; i++) {
+            if (params[s0 + i].init_given) continue;
+            const double *Xs = X + (size_t)row_offsets[s0 + i] * D;
+            Xf.resize((size_t)spk[i].n * D);
+            for (size_t e = 0; e < Xf.size(); e++) Xf[e] = (float)Xs[e];
+            const std::vector<int> l = kmeans_labels(Xf.data(), spk[i].n, D, K, params[s0 + i].seed);
+            std::copy(l.begin(), l.end(), label.begin() + spk[i].row0);
+        }
+        ws.label.upload(label.data(), label.size());
+        b.only = 1;
+        hipLaunchKernelGGL(fe_onehot_batch_kernel, dim3(n_lse), dim3(256), 0, st, b, ws.label.p);
+        mstep(1);
+        hipLaunchKernelGGL(fe_stop_batch_kernel, dim3(gs), dim3(64), 0, st, b, 0);       // (a first M-step can only fail)
+    }
+    if (any_given) {
+        b.only = 2;
+        hipLaunchKernelGGL(fe_derive_batch_kernel, dim3((K + 63) / 64, S), dim3(64), 0, st, b);
+    }
+    b.only = 0;
+    bool active = true;
+    if (any_kmeans) {
+        read_records();
+        active = false;
+        for (int i = 0; i < S; i++) active = active || ws.h_rec.p[i].state == FE_ACTIVE;
+    }
+    for (int it = 1; active && it <= max_iter; it++) {
+        hipLaunchKernelGGL(fe_logprob_batch_kernel, dim3(n_lp, K), dim3(256), lds_lp, st, b);
+        hipLaunchKernelGGL(fe_lse_batch_kernel, dim3(n_lse), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(fe_bound_batch_kernel, dim3(S), dim3(256), 0, st, b);
+        mstep(0);
+        hipLaunchKernelGGL(fe_stop_batch_kernel, dim3(gs), dim3(64), 0, st, b, it);
+        read_records();
+        g_fit_batch_iterations++;
+        active = false;
+        for (int i = 0; i < S; i++) active = active || ws.h_rec.p[i].state == FE_ACTIVE;
+    }
+    std::vector<double> w(SK), mu(SK * D), prec(SK * D * D), cov(SK * D * D);
+    ws.w.download(w.data(), w.size());
+    ws.mu.download(mu.data(), mu.size());
+    ws.prec.download(prec.data(), prec.size());
+    ws.cov.download(cov.data(), cov.size());
+    sync_stream();
+    for (int i = 0; i < S; i++) {
+        const FeRec &r = ws.h_rec.p[i];
+        SRFullGMM &g = *models[s0 + i];
+        if (r.state == FE_FAILED) {
+            status[s0 + i] = -1;
+            messages[s0 + i] = FC_ILL_DEFINED;
+            continue;
+        }
+        status[s0 + i] = 0;
+        out[s0 + i].converged = r.state == FE_CONVERGED ? 1 : 0;
+        out[s0 + i].n_iter = r.n_iter;
+        out[s0 + i].lower_bound = r.bound;
+        g.weights.assign(w.begin() + (size_t)i * K, w.begin() + (size_t)(i + 1) * K);
+        g.means.assign(mu.begin() + (size_t)i * K * D, mu.begin() + (size_t)(i + 1) * K * D);
+        g.prec_chol.assign(prec.begin() + (size_t)i * K * D * D, prec.begin() + (size_t)(i + 1) * K * D * D);
+        g.covariances.assign(cov.begin() + (size_t)i * K * D * D, cov.begin() + (size_t)(i + 1) * K * D * D);
+        g.trained = true;
+    }
+}
+
+}  // namespace
+
+void fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
+                       SRFullFitStats *out, int *status, std::vector<std::string> &messages) {
+    if (S < 1) fail("a batch needs at least one speaker (S = %d)", S);
+    for (int s = 0; s < S; s++)
+        if (!models[s]) fail("speaker %d: null model handle", s);
+    if (row_offsets[0] != 0) fail("row_offsets must start at 0 (got %lld)", (long long)row_offsets[0]);
+    for (int s = 0; s < S; s++)
+        if (row_offsets[s + 1] < row_offsets[s])
+            fail("row_offsets must not decrease (speaker %d: %lld after %lld)", s, (long long)row_offsets[s + 1], (long long)row_offsets[s]);
+    const int K = models[0]->K;
+    for (int s = 1; s < S; s++) {
+        if (models[s]->K != K) fail("speaker %d has %d components, speaker 0 has %d: a batch is fitted with one K", s, models[s]->K, K);
+        if (models[s]->D != models[0]->D) fail("speaker %d has %d dims, speaker 0 has %d: a batch is fitted with one D", s, models[s]->D, models[0]->D);
+    }
+    {
+        std::vector<const SRFullGMM *> seen(models, models + S);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) fail("a model handle appears twice in the batch");
+    }
+    char who[32];
+    for (int s = 0; s < S; s++) {
+        snprintf(who, sizeof who, "speaker %d: ", s);
+        fe_check_args(*models[s], X + (size_t)row_offsets[s] * D, (long)(row_offsets[s + 1] - row_offsets[s]), D, params[s], who);
+    }
+    messages.assign((size_t)S, std::string());
+    ensure_device();
+    g_fit_batch_calls++;
+    g_fit_batch_speakers += S;
+    // groups of speakers, in batch order, whose workspace stays under full_fit_batch_bytes (a speaker larger than that is a group
+    // of its own); a speaker's fit does not depend on its group
+    const long limit = g_fit_batch_bytes.load();
+    const size_t npairs = (size_t)D * (D + 1) / 2;
+    int s0 = 0;
+    while (s0 < S) {
+        size_t bytes = 0;
+        int s1 = s0;
+        while (s1 < S && s1 - s0 < 65535) {
+            const size_t n = (size_t)(row_offsets[s1 + 1] - row_offsets[s1]), chunks = std::min<size_t>(32, (n + 255) / 256);
+            // everything FeBatchWorkspace holds for the speaker: X, lp, lpn, partial, the parameters, head; the three work lists,
+            // the k-means labels, its table entry and record
+            const size_t need = sizeof(double) * (n * D + n * K + n + chunks * K * npairs + (size_t)K * (2 * D * D + D + 4) + 2) +
+                                sizeof(int2) * ((n + FE_FB - 1) / FE_FB + (n + 255) / 256 + chunks) + sizeof(int) * n + sizeof(FeSpk) +
+                                sizeof(FeRec);
+            if (s1 > s0 && bytes + need > (size_t)limit) break;
+            bytes += need;
+            s1++;
+        }
+        fe_fit_group(models, s0, s1, X, row_offsets, D, params, out, status, messages);
+        s0 = s1;
+    }
 }
 
 void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S) {

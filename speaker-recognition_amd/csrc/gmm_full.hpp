@@ -8,6 +8,7 @@
 
 #include "../../include/pygmm_hip.h"
 
+#include <string>
 #include <vector>
 
 // One model: weights[K], means[K][D], precisions_cholesky[K][D][D] (upper triangular P_k, precision = P_k P_k^T), float64 on the
@@ -36,6 +37,13 @@ struct SRFullSet {
 namespace sr {
 constexpr int FULL_MAX_D = 64;
 void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out);
+// S models of one K and D in one set of launches per EM iteration (the stop rule per speaker, on the device); every fitted
+// speaker gets the bits fullgmm_fit gives it alone.  status[s]: 0 fitted, -1 failed (messages[s] says why; the handle is untouched).
+void fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
+                       SRFullFitStats *out, int *status, std::vector<std::string> &messages);
+long full_fit_batch_bytes();
+void set_full_fit_batch_bytes(long bytes);       // sr_set_option("full_fit_batch_bytes"): the workspace bound of a group of speakers
+void full_fit_batch_stats(long *calls, long *speakers, long *iterations);
 void fullset_pack(SRFullSet &set, const SRFullGMM *const *models, int S);
 void fullset_score(SRFullSet &set, SRBatch &batch, double *sums, int *argmax, float *frame_ll);
 // Launches only (capturable): scoring + finalize of a feature batch on the calling thread's stream.  Returns set.res: sums [U][S]

@@ -92,8 +92,12 @@ class ModelInterface(object):
         start = time.time()
         if self.verbose:
             print("Start training...")
-        for name, feats in self.features.items():
-            self.gmmset.fit_new(np.asarray(feats), name)
+        if getattr(self, "covariance_type", "diag") == "full":
+            # every speaker in one batched device EM: the models of a loop of fit_new, bit for bit
+            self.gmmset.fit_many([np.asarray(feats) for feats in self.features.values()], list(self.features.keys()))
+        else:
+            for name, feats in self.features.items():
+                self.gmmset.fit_new(np.asarray(feats), name)
         if self.verbose:
             print(time.time() - start, " seconds")
 

@@ -196,6 +196,28 @@ class GMM(object):
                           "max_iter, tol, or check for degenerate data.", ConvergenceWarning)
         return self
 
+    def _new_handle(self, D):
+        """A fresh device-side model for a fit on D columns: the explicit initialisation when one was given, else no parameters.
+        -> (handle, init_given).  This restates the first half of ``fit``, which keeps its own copy so that the single fit stays
+        as it was: a change to either belongs in both."""
+        K = self.n_components
+        init = self.weights_init is not None
+        if init:
+            w = np.ascontiguousarray(self.weights_init, dtype=np.float64)
+            mu = np.ascontiguousarray(self.means_init, dtype=np.float64)
+            if w.shape != (K,) or mu.shape != (K, D):
+                raise ValueError("weights_init must be [%d], means_init [%d, %d]" % (K, K, D))
+            prec = np.asarray(self.precisions_init, dtype=np.float64)
+            if prec.shape != (K, D, D):
+                raise ValueError("precisions_init must be [%d, %d, %d]" % (K, D, D))
+            P = np.ascontiguousarray(_precision_cholesky_from_precisions(prec))
+            h = lib().sr_fullgmm_create(K, D, _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(P))
+        else:
+            h = lib().sr_fullgmm_create(K, D, None, None, None)
+        if not h:
+            _raise_lib("sr_fullgmm_create")
+        return C.c_void_p(h), init
+
     # ---- scoring ----
     def score_samples(self, X) -> np.ndarray:
         """Per-frame log-likelihood (fp32 on the device, returned as float64)."""
@@ -228,6 +250,80 @@ class GMM(object):
     def __setstate__(self, d):
         self.__dict__.update(d)
         self._h = None
+
+
+def fit_many(gmms, Xs):
+    """Fit the unfitted models ``gmms[s]`` on the matrices ``Xs[s]`` in one batched device EM (``sr_fullgmm_fit_batch``): all
+    models share ``n_components`` and all matrices the feature width; frame counts, ``tol``, ``max_iter``, ``reg_covar``,
+    ``random_state`` and explicit initialisations are per model.  Every fitted model ends up exactly as ``gmms[s].fit(Xs[s])``
+    leaves it, bit for bit -- ``weights_``, ``means_``, ``covariances_``, ``precisions_cholesky_``, ``converged_``, ``n_iter_``,
+    ``lower_bound_``, a device handle -- with a ``ConvergenceWarning`` per model that stopped at ``max_iter``.
+
+    -> a list with one entry per model: ``None`` for a fitted model, and for a model whose fit failed on the device (an
+    ill-defined empirical covariance) the ``ValueError`` that ``fit`` would have raised, as an object, not raised; that model is
+    left as it was.  Bad arguments (lengths, shapes, too few rows, non-finite data) raise for the call as a whole, before
+    any model changes."""
+    gmms, Xs = list(gmms), list(Xs)
+    if len(gmms) != len(Xs):
+        raise ValueError("fit_many: %d models but %d matrices" % (len(gmms), len(Xs)))
+    if not gmms:
+        return []
+    if len(set(id(g) for g in gmms)) != len(gmms):
+        raise ValueError("fit_many: a model appears twice")
+    K = gmms[0].n_components
+    Xs = [g._check_X(X) for g, X in zip(gmms, Xs)]
+    D = Xs[0].shape[1]
+    for s, (g, X) in enumerate(zip(gmms, Xs)):
+        if g.n_components != K:
+            raise ValueError("fit_many: model %d has %d components, model 0 has %d" % (s, g.n_components, K))
+        if X.shape[1] != D:
+            raise ValueError("fit_many: matrix %d has %d features, matrix 0 has %d" % (s, X.shape[1], D))
+        if X.shape[0] < K:
+            raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d (model %d)"
+                             % (K, X.shape[0], s))
+    S = len(gmms)
+    handles = []
+    try:
+        prm = (_lib.FullFitParams * S)()
+        for s, g in enumerate(gmms):
+            h, init = g._new_handle(D)
+            handles.append(h)
+            seed = DEFAULT_SEED if g.random_state is None else int(g.random_state)
+            prm[s] = _lib.FullFitParams(g.tol, g.reg_covar, g.max_iter, 1 if init else 0, seed)
+        off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum([X.shape[0] for X in Xs], out=off[1:])
+        Xall = Xs[0] if S == 1 else np.ascontiguousarray(np.concatenate(Xs, axis=0))
+        st = (_lib.FullFitStats * S)()
+        status = np.zeros(S, dtype=np.int32)
+        arr = (C.c_void_p * S)(*[h.value for h in handles])
+        if lib().sr_fullgmm_fit_batch(arr, S, _lib.as_dp(Xall), _lib.as_i64p(off), D, prm, st, _lib.as_i32p(status)) < 0:
+            _raise_lib("sr_fullgmm_fit_batch")
+        fitted = [None] * S
+        errors = [None] * S
+        for s in range(S):
+            if status[s] != 0:
+                errors[s] = ValueError(lib().sr_fullgmm_fit_batch_error(s).decode("utf-8", "replace"))
+                continue
+            w, mu = np.empty(K), np.empty((K, D))
+            cov, P = np.empty((K, D, D)), np.empty((K, D, D))
+            _lib.check(lib().sr_fullgmm_get(handles[s], _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(cov), _lib.as_dp(P)), "sr_fullgmm_get")
+            fitted[s] = (w, mu, cov, P)
+    except BaseException:
+        for h in handles:
+            lib().sr_fullgmm_free(h)
+        raise
+    for s, g in enumerate(gmms):
+        if fitted[s] is None:
+            lib().sr_fullgmm_free(handles[s])
+            continue
+        g._free()
+        g._h = handles[s]
+        g._set_params(*fitted[s])
+        g.converged_, g.n_iter_, g.lower_bound_ = bool(st[s].converged), int(st[s].n_iter), float(st[s].lower_bound)
+        if not g.converged_:
+            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase "
+                          "max_iter, tol, or check for degenerate data.", ConvergenceWarning)
+    return errors
 
 
 class FullSet(object):
@@ -302,6 +398,30 @@ class GMMSet(object):
         gmm = GMM(self.gmm_order, **self.gmm_kwargs)
         gmm.fit(x)
         self.gmms.append(gmm)
+
+    def fit_many(self, xs, labels):
+        """``fit_new`` for every (x, label) pair, the fits in one batched device EM (``skgmm.fit_many``): the same models bit
+        for bit, appended in order.  A speaker whose fit fails raises its ``ValueError`` with the set in the state a loop of
+        ``fit_new`` leaves: the earlier speakers in ``gmms``, their labels and the failing one in ``y``.  Arguments the batch
+        refuses as a whole (a matrix ``fit`` would refuse, matrices of different widths) go through that loop itself, which
+        raises where it always did."""
+        xs, labels = list(xs), list(labels)
+        if len(xs) != len(labels):
+            raise ValueError("fit_many: %d matrices but %d labels" % (len(xs), len(labels)))
+        gmms = [GMM(self.gmm_order, **self.gmm_kwargs) for _ in labels]
+        try:
+            errors = fit_many(gmms, xs)
+        except ValueError:
+            # an argument error, raised before any model changed.  Device errors are _lib.SRError, a RuntimeError, and must
+            # never land here: a failed batched fit is not to be answered by a second, sequential one
+            for x, label in zip(xs, labels):
+                self.fit_new(x, label)
+            return
+        for gmm, label, err in zip(gmms, labels, errors):
+            self.y.append(label)
+            if err is not None:
+                raise err
+            self.gmms.append(gmm)
 
     def gmm_score(self, gmm, x):
         """Summed per-frame log-likelihood of ``x`` under one model."""
