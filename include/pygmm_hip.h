@@ -352,7 +352,9 @@ struct SRFullFitStats {
 SRFullGMM *sr_fullgmm_create(int K, int D, const double *weights, const double *means, const double *prec_chol);
 /* EM in float64 on the device, as GaussianMixture.fit with n_init = 1.  X: [n][D] float64.  A component whose covariance's
  * Cholesky meets a pivot <= 0 fails the fit with scikit-learn's message ("Fitting the mixture model failed because some
- * components have ill-defined empirical covariance ..."); the handle keeps its previous parameters then. */
+ * components have ill-defined empirical covariance ..."); the handle keeps its previous parameters then.  The fit runs as a group
+ * of one in sr_fullgmm_fit_batch's driver; it moves none of sr_full_fit_batch_stats' counters, and "full_fit_batch_bytes" does
+ * not bear on it. */
 int sr_fullgmm_fit(SRFullGMM *g, const double *X, int64_t n, int D, const struct SRFullFitParams *params, struct SRFullFitStats *out);
 /* S >= 1 handles of one K and D fitted together: every EM iteration is one set of launches for the whole batch, the stop rule
  * is applied per speaker on the device, and the host reads one small record per speaker and iteration.  X: the speakers' rows

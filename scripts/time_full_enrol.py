@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Enrolling a full-covariance speaker set: the loop of single fits (skgmm.GMM.fit, one sr_fullgmm_fit per speaker) against the
-batched fit (skgmm.fit_many, one sr_fullgmm_fit_batch); one JSON line on stdout.
+"""Enrolling a full-covariance speaker set: the loop of single fits (skgmm.GMM.fit, one sr_fullgmm_fit per speaker: a loop of
+one-speaker groups through the EM driver) against the batched fit (skgmm.fit_many, one sr_fullgmm_fit_batch: the same driver on
+groups of many); one JSON line on stdout.
 
     python scripts/time_full_enrol.py [--speakers 10,100] [--reps 5] [--out profiles/full_enrol.json]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/time_full_enrol.py --batch-only 100      # per-kernel times

@@ -14,15 +14,16 @@
 // fullcov_finalize_kernel forms the same sums and, behind them, every utterance's argmax on the device: the serving paths (the
 // fused PCM call, the serving stream, the multi-GPU predictor) bring a decision back in one copy, with no host work in between.
 //
-// Training (float64, the whole fit on the device; em_f64.hip's pattern): an iteration is seven launches -- log densities,
-// log-sum-exp + responsibilities, the mean (lower bound), nk + means, the covariance sums by frame chunks, the per-mixture
-// Cholesky + inverse (one workgroup per mixture), the weights -- and the host reads 16 bytes ({lower bound, failure flag}) for the
-// stop rule.  The statistics run on the vector ALU in float64: at speaker size (K 32, D 28, ~5600 frames) the covariance GEMMs are
-// 8e7 FMAs per iteration, microseconds of arithmetic, while a measured iteration takes ~0.4 ms (K-wide per-mixture kernels, DESIGN
-// section 7); the fp64 MFMA (D = 28 padded to 32, the responsibility applied to an operand first) was therefore not tried.
-// A set of speakers of one K and D is fitted in the same launches (fullgmm_fit_batch): the kernels' bodies with a speaker axis, the
-// stop rule per speaker on the device, one 16-byte record per speaker read back per iteration -- and every speaker's bits those of
-// its single fit ("Batched training").
+// Training (float64, the whole fit on the device; em_f64.hip's pattern): one driver, fe_fit_group, fits a group of speakers of one
+// K and D in the same launches.  An iteration is eight launches -- log densities, log-sum-exp + responsibilities, the mean (lower
+// bound), nk + means, the covariance sums by frame chunks, the per-mixture Cholesky + inverse (one workgroup per mixture), the
+// weights, the stop rule per speaker -- and the host reads one 16-byte record per speaker.  The statistics run on the vector ALU
+// in float64: at speaker size (K 32, D 28, ~5600 frames) the covariance GEMMs are 8e7 FMAs per iteration, microseconds of
+// arithmetic, while a measured iteration takes ~0.4 ms (K-wide per-mixture kernels); the fp64 MFMA (D = 28
+// padded to 32, the responsibility applied to an operand first) was therefore not tried.
+// The kernels are the bodies below with a speaker axis; inside a speaker every sum is formed by the same threads in the same order
+// whatever the group, so a speaker's bits do not depend on the speakers fitted with it.  fullgmm_fit is a group of one,
+// fullgmm_fit_batch cuts its speakers into groups by workspace size ("Training").
 #include "gmm_full.hpp"
 
 #include <algorithm>
@@ -431,21 +432,11 @@ __device__ __forceinline__ void fe_derive(const FeArgs &a) {
     a.logw[k] = log(a.w[k]);
 }
 
-// ---- one model: the bodies above, the launch's own block coordinates
-__global__ __launch_bounds__(256) void fe_logprob_kernel(const FeArgs a) { fe_logprob(a, blockIdx.x, blockIdx.y); }
-__global__ __launch_bounds__(256) void fe_lse_kernel(const FeArgs a) { fe_lse(a, blockIdx.x); }
-__global__ __launch_bounds__(256) void fe_bound_kernel(const FeArgs a) { fe_bound(a); }
-__global__ __launch_bounds__(256) void fe_means_kernel(const FeArgs a) { fe_means(a, blockIdx.x); }
-__global__ __launch_bounds__(256) void fe_cov_kernel(const FeArgs a) { fe_cov(a, blockIdx.x, blockIdx.y); }
-__global__ __launch_bounds__(64) void fe_chol_kernel(const FeArgs a) { fe_chol(a, blockIdx.x); }
-__global__ void fe_weights_kernel(const FeArgs a, int mode) { fe_weights(a, mode); }
-__global__ void fe_derive_kernel(const FeArgs a) { fe_derive(a); }
-
-// ---- a batch of S models of one K and D (fullgmm_fit_batch): the same bodies with a speaker axis.  A workgroup looks its speaker
+// ---- a group of S models of one K and D (fe_fit_group): the bodies above with a speaker axis.  A workgroup looks its speaker
 // up, leaves at once when that speaker has stopped (converged, at max_iter, or failed), and otherwise runs the body on the speaker's
-// view -- the FeArgs a fit of that speaker alone would pass -- so inside a speaker every sum is formed by the same threads in the
-// same order as in the single fit.  The frame-parallel kernels (densities, log-sum-exp, covariance chunks) take (speaker, block)
-// pairs from a work list built once per batch: frame counts are ragged, and a grid sized by the longest speaker would mostly idle.
+// view -- the FeArgs of that speaker alone -- so inside a speaker every sum is formed by the same threads in the same order
+// whatever the group.  The frame-parallel kernels (densities, log-sum-exp, covariance chunks) take (speaker, block)
+// pairs from a work list built once per group: frame counts are ragged, and a grid sized by the longest speaker would mostly idle.
 enum { FE_ACTIVE = 0, FE_CONVERGED = 1, FE_MAX_ITER = 2, FE_FAILED = 3 };
 
 struct FeSpk {                      // the per-speaker table (device memory)
@@ -456,6 +447,11 @@ struct FeSpk {                      // the per-speaker table (device memory)
     int max_iter, state;            // state: FE_*
     int given, pad;                 // given: the fit starts from the handle's parameters (else from k-means labels)
 };
+// a speaker's launch geometry, each formula once: fe_fit_group builds the tables and work lists from them, fe_spk_bytes the group cut
+inline long fe_lp_blocks(long n) { return (n + FE_FB - 1) / FE_FB; }                      // density workgroups
+inline long fe_lse_blocks(long n) { return (n + 255) / 256; }                             // log-sum-exp / one-hot workgroups
+inline int fe_n_chunks(long n) { return (int)std::min<long>(32, (n + 255) / 256); }       // covariance chunks
+inline size_t fe_partial_len(long n, int K, int D) { return (size_t)fe_n_chunks(n) * K * (D * (D + 1) / 2); }
 struct FeRec {                      // what the host reads after every iteration
     double bound;
     int state, n_iter;
@@ -548,8 +544,8 @@ __global__ __launch_bounds__(256) void fe_onehot_batch_kernel(const FeBatch b, c
     for (int k = 0; k < b.K; k++) row[k] = k == l ? 1.0 : 0.0;
 }
 
-// fullgmm_fit's stop rule, per speaker, behind the M-step of iteration `it`: a failure flag fails the speaker; else the E-step's
-// bound of this iteration against the one before decides (the M-step of the converging iteration has run, as there).
+// The stop rule (scikit-learn's), per speaker, behind the M-step of iteration `it`: a failure flag fails the speaker; else the E-step's
+// bound of this iteration against the one before decides (the M-step of the converging iteration has run, as in scikit-learn).
 // it == 0: the M-step of the k-means start, which can only fail.
 __global__ void fe_stop_batch_kernel(const FeBatch b, int it) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -571,11 +567,6 @@ __global__ void fe_stop_batch_kernel(const FeBatch b, int it) {
     t.prev = lower;
 }
 
-struct FeWorkspace {
-    DevBuf<double> X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head;
-};
-FeWorkspace &few() { return per_device<FeWorkspace>(); }
-
 struct FeBatchWorkspace {
     DevBuf<double> X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head;
     DevBuf<FeSpk> spk;
@@ -584,6 +575,13 @@ struct FeBatchWorkspace {
     DevBuf<int> label;
     PinnedBuf<FeRec> h_rec;
 };
+// the device memory a speaker of n frames takes in it: X, lp, lpn, partial, the parameters (prec and cov, mu, w logw logdet nk),
+// head; the three work lists, the k-means labels, its table entry and record
+size_t fe_spk_bytes(long n, int K, int D) {
+    const size_t N = (size_t)n, KD = (size_t)K * D;
+    return sizeof(double) * (N * D + N * K + N + fe_partial_len(n, K, D) + 2 * KD * D + KD + 4 * K + 2) +
+           sizeof(int2) * (size_t)(fe_lp_blocks(n) + fe_lse_blocks(n) + fe_n_chunks(n)) + sizeof(int) * N + sizeof(FeSpk) + sizeof(FeRec);
+}
 
 // sr_set_option("full_fit_batch_bytes"): 1 GiB holds 100 speakers of 5600 x 28 at K 32 (5.5 MB each: X, lp, lpn, the chunk sums,
 // the parameters and tables) in one group with room to spare.  The workspace only grows and is kept for the next call, like the
@@ -591,7 +589,7 @@ struct FeBatchWorkspace {
 std::atomic<long> g_fit_batch_bytes{1L << 30};
 std::atomic<long> g_fit_batch_calls{0}, g_fit_batch_speakers{0}, g_fit_batch_iterations{0};
 
-// the argument checks of fullgmm_fit (no device work)
+// the argument checks of a fit (no device work); `who`: "" or "speaker s: "
 void fe_check_args(const SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, const char *who) {
     const int K = g.K;
     if (D != g.D) fail("%sdata has %d columns, the model %d", who, D, g.D);
@@ -604,112 +602,11 @@ void fe_check_args(const SRFullGMM &g, const double *X, long n, int D, const SRF
         if (!std::isfinite(X[e])) fail("%sInput X contains NaN or infinity.", who);
 }
 
-}  // namespace
-
-void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out) {
-    const int K = g.K;
-    fe_check_args(g, X, n, D, p, "");
-    ensure_device();
-    auto &ws = few();
-    const int npairs = D * (D + 1) / 2;
-    FeArgs a{};
-    a.n = n;
-    a.D = D;
-    a.K = K;
-    a.n_chunks = (int)std::min<long>(32, (n + 255) / 256);
-    a.chunk = (int)((n + a.n_chunks - 1) / a.n_chunks);
-    a.reg = p.reg_covar;
-    ws.X.upload(X, (size_t)n * D);
-    ws.w.ensure(K);
-    ws.logw.ensure(K);
-    ws.mu.ensure((size_t)K * D);
-    ws.prec.ensure((size_t)K * D * D);
-    ws.logdet.ensure(K);
-    ws.cov.ensure((size_t)K * D * D);
-    ws.lp.ensure((size_t)n * K);
-    ws.lpn.ensure(n);
-    ws.nk.ensure(K);
-    ws.partial.ensure((size_t)a.n_chunks * K * npairs);
-    ws.head.ensure(2);
-    a.X = ws.X.p; a.w = ws.w.p; a.logw = ws.logw.p; a.mu = ws.mu.p; a.prec = ws.prec.p; a.logdet = ws.logdet.p; a.cov = ws.cov.p;
-    a.lp = ws.lp.p; a.lpn = ws.lpn.p; a.nk = ws.nk.p; a.partial = ws.partial.p; a.head = ws.head.p;
-    hipStream_t st = ctx().stream;
-    SR_HIP(hipMemsetAsync(ws.head.p, 0, 2 * sizeof(double), st));
-    const size_t lds_lp = sizeof(double) * ((size_t)D * D + D + FE_FB * (D + 1) + 256);
-    auto mstep = [&](int weight_mode) {
-        hipLaunchKernelGGL(fe_means_kernel, dim3(K), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(fe_cov_kernel, dim3(K, a.n_chunks), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(fe_chol_kernel, dim3(K), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(fe_weights_kernel, dim3(1), dim3(64), 0, st, a, weight_mode);
-    };
-    double head[2] = {0.0, 0.0};
-    if (p.init_given) {
-        ws.w.upload(g.weights.data(), K);
-        ws.mu.upload(g.means.data(), (size_t)K * D);
-        ws.prec.upload(g.prec_chol.data(), (size_t)K * D * D);
-        hipLaunchKernelGGL(fe_derive_kernel, dim3((K + 63) / 64), dim3(64), 0, st, a);
-    } else {
-        // sklearn's init_params='kmeans': one-hot responsibilities from k-means labels, then the M-step with weights nk / n
-        std::vector<float> Xf((size_t)n * D);
-        for (size_t e = 0; e < Xf.size(); e++) Xf[e] = (float)X[e];
-        const std::vector<int> label = kmeans_labels(Xf.data(), n, D, K, p.seed);
-        std::vector<double> resp((size_t)n * K, 0.0);
-        for (long f = 0; f < n; f++) resp[(size_t)f * K + label[f]] = 1.0;
-        ws.lp.upload(resp.data(), resp.size());
-        mstep(1);
-        SR_HIP(hipGetLastError());
-        ws.head.download(head, 2);
-        sync_stream();
-        if (head[1] != 0.0) fail("%s", FC_ILL_DEFINED);
-    }
-    double lower = -std::numeric_limits<double>::infinity();
-    out.converged = 0;
-    int it = 1;
-    for (; it <= p.max_iter; it++) {
-        const double prev = lower;
-        hipLaunchKernelGGL(fe_logprob_kernel, dim3((unsigned)((n + FE_FB - 1) / FE_FB), K), dim3(256), lds_lp, st, a);
-        hipLaunchKernelGGL(fe_lse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(fe_bound_kernel, dim3(1), dim3(256), 0, st, a);
-        mstep(0);
-        SR_HIP(hipGetLastError());
-        ws.head.download(head, 2);
-        sync_stream();
-        if (head[1] != 0.0) fail("%s", FC_ILL_DEFINED);
-        lower = head[0];
-        if (std::fabs(lower - prev) < p.tol) {
-            out.converged = 1;
-            break;
-        }
-    }
-    out.n_iter = std::min(it, p.max_iter);
-    out.lower_bound = lower;
-    g.weights.resize(K);
-    g.means.resize((size_t)K * D);
-    g.prec_chol.resize((size_t)K * D * D);
-    g.covariances.resize((size_t)K * D * D);
-    ws.w.download(g.weights.data(), K);
-    ws.mu.download(g.means.data(), (size_t)K * D);
-    ws.prec.download(g.prec_chol.data(), (size_t)K * D * D);
-    ws.cov.download(g.covariances.data(), (size_t)K * D * D);
-    sync_stream();
-    g.trained = true;
-}
-
-void set_full_fit_batch_bytes(long bytes) { g_fit_batch_bytes.store(bytes); }
-long full_fit_batch_bytes() { return g_fit_batch_bytes.load(); }
-
-void full_fit_batch_stats(long *calls, long *speakers, long *iterations) {
-    if (calls) *calls = g_fit_batch_calls.load();
-    if (speakers) *speakers = g_fit_batch_speakers.load();
-    if (iterations) *iterations = g_fit_batch_iterations.load();
-}
-
-namespace {
-
-// speakers [s0, s1) of a batch: one set of launches per EM iteration, one download of the S records behind it
-void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
+// The EM driver.  Speakers [s0, s1) of `models`: one set of launches per EM iteration, one download of the S records behind it.
+// status[s]: 0 fitted, -1 failed (messages[s] says why; the handle keeps its parameters).  -> the iterations launched
+long fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
                   SRFullFitStats *out, int *status, std::vector<std::string> &messages) {
-    const int S = s1 - s0, K = models[s0]->K, npairs = D * (D + 1) / 2;
+    const int S = s1 - s0, K = models[s0]->K;
     const long r0 = (long)row_offsets[s0], rows = (long)row_offsets[s1] - r0;
     auto &ws = per_device<FeBatchWorkspace>();
     std::vector<FeSpk> spk((size_t)S);
@@ -724,10 +621,10 @@ void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, con
         FeSpk &t = spk[i];
         t.row0 = (long)row_offsets[s0 + i] - r0;
         t.n = n;
-        t.n_chunks = (int)std::min<long>(32, (n + 255) / 256);         // (fullgmm_fit's chunking)
+        t.n_chunks = fe_n_chunks(n);
         t.chunk = (int)((n + t.n_chunks - 1) / t.n_chunks);
         t.o_partial = o_partial;
-        o_partial += (long)t.n_chunks * K * npairs;
+        o_partial += (long)fe_partial_len(n, K, D);
         t.reg = p.reg_covar;
         t.tol = p.tol;
         t.prev = -std::numeric_limits<double>::infinity();
@@ -738,8 +635,8 @@ void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, con
         rec[i] = FeRec{t.prev, FE_ACTIVE, 0};
         max_iter = std::max(max_iter, p.max_iter);
         (p.init_given ? any_given : any_kmeans) = true;
-        for (long b = 0; b < (n + FE_FB - 1) / FE_FB; b++) wl_lp.push_back(make_int2(i, (int)b));
-        for (long b = 0; b < (n + 255) / 256; b++) wl_lse.push_back(make_int2(i, (int)b));
+        for (long b = 0; b < fe_lp_blocks(n); b++) wl_lp.push_back(make_int2(i, (int)b));
+        for (long b = 0; b < fe_lse_blocks(n); b++) wl_lse.push_back(make_int2(i, (int)b));
         for (int c = 0; c < t.n_chunks; c++) wl_cov.push_back(make_int2(i, c));
     }
     const size_t SK = (size_t)S * K;
@@ -830,6 +727,7 @@ void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, con
         active = false;
         for (int i = 0; i < S; i++) active = active || ws.h_rec.p[i].state == FE_ACTIVE;
     }
+    long iterations = 0;
     for (int it = 1; active && it <= max_iter; it++) {
         hipLaunchKernelGGL(fe_logprob_batch_kernel, dim3(n_lp, K), dim3(256), lds_lp, st, b);
         hipLaunchKernelGGL(fe_lse_batch_kernel, dim3(n_lse), dim3(256), 0, st, b);
@@ -837,7 +735,7 @@ void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, con
         mstep(0);
         hipLaunchKernelGGL(fe_stop_batch_kernel, dim3(gs), dim3(64), 0, st, b, it);
         read_records();
-        g_fit_batch_iterations++;
+        iterations++;
         active = false;
         for (int i = 0; i < S; i++) active = active || ws.h_rec.p[i].state == FE_ACTIVE;
     }
@@ -865,9 +763,31 @@ void fe_fit_group(SRFullGMM *const *models, int s0, int s1, const double *X, con
         g.covariances.assign(cov.begin() + (size_t)i * K * D * D, cov.begin() + (size_t)(i + 1) * K * D * D);
         g.trained = true;
     }
+    return iterations;
 }
 
 }  // namespace
+
+// a group of one.  Not a fullgmm_fit_batch of one: no "speaker 0: " in a message, no counter moves, and no option cuts or refuses it
+void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out) {
+    fe_check_args(g, X, n, D, p, "");
+    ensure_device();
+    SRFullGMM *const model = &g;
+    const int64_t row_offsets[2] = {0, n};
+    int status = 0;
+    std::vector<std::string> message(1);
+    fe_fit_group(&model, 0, 1, X, row_offsets, D, &p, &out, &status, message);
+    if (status != 0) fail("%s", message[0].c_str());
+}
+
+void set_full_fit_batch_bytes(long bytes) { g_fit_batch_bytes.store(bytes); }
+long full_fit_batch_bytes() { return g_fit_batch_bytes.load(); }
+
+void full_fit_batch_stats(long *calls, long *speakers, long *iterations) {
+    if (calls) *calls = g_fit_batch_calls.load();
+    if (speakers) *speakers = g_fit_batch_speakers.load();
+    if (iterations) *iterations = g_fit_batch_iterations.load();
+}
 
 void fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const int64_t *row_offsets, int D, const SRFullFitParams *params,
                        SRFullFitStats *out, int *status, std::vector<std::string> &messages) {
@@ -900,23 +820,17 @@ void fullgmm_fit_batch(SRFullGMM *const *models, int S, const double *X, const i
     // groups of speakers, in batch order, whose workspace stays under full_fit_batch_bytes (a speaker larger than that is a group
     // of its own); a speaker's fit does not depend on its group
     const long limit = g_fit_batch_bytes.load();
-    const size_t npairs = (size_t)D * (D + 1) / 2;
     int s0 = 0;
     while (s0 < S) {
         size_t bytes = 0;
         int s1 = s0;
         while (s1 < S && s1 - s0 < 65535) {
-            const size_t n = (size_t)(row_offsets[s1 + 1] - row_offsets[s1]), chunks = std::min<size_t>(32, (n + 255) / 256);
-            // everything FeBatchWorkspace holds for the speaker: X, lp, lpn, partial, the parameters, head; the three work lists,
-            // the k-means labels, its table entry and record
-            const size_t need = sizeof(double) * (n * D + n * K + n + chunks * K * npairs + (size_t)K * (2 * D * D + D + 4) + 2) +
-                                sizeof(int2) * ((n + FE_FB - 1) / FE_FB + (n + 255) / 256 + chunks) + sizeof(int) * n + sizeof(FeSpk) +
-                                sizeof(FeRec);
+            const size_t need = fe_spk_bytes((long)(row_offsets[s1 + 1] - row_offsets[s1]), K, D);
             if (s1 > s0 && bytes + need > (size_t)limit) break;
             bytes += need;
             s1++;
         }
-        fe_fit_group(models, s0, s1, X, row_offsets, D, params, out, status, messages);
+        g_fit_batch_iterations += fe_fit_group(models, s0, s1, X, row_offsets, D, params, out, status, messages);
         s0 = s1;
     }
 }

@@ -36,6 +36,9 @@ struct SRFullSet {
 
 namespace sr {
 constexpr int FULL_MAX_D = 64;
+// Both fits run gmm_full.hip's one EM driver, in which a speaker's bits do not depend on the speakers fitted with it.
+// One model, a group of one: a failed fit throws and leaves the handle untouched; it moves none of full_fit_batch_stats' counters
+// and full_fit_batch_bytes does not bear on it.
 void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out);
 // S models of one K and D in one set of launches per EM iteration (the stop rule per speaker, on the device); every fitted
 // speaker gets the bits fullgmm_fit gives it alone.  status[s]: 0 fitted, -1 failed (messages[s] says why; the handle is untouched).

@@ -159,47 +159,23 @@ class GMM(object):
         K = self.n_components
         if n < K:
             raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, n))
-        init = self.weights_init is not None
-        if init:
-            w = np.ascontiguousarray(self.weights_init, dtype=np.float64)
-            mu = np.ascontiguousarray(self.means_init, dtype=np.float64)
-            if w.shape != (K,) or mu.shape != (K, D):
-                raise ValueError("weights_init must be [%d], means_init [%d, %d]" % (K, K, D))
-            prec = np.asarray(self.precisions_init, dtype=np.float64)
-            if prec.shape != (K, D, D):
-                raise ValueError("precisions_init must be [%d, %d, %d]" % (K, D, D))
-            P = np.ascontiguousarray(_precision_cholesky_from_precisions(prec))
-            h = lib().sr_fullgmm_create(K, D, _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(P))
-        else:
-            h = lib().sr_fullgmm_create(K, D, None, None, None)
-        if not h:
-            _raise_lib("sr_fullgmm_create")
-        h = C.c_void_p(h)
+        h, init = self._new_handle(D)
         try:
             seed = DEFAULT_SEED if self.random_state is None else int(self.random_state)
             prm = _lib.FullFitParams(self.tol, self.reg_covar, self.max_iter, 1 if init else 0, seed)
             st = _lib.FullFitStats()
             if lib().sr_fullgmm_fit(h, _lib.as_dp(X), n, D, C.byref(prm), C.byref(st)) < 0:
                 _raise_lib("sr_fullgmm_fit")
-            w, mu = np.empty(K), np.empty((K, D))
-            cov, P = np.empty((K, D, D)), np.empty((K, D, D))
-            _lib.check(lib().sr_fullgmm_get(h, _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(cov), _lib.as_dp(P)), "sr_fullgmm_get")
+            fitted = self._read_handle(h, D)
         except BaseException:
             lib().sr_fullgmm_free(h)
             raise
-        self._free()
-        self._h = h
-        self._set_params(w, mu, cov, P)
-        self.converged_, self.n_iter_, self.lower_bound_ = bool(st.converged), int(st.n_iter), float(st.lower_bound)
-        if not self.converged_:
-            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase "
-                          "max_iter, tol, or check for degenerate data.", ConvergenceWarning)
+        self._adopt(h, fitted, st)
         return self
 
     def _new_handle(self, D):
         """A fresh device-side model for a fit on D columns: the explicit initialisation when one was given, else no parameters.
-        -> (handle, init_given).  This restates the first half of ``fit``, which keeps its own copy so that the single fit stays
-        as it was: a change to either belongs in both."""
+        -> (handle, init_given)"""
         K = self.n_components
         init = self.weights_init is not None
         if init:
@@ -217,6 +193,24 @@ class GMM(object):
         if not h:
             _raise_lib("sr_fullgmm_create")
         return C.c_void_p(h), init
+
+    def _read_handle(self, h, D):
+        """-> (weights, means, covariances, precisions_cholesky) of the fitted handle ``h`` (``sr_fullgmm_get``)"""
+        K = self.n_components
+        w, mu = np.empty(K), np.empty((K, D))
+        cov, P = np.empty((K, D, D)), np.empty((K, D, D))
+        _lib.check(lib().sr_fullgmm_get(h, _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(cov), _lib.as_dp(P)), "sr_fullgmm_get")
+        return w, mu, cov, P
+
+    def _adopt(self, h, fitted, st):
+        """Become the fitted model: the handle ``h``, its parameters as ``_read_handle`` gave them, the fit's ``FullFitStats``."""
+        self._free()
+        self._h = h
+        self._set_params(*fitted)
+        self.converged_, self.n_iter_, self.lower_bound_ = bool(st.converged), int(st.n_iter), float(st.lower_bound)
+        if not self.converged_:
+            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase "
+                          "max_iter, tol, or check for degenerate data.", ConvergenceWarning)
 
     # ---- scoring ----
     def score_samples(self, X) -> np.ndarray:
@@ -304,10 +298,7 @@ def fit_many(gmms, Xs):
             if status[s] != 0:
                 errors[s] = ValueError(lib().sr_fullgmm_fit_batch_error(s).decode("utf-8", "replace"))
                 continue
-            w, mu = np.empty(K), np.empty((K, D))
-            cov, P = np.empty((K, D, D)), np.empty((K, D, D))
-            _lib.check(lib().sr_fullgmm_get(handles[s], _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(cov), _lib.as_dp(P)), "sr_fullgmm_get")
-            fitted[s] = (w, mu, cov, P)
+            fitted[s] = gmms[s]._read_handle(handles[s], D)
     except BaseException:
         for h in handles:
             lib().sr_fullgmm_free(h)
@@ -316,13 +307,7 @@ def fit_many(gmms, Xs):
         if fitted[s] is None:
             lib().sr_fullgmm_free(handles[s])
             continue
-        g._free()
-        g._h = handles[s]
-        g._set_params(*fitted[s])
-        g.converged_, g.n_iter_, g.lower_bound_ = bool(st[s].converged), int(st[s].n_iter), float(st[s].lower_bound)
-        if not g.converged_:
-            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase "
-                          "max_iter, tol, or check for degenerate data.", ConvergenceWarning)
+        g._adopt(handles[s], fitted[s], st[s])
     return errors
 
 

@@ -1,6 +1,9 @@
-"""Batched full-covariance fits on the MI355X (sr_fullgmm_fit_batch, skgmm.fit_many, ModelInterface.train; csrc/gmm_full.hip).
-The contract is bit identity with the single fit: every comparison against ``skgmm.GMM.fit`` below is ``np.array_equal`` / ``==``,
-without a tolerance."""
+"""Full-covariance fits on the MI355X, single and batched (sr_fullgmm_fit, sr_fullgmm_fit_batch, skgmm.fit_many,
+ModelInterface.train; csrc/gmm_full.hip).  Both run the one EM driver: ``skgmm.GMM.fit`` is a group of one, a batch is cut into
+groups of S.  The contract is that a speaker's bits do not depend on its group: every comparison of a group of one
+(``skgmm.GMM.fit``) against a group of S below is ``np.array_equal`` / ``==``, without a tolerance.  The scikit-learn goldens of
+the group of one are test_gpu_full_cov.py's."""
+import ctypes as C
 import os
 import warnings
 
@@ -301,3 +304,109 @@ def test_model_interface_failure_leaves_the_earlier_labels():
         m.train()
     assert m.gmmset.y == ["a", "bad"] and len(m.gmmset.gmms) == 1
     _same(_fit_single(dict(n_components=2, reg_covar=0.0), np.asarray(m.features["a"])), m.gmmset.gmms[0], None, "a")
+
+
+# ---- the single fit as a group of one: what it must not share with a batch (counters, the option, message prefixes), and the one
+# workspace it does share
+def test_a_single_fit_moves_no_batch_counter():
+    from speaker_recognition_amd import _lib
+    rng = np.random.default_rng(37)
+    X, init = _explicit_case(rng, 2, 5, 300)
+    before = _lib.full_fit_batch_stats()
+    for kw in (dict(n_components=2, random_state=1), dict(n_components=2, **init)):
+        m = _fit_single(kw, X)
+        assert not isinstance(m, Exception) and m.n_iter_ >= 1
+    assert _lib.full_fit_batch_stats() == before
+
+
+def _raw_fit(h, X, reg_covar, init_given):
+    """sr_fullgmm_fit on a handle -> (return value, sr_last_error())"""
+    from speaker_recognition_amd import _lib
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    prm, st = _lib.FullFitParams(1e-3, reg_covar, 100, init_given, 0), _lib.FullFitStats()
+    rc = _lib.lib().sr_fullgmm_fit(h, _lib.as_dp(X), X.shape[0], X.shape[1], C.byref(prm), C.byref(st))
+    return rc, _lib.last_error()
+
+
+def test_single_fit_failing_at_the_kmeans_start_says_so_without_a_speaker_prefix():
+    from speaker_recognition_amd import _lib, skgmm
+    rng = np.random.default_rng(41)
+    X = _two_points(rng, 5)
+    h = C.c_void_p(_lib.lib().sr_fullgmm_create(2, 5, None, None, None))
+    assert h
+    try:
+        rc, msg = _raw_fit(h, X, 0.0, 0)
+        assert rc == -1 and msg.startswith(skgmm._ILL_DEFINED) and "ill-defined empirical covariance" in msg, msg
+        assert "speaker" not in msg, msg
+        assert _lib.lib().sr_fullgmm_info(h, None, None) == 0                # still without parameters
+        rc, msg = _raw_fit(h, fo.draw(rng, fo.random_model(rng, 2, 5), 200), 1e-6, 0)        # the device goes on
+        assert rc == 0 and _lib.lib().sr_fullgmm_info(h, None, None) == 1, msg
+    finally:
+        _lib.lib().sr_fullgmm_free(h)
+
+
+def test_single_fit_failing_from_an_explicit_start_leaves_the_handle_as_given(g):
+    from speaker_recognition_amd import _lib, skgmm
+    X = np.ascontiguousarray(g["collapsed_X"], dtype=np.float64)
+    Dc = X.shape[1]
+    w0 = np.ascontiguousarray(g["collapsed_w0"], dtype=np.float64)
+    mu0 = np.ascontiguousarray(g["collapsed_mu0"], dtype=np.float64)
+    P0 = np.ascontiguousarray(skgmm._precision_cholesky_from_precisions(g["collapsed_prec0"]))
+
+    def get():
+        w, mu, cov, P = np.empty(2), np.empty((2, Dc)), np.empty((2, Dc, Dc)), np.empty((2, Dc, Dc))
+        assert _lib.lib().sr_fullgmm_get(h, _lib.as_dp(w), _lib.as_dp(mu), _lib.as_dp(cov), _lib.as_dp(P)) == 0
+        return w, mu, cov, P
+
+    h = C.c_void_p(_lib.lib().sr_fullgmm_create(2, Dc, _lib.as_dp(w0), _lib.as_dp(mu0), _lib.as_dp(P0)))
+    assert h
+    try:
+        rc, msg = _raw_fit(h, X, 0.0, 1)
+        assert rc == -1 and msg.startswith(skgmm._ILL_DEFINED) and "speaker" not in msg, msg
+        w, mu, cov, P = get()
+        assert np.array_equal(w, w0) and np.array_equal(mu, mu0) and np.array_equal(P, P0)
+        assert not cov.any()                                                 # (a handle built from arrays has no covariances)
+        rc, msg = _raw_fit(h, X, 1e-6, 1)                                    # the device goes on: the same start, regularised
+        assert rc == 0, msg
+        assert all(np.all(np.isfinite(a)) for a in get()) and get()[2].any()
+    finally:
+        _lib.lib().sr_fullgmm_free(h)
+
+
+def _mixed_sizes():
+    """K 8 x D 13 speakers of 600, 64, 2000 and 257 frames (3, 1, 8 and 2 covariance chunks), the first four of
+    test_group_cuts_do_not_show -> (kwargs, data)"""
+    rng = np.random.default_rng(17)
+    Xs = [fo.draw(rng, fo.random_model(rng, 4, 13), n) for n in (600, 64, 2000, 257)]
+    return [dict(n_components=8, random_state=s, max_iter=40 + s) for s in range(4)], Xs
+
+
+def test_the_group_bound_does_not_bear_on_a_single_fit():
+    from speaker_recognition_amd import _lib
+    kws, Xs = _mixed_sizes()
+    at_default = _fit_single(kws[0], Xs[0])
+    default = _lib.full_fit_batch_bytes()
+    try:
+        _lib.set_option("full_fit_batch_bytes", 1)             # far below the speaker's own workspace
+        at_one = _fit_single(kws[0], Xs[0])
+    finally:
+        _lib.set_option("full_fit_batch_bytes", default)
+    assert not isinstance(at_default, Exception)
+    _same(at_default, at_one, None, "full_fit_batch_bytes = 1")
+    _same(at_default, _fit_single(kws[0], Xs[0]), None, "restored")
+
+
+def test_single_fits_and_a_batch_alternate_on_the_one_workspace():
+    """600 frames alone, then {64, 2000} as a batch, then 257 alone: every call leaves longer tables and work lists behind than
+    the next one writes.  Each result is the speaker's fit in another sequence (alone, shortest first)."""
+    kws, Xs = _mixed_sizes()
+    alone = [_fit_single(kws[s], Xs[s]) for s in (1, 3, 0, 2)]
+    alone = dict(zip((1, 3, 0, 2), alone))
+    assert not any(isinstance(m, Exception) for m in alone.values())
+    first = _fit_single(kws[0], Xs[0])
+    gm, errors = _fit_batch(kws[1:3], Xs[1:3])
+    last = _fit_single(kws[3], Xs[3])
+    _same(alone[0], first, None, 600)
+    _same(alone[1], gm[0], errors[0], 64)
+    _same(alone[2], gm[1], errors[1], 2000)
+    _same(alone[3], last, None, 257)
