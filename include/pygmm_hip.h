@@ -419,6 +419,41 @@ SRStream *sr_stream_create_vad(SRMfcc *m, SRModelSet *set, SRFullSet *fullset, i
                                int ltsd_window, int order, const float *noise_amp, double lambda0, double lambda1);
 int sr_stream_collect_vad(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms);
 
+/* ---- Open-set decision against a background model (csrc/open_set.hip): the reference's GMMSet.predict_one_with_rejection
+ * (src/testbench/gmmset.py:69-81) taken on the device.  The set carries the UBM as one of its columns, `bg` (GMMSet packs it
+ * as column 0).  For an utterance of n frames, in float64 and in the reference's order: q[s] = sums[s] / n for every s != bg;
+ * best = the first maximum of q (the quotients are compared, the lowest index wins among equals); margin = q[best] - sums[bg] / n;
+ * label = best unless margin < threshold, then -1 (the reference's None).  An utterance without frames, or a set without a column
+ * besides bg: label -1, margin NaN.  NaN sums go as the reference's max() takes them: a NaN in the first column besides bg is
+ * never replaced and is accepted with margin NaN, a NaN elsewhere never wins.  The kernel runs on FINAL sums: behind the
+ * pass's finalize and, for utterances with frames in the partial-product band (SR_CLAMP_COMPAT), again behind their patch.
+ * Every call checks its arguments before it touches the device: bg inside [0, S), a threshold that is not a NaN, label_out and
+ * margin_out both given (sums_out may be NULL).  Diagonal sets only: a full-covariance set has no UBM (the reference's skgmm.GMMSet
+ * has no rejection).  In a process forked after GPU initialisation the calls fail.
+ * sr_open_set_decide: the rule on sums in host memory ([U][S], n_frames [U] >= 0) -- upload, kernel, one copy back: for callers
+ * that hold sums of several passes, and the direct test of the kernel.
+ * sr_score_batch_set_open / sr_predict_pcm_batch_open: the passes of sr_score_batch_set / sr_predict_pcm_batch with the decision
+ * kernel behind them; labels and margins come back with the sums, in the same single host wait (results always travel by copy).
+ * sr_stream_set_open: before the first sr_stream_submit of a diagonal session (plain, SR_STREAM_GRAPH or voice-activity); from then
+ * on every tick enqueues the decision behind its finalize -- a captured tick contains it; a voice-activity session takes the frame
+ * counts from its device-side table, and a window it does not score gets -1 / NaN.  Rule and threshold are fixed for the session's
+ * life: the call fails once a tick was submitted (a new threshold is a new session), so no captured tick ever goes stale.
+ * sr_stream_collect_open: sr_stream_collect_vad with label_out / margin_out [n_windows] in place of the argmax (voiced_out: NULL,
+ * or [n_windows] on a voice-activity session); sr_stream_collect / _vad keep working on such a session and return the closed-set
+ * argmax.
+ * sr_multi_predict_pcm_open: sr_multi_predict_pcm's partition and pieces; every slot decides its utterances on its own device. */
+int sr_open_set_decide(const double *sums /* [U][S] */, int U, int S, int bg, const int64_t *n_frames /* [U] */, double threshold,
+                       int *label_out /* [U] */, double *margin_out /* [U] */);
+int sr_score_batch_set_open(SRModelSet *set, SRBatch *features, int bg, double threshold, double *sums_out, int *label_out,
+                            double *margin_out, int flags);
+int sr_predict_pcm_batch_open(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int bg, double threshold, double *sums_out,
+                              int *label_out, double *margin_out, int flags);
+int sr_stream_set_open(SRStream *s, int bg, double threshold);
+int sr_stream_collect_open(SRStream *s, double *sums_out, int *label_out, double *margin_out, int *voiced_out, double *device_ms);
+int sr_multi_predict_pcm_open(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt, int nd, int bg,
+                              double threshold, double *sums_out, int *label_out, double *margin_out, double *slot_seconds_out,
+                              int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_PYGMM_LIB points at another build of the same library (A/B timing of kernel variants)
+# (SR_PYGMM_ALLOW_MISSING: comma-separated calls such a build may lack, e.g. the parent commit's; any other missing call fails the load)
 LIB_PATH = os.environ.get("SR_PYGMM_LIB") or os.path.join(_HERE, "lib", "pygmm.so")
 
 LEGACY_SYMBOLS = ["new_gmm", "load", "dump", "train_model", "train_model_from_ubm", "score_all",
@@ -36,6 +37,8 @@ EXT_SYMBOLS = [
     "sr_fullset_score_batch", "sr_fullset_free", "sr_fullset_predict_pcm_batch", "sr_stream_create_full", "sr_multi_create_full",
     "sr_stream_create_vad", "sr_stream_collect_vad",
     "sr_fullgmm_fit_batch", "sr_fullgmm_fit_batch_error", "sr_full_fit_batch_stats", "sr_full_fit_batch_bytes",
+    "sr_open_set_decide", "sr_score_batch_set_open", "sr_predict_pcm_batch_open", "sr_stream_set_open", "sr_stream_collect_open",
+    "sr_multi_predict_pcm_open",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -184,9 +187,23 @@ def lib():
         "sr_multi_create_full": (vp, [C.POINTER(vp), i32, dbl, dbl, dbl, i32, i32, i32, dbl, i32, i32]),
         "sr_stream_create_vad": (vp, [vp, vp, vp, i32, i64, i32, i32, i32, i32, fp, dbl, dbl]),
         "sr_stream_collect_vad": (i32, [vp, dp, C.POINTER(i32), C.POINTER(i32), dp]),
+        "sr_open_set_decide": (i32, [dp, i32, i32, i32, C.POINTER(i64), dbl, C.POINTER(i32), dp]),
+        "sr_score_batch_set_open": (i32, [vp, vp, i32, dbl, dp, C.POINTER(i32), dp, i32]),
+        "sr_predict_pcm_batch_open": (i32, [vp, vp, vp, i32, i32, dbl, dp, C.POINTER(i32), dp, i32]),
+        "sr_stream_set_open": (i32, [vp, i32, dbl]),
+        "sr_stream_collect_open": (i32, [vp, dp, C.POINTER(i32), dp, C.POINTER(i32), dp]),
+        "sr_multi_predict_pcm_open": (i32, [vp, C.POINTER(C.c_int16), C.POINTER(i64), i32, i32, i32, dbl, dp, C.POINTER(i32), dp, dp,
+                                            i32]),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None:
+            # another build loaded for an A/B run (SR_PYGMM_LIB) may predate a call: SR_PYGMM_ALLOW_MISSING names, comma-separated,
+            # the calls the run does without (using one there raises AttributeError); any other missing call is a stale build
+            if os.environ.get("SR_PYGMM_LIB") and name in os.environ.get("SR_PYGMM_ALLOW_MISSING", "").split(","):
+                continue
+            raise SRError("%s does not export %s: rebuild it (an older build loaded through SR_PYGMM_LIB on purpose: name the "
+                          "calls it lacks in SR_PYGMM_ALLOW_MISSING)" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
     _lib = L

@@ -2,6 +2,7 @@
 
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/ ./person*" -m model.out
     speaker-recognition.py -t predict -i "./*.wav" -m model.out
+    speaker-recognition.py -t predict -i "./*.wav" -m model.out --reject-threshold 0.5
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --covariance full
 
 Wav files in each input directory are labelled with the directory's basename; wildcard inputs
@@ -47,6 +48,9 @@ def get_args(argv=None):
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--gpus", type=int, default=1,
                         help="predict: shard the input files over this many GPUs from one process (0 = all visible)")
+    parser.add_argument("--reject-threshold", type=float, default=None,
+                        help="predict: open-set decision -- print None for a file whose best speaker's per-frame margin over the "
+                             "UBM is below this (only for a model enrolled from a UBM)")
     return parser.parse_args(argv)
 
 
@@ -81,10 +85,25 @@ def task_enroll(input_dirs, output_model, args=None):
     m.dump(output_model)
 
 
-def task_predict(input_files, input_model, gpus=1):
+def task_predict(input_files, input_model, gpus=1, reject_threshold=None):
     m = ModelInterface.load(input_model)
     out = []
     files = sorted(glob.glob(os.path.expanduser(input_files)))
+    if reject_threshold is not None:
+        try:
+            m._check_reject()
+        except ValueError as e:
+            print("--reject-threshold: %s" % e)
+            sys.exit(2)
+        if gpus != 1:
+            print("--reject-threshold: the open-set decision of a file list runs on one GPU (--gpus 1)")
+            sys.exit(2)
+        # every file in one batch, decided on the device (interface.predict_many_with_reject)
+        labels = m.predict_many_with_reject([read_wav(f) for f in files], reject_threshold)
+        for f, label in zip(files, labels):
+            print(f, "->", label)
+            out.append((f, label))
+        return out
     if gpus != 1:
         # every file in one utterance-sharded pass over the node's GPUs (interface.predict_many)
         labels = m.predict_many([read_wav(f) for f in files], gpus=gpus)
@@ -122,7 +141,7 @@ def main(argv=None):
     if args.task == "enroll":
         task_enroll(args.input, args.model, args)
     elif args.task == "predict":
-        task_predict(args.input, args.model, args.gpus)
+        task_predict(args.input, args.model, args.gpus, args.reject_threshold)
     else:
         print('task must be "enroll" or "predict"')
         sys.exit(2)

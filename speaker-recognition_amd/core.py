@@ -159,6 +159,20 @@ class ModelSet:
               "sr_score_batch_set")
         return (sums, arg, fll) if frame_ll else (sums, arg)
 
+    def score_open(self, feats: Batch, bg: int, threshold: float, clamp_compat: bool = True):
+        """The same pass with the open-set decision taken on the device (sr_score_batch_set_open): column ``bg`` is the
+        background model (the UBM); -> (sums[U, S] float64, labels[U] int32, margins[U] float64).  A label is the first maximum
+        of sums / frames over the other columns, or -1 when its margin over the background's sums / frames is below
+        ``threshold`` (gmmset.py:69-81); an utterance without frames has label -1 and margin NaN."""
+        U, S = feats.n_utt, len(self)
+        sums = np.zeros((U, S), dtype=np.float64)
+        labels = np.full(U, -1, dtype=np.int32)
+        margins = np.full(U, np.nan, dtype=np.float64)
+        check(lib().sr_score_batch_set_open(self._h, feats._h, int(bg), float(threshold), _lib.as_dp(sums), _lib.as_i32p(labels),
+                                            _lib.as_dp(margins), _lib.SR_CLAMP_COMPAT if clamp_compat else 0),
+              "sr_score_batch_set_open")
+        return sums, labels, margins
+
     def __del__(self):
         try:
             if self._h:
@@ -232,6 +246,18 @@ class MfccExtractor:
               "sr_predict_pcm_batch")
         return sums, arg
 
+    def predict_batch_open(self, models: ModelSet, pcm: Batch, bg: int, threshold: float, nd: int = 0, clamp_compat: bool = True):
+        """``predict_batch`` with the open-set decision of ``ModelSet.score_open`` (sr_predict_pcm_batch_open):
+        -> (sums[U, S], labels[U] int32, margins[U] float64)."""
+        U, S = pcm.n_utt, len(models)
+        sums = np.zeros((U, S), dtype=np.float64)
+        labels = np.full(U, -1, dtype=np.int32)
+        margins = np.full(U, np.nan, dtype=np.float64)
+        check(lib().sr_predict_pcm_batch_open(self._h, models._h, pcm._h, int(nd), int(bg), float(threshold), _lib.as_dp(sums),
+                                              _lib.as_i32p(labels), _lib.as_dp(margins),
+                                              _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_predict_pcm_batch_open")
+        return sums, labels, margins
+
     def __del__(self):
         try:
             if self._h:
@@ -239,6 +265,23 @@ class MfccExtractor:
                 self._h = None
         except Exception:
             pass
+
+
+def open_set_decide(sums, n_frames, bg: int, threshold: float):
+    """The open-set rule on sums the caller holds (sr_open_set_decide): ``sums`` [U, S] float64, ``n_frames`` [U];
+    -> (labels[U] int32, margins[U] float64), as ``ModelSet.score_open`` gives them."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.ndim != 2:
+        raise ValueError("expected [utterances, models] sums, got shape %r" % (sums.shape,))
+    n = np.ascontiguousarray(n_frames, dtype=np.int64)
+    U, S = sums.shape
+    if n.shape != (U,):
+        raise ValueError("expected %d frame counts, got shape %r" % (U, n.shape))
+    labels = np.full(U, -1, dtype=np.int32)
+    margins = np.full(U, np.nan, dtype=np.float64)
+    check(lib().sr_open_set_decide(_lib.as_dp(sums), U, S, int(bg), _lib.as_i64p(n), float(threshold), _lib.as_i32p(labels),
+                                   _lib.as_dp(margins)), "sr_open_set_decide")
+    return labels, margins
 
 
 def vad_thresholds(lambda0, lambda1):
@@ -262,10 +305,13 @@ class ServingStream:
     voice-activity front end in front of every window, on the device (sr_stream_create_vad): a window is scored on its voiced
     samples alone, as ``ModelInterface.filter`` + the fused call would score it, and only if more than a third of it is voiced --
     otherwise its sums are 0 and its argmax -1.  ``collect`` returns what it always did; the voiced sample counts of the tick
-    collected last are in ``last_voiced`` (``collect_vad`` returns them as a fourth value).  ``nd`` must be 0 then."""
+    collected last are in ``last_voiced`` (``collect_vad`` returns them as a fourth value).  ``nd`` must be 0 then.
+    ``open_set=(bg, threshold)`` (a diagonal ``ModelSet`` whose column ``bg`` is the UBM): every tick also takes the open-set
+    decision of ``ModelSet.score_open`` on the device (sr_stream_set_open); ``collect_open`` returns it.  The pair is fixed for
+    the session's life."""
 
     def __init__(self, extractor: MfccExtractor, models, n_windows: int, window_samples: int,
-                 nd: int = 0, clamp_compat: bool = True, graph: bool = False, vad=None):
+                 nd: int = 0, clamp_compat: bool = True, graph: bool = False, vad=None, open_set=None):
         from .skgmm import FullSet
         self._keep = (extractor, models)
         self.n_windows, self.window_samples, self.n_models = int(n_windows), int(window_samples), len(models)
@@ -299,6 +345,11 @@ class ServingStream:
         if not h:
             raise SRError("%s failed: %s" % (what, _lib.last_error()))
         self._h = C.c_void_p(h)
+        self.open_set = None
+        if open_set is not None:
+            bg, threshold = open_set
+            check(lib().sr_stream_set_open(self._h, int(bg), float(threshold)), "sr_stream_set_open")
+            self.open_set = (int(bg), float(threshold))
 
     def submit(self, pcm) -> None:
         a = np.ascontiguousarray(pcm, dtype=np.int16)
@@ -325,6 +376,20 @@ class ServingStream:
             raise SRError("not a voice-activity session: create the stream with vad=")
         sums, arg, ms = self.collect()
         return sums, arg, self.last_voiced, ms
+
+    def collect_open(self):
+        """The oldest tick of a session with ``open_set=``: (sums, labels int32, margins float64, device ms).  A window a
+        voice-activity session did not score has label -1 and margin NaN; its voiced counts are in ``last_voiced``."""
+        sums = np.empty((self.n_windows, self.n_models), dtype=np.float64)
+        labels = np.empty(self.n_windows, dtype=np.int32)
+        margins = np.empty(self.n_windows, dtype=np.float64)
+        voiced = np.empty(self.n_windows, dtype=np.int32) if self.vad else None
+        ms = C.c_double(0)
+        check(lib().sr_stream_collect_open(self._h, _lib.as_dp(sums), _lib.as_i32p(labels), _lib.as_dp(margins),
+                                           _lib.as_i32p(voiced) if self.vad else None, C.byref(ms)), "sr_stream_collect_open")
+        if self.vad:
+            self.last_voiced = voiced
+        return sums, labels, margins, ms.value
 
     def __del__(self):
         try:
@@ -402,6 +467,25 @@ class MultiPredictor:
                                          _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_multi_predict_pcm")
         self.slot_seconds = secs
         return sums, arg
+
+    def predict_open(self, signals, bg, threshold, nd=0, clamp_compat=True):
+        """``predict`` with the open-set decision of ``ModelSet.score_open``, every slot deciding its utterances on its own
+        device (sr_multi_predict_pcm_open).  -> (sums[U, S], labels[U] int32, margins[U] float64)."""
+        sigs = [np.ascontiguousarray(s, dtype=np.int16) for s in signals]
+        offsets = np.zeros(len(sigs) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([len(s) for s in sigs])
+        cat = np.ascontiguousarray(np.concatenate(sigs)) if sigs else np.zeros(0, np.int16)
+        U = len(sigs)
+        sums = np.zeros((U, self.n_models), dtype=np.float64)
+        labels = np.full(U, -1, dtype=np.int32)
+        margins = np.full(U, np.nan, dtype=np.float64)
+        secs = np.zeros(self.n_slots, dtype=np.float64)
+        check(lib().sr_multi_predict_pcm_open(self._h, cat.ctypes.data_as(C.POINTER(C.c_int16)), _lib.as_i64p(offsets), U, int(nd),
+                                              int(bg), float(threshold), _lib.as_dp(sums), _lib.as_i32p(labels), _lib.as_dp(margins),
+                                              _lib.as_dp(secs), _lib.SR_CLAMP_COMPAT if clamp_compat else 0),
+              "sr_multi_predict_pcm_open")
+        self.slot_seconds = secs
+        return sums, labels, margins
 
     def __del__(self):
         try:

@@ -701,9 +701,13 @@ SRBatch *sr_mfcc_extract_batch(SRMfcc *m, SRBatch *pcm, int nd, int cmvn) {
 // from 20 to 271 ms and the scoring chunks pay their tails, profiles/r02_overlap.txt -- and its second stream did not wait for the
 // uploads of sr_multi_predict_pcm's pieces.  Removed in round 4.)
 static void predict_unpipelined(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out,
-                                int flags) {
+                                int flags, const OpenSetFetch *open) {
     SRBatch *feat_ws = &per_device<SRBatch>();   // reused across steps: the serving loop allocates nothing
     mfcc_extract_batch(*m, *pcm, nd, 1, *feat_ws);
+    if (open) {      // the decision kernel reads the device's sums: no delivery by finalize itself (open_set.hip)
+        score_resolved(*set, *feat_ws, false, flags, 0, sums_out, argmax_out, nullptr, open);
+        return;
+    }
     // (small result sets land in host memory by themselves: SCORE_HOST_DELIVER, score.hpp)
     const int deliver = (sums_out && argmax_out && host_deliverable((size_t)pcm->n_utt, (size_t)set->host.n_models)) ? SCORE_HOST_DELIVER : 0;
     score_resolved(*set, *feat_ws, false, flags, deliver, sums_out, argmax_out, nullptr);
@@ -712,10 +716,11 @@ static void predict_unpipelined(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd
 }  // extern "C"
 
 namespace sr {
-void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out, int flags) {
+void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out, int flags,
+                 const OpenSetFetch *open) {
     if (!m || !set || !pcm) fail("null argument");
     ensure_device();
-    predict_unpipelined(m, set, pcm, nd, sums_out, argmax_out, flags);
+    predict_unpipelined(m, set, pcm, nd, sums_out, argmax_out, flags, open);
 }
 }  // namespace sr
 
@@ -724,7 +729,51 @@ extern "C" {
 int sr_predict_pcm_batch(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out,
                          int *argmax_out, int flags) {
     SR_TRY
-    predict_pcm(m, set, pcm, nd, sums_out, argmax_out, flags);
+    predict_pcm(m, set, pcm, nd, sums_out, argmax_out, flags, nullptr);
+    return 0;
+    SR_CATCH(-1)
+}
+
+// ---- the open-set decision (open_set.hip).  Every argument is checked before the device is touched. ----
+
+int sr_open_set_decide(const double *sums, int U, int S, int bg, const int64_t *n_frames, double threshold, int *label_out,
+                       double *margin_out) {
+    SR_TRY
+    if (U < 0 || S <= 0) fail("sr_open_set_decide: bad shape (%d utterances x %d models)", U, S);
+    if (!label_out || !margin_out) fail("sr_open_set_decide: null output (labels and margins are both required)");
+    if (U > 0 && (!sums || !n_frames)) fail("sr_open_set_decide: null argument");
+    const OpenSetRule rule{bg, threshold};
+    open_set_check(rule, S);
+    for (int u = 0; u < U; u++)
+        if (n_frames[u] < 0) fail("sr_open_set_decide: utterance %d has a negative frame count", u);
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_open_set_decide");
+    open_set_decide_host(sums, U, S, rule, n_frames, label_out, margin_out);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_score_batch_set_open(SRModelSet *set, SRBatch *features, int bg, double threshold, double *sums_out, int *label_out,
+                            double *margin_out, int flags) {
+    SR_TRY
+    if (!set || !features) fail("sr_score_batch_set_open: null argument");
+    if (!label_out || !margin_out) fail("sr_score_batch_set_open: null output (labels and margins are both required)");
+    const OpenSetFetch open{{bg, threshold}, label_out, margin_out};
+    open_set_check(open.rule, set->host.n_models);
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_score_batch_set_open");
+    score_batch_set_open(*set, *features, sums_out, open, flags);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_predict_pcm_batch_open(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int bg, double threshold, double *sums_out,
+                              int *label_out, double *margin_out, int flags) {
+    SR_TRY
+    if (!m || !set || !pcm) fail("sr_predict_pcm_batch_open: null argument");
+    if (!label_out || !margin_out) fail("sr_predict_pcm_batch_open: null output (labels and margins are both required)");
+    const OpenSetFetch open{{bg, threshold}, label_out, margin_out};
+    open_set_check(open.rule, set->host.n_models);
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_predict_pcm_batch_open");
+    predict_pcm(m, set, pcm, nd, sums_out, nullptr, flags, &open);
     return 0;
     SR_CATCH(-1)
 }

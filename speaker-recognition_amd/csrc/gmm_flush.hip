@@ -348,7 +348,7 @@ static void flush_evaluate(SRModelSet &set, SRBatch &feat, const TileTable &tt, 
 }
 
 void flush_resolve(SRModelSet &set, SRBatch &feat, const TileTable &tt, const int2 *d_list, int count, double *d_sums,
-                   int *d_argmax, float *d_frame_ll) {
+                   int *d_argmax, float *d_frame_ll, const OpenSetRule *open, double *d_open_margin, int *d_open_label) {
     if (count <= 0) return;
     auto &fw = per_device<FlushWorkspace>();
     const int S = set.host.n_models;
@@ -362,6 +362,8 @@ void flush_resolve(SRModelSet &set, SRBatch &feat, const TileTable &tt, const in
     hipLaunchKernelGGL(gmm_flush_argmax_kernel, dim3((unsigned)utts.size()), dim3(256), 0, ctx().stream, fw.utts.p, S, d_sums,
                        d_argmax);
     SR_HIP(hipGetLastError());
+    // the open-set decision of the same utterances, on their patched sums (open_set.hip)
+    if (open) launch_open_set(d_sums, S, *open, feat.d_offsets.p, nullptr, fw.utts.p, (int)utts.size(), d_open_margin, d_open_label);
     sync_stream();       // the uploads above read host vectors that die with this frame
 }
 

@@ -70,6 +70,7 @@ struct ScoreWorkspace {
     DevBuf<double> ref_partial;
     DevBuf<int> exc_list;                // ... and its exception lists ({tile, listed frames} per block) + the exception pass's plan
     DevBuf<float> hy_a, hy_b;            // hybrid sets: per-frame LL of the two sub-sets
+    DevBuf<double> open;                 // the open-set decision of a fetch that asks for it: margin [U], then label [U] (open_set.hip)
     DevBuf<int2> flush_list;             // (tile, model) pairs in the partial-product band (lse.hpp, gmm_flush.hip)
     size_t flush_min_cap = 0;            // set after an overflow: the next pass gets a list of that length
     // SCORE_HOST_DELIVER: the page-locked landing area and the last sequence number handed out
@@ -479,6 +480,7 @@ struct ResultStaging {
     PinnedBuf<int> argmax;
     PinnedBuf<float> frame_ll;
     PinnedBuf<int> oor;
+    PinnedBuf<double> open;
 };
 static ResultStaging &staging() { return per_device<ResultStaging>(); }   // leaked on purpose (no hipHostFree at exit)
 
@@ -523,9 +525,20 @@ static int fetch_delivered(SRModelSet &set, SRBatch &feat, const ScoreResult &r,
 
 // The pass's two counters, and what the caller asked for, into the pinned staging buffers (large per-frame arrays straight into
 // `frame_ll_out`); waits for them.  Returns where the staged argmax values are (behind the sums when they came in one copy).
-static const int *stage_results(const ScoreResult &r, size_t U, size_t S, bool want_sums, bool want_argmax, size_t fll_n, bool stage_fll,
-                                float *frame_ll_out) {
+// `open`: the open-set decision comes with them -- the kernel first, over every utterance, unless `open_decided` says the device's
+// block already holds the decision of these sums (gmm_flush.hip redid the patched utterances' itself).
+static const int *stage_results(const ScoreResult &r, SRBatch &feat, size_t U, size_t S, bool want_sums, bool want_argmax, size_t fll_n,
+                                bool stage_fll, float *frame_ll_out, const OpenSetFetch *open, bool &open_decided) {
     auto &st = staging();
+    if (open && U) {
+        auto &w = ws();
+        w.open.ensure(open_set_doubles(U));
+        st.open.ensure(open_set_doubles(U));
+        if (!open_decided)
+            launch_open_set(r.d_sums, (int)S, open->rule, feat.d_offsets.p, nullptr, nullptr, (int)U, w.open.p, open_set_labels(w.open.p, U));
+        open_decided = true;
+        SR_HIP(hipMemcpyAsync(st.open.p, w.open.p, open_set_bytes(U), hipMemcpyDeviceToHost, ctx().stream));
+    }
     st.oor.p[0] = st.oor.p[1] = 0;
     // (the workspace keeps the two counters, and the argmax values behind the sums, side by side: one copy each)
     copy_pass_flags(r, st.oor.p, ctx().stream);
@@ -563,7 +576,7 @@ static const int *stage_results(const ScoreResult &r, size_t U, size_t S, bool w
 // are resolved first (gmm_flush.hip patches the device results; nothing to do, and nothing extra copied but one int,
 // when there are none -- the case of real data).
 bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult &r_in, double *sums_out, int *argmax_out,
-                   float *frame_ll_out) {
+                   float *frame_ll_out, const OpenSetFetch *open) {
     auto &st = staging();
     ScoreResult r = r_in;
     const size_t U = (size_t)feat.n_utt, S = (size_t)set.host.n_models, n_frames = (size_t)feat.n_rows;
@@ -571,6 +584,7 @@ bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult 
         bool armed = false;
         ~ResetCap() { if (armed) ws().flush_min_cap = 0; }
     } reset_cap;
+    if (r.h_deliver && open) fail("open-set decision: the pass delivered its results to the host by itself");
     if (r.h_deliver) {
         int n_flush = 0;
         const int how = fetch_delivered(set, feat, r, sums_out, argmax_out, n_flush);
@@ -585,8 +599,9 @@ bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult 
     const bool stage_fll = fll_n > 0 && fll_n * sizeof(float) <= ((size_t)64 << 20);
     const int *h_argmax = nullptr;
     bool rescored = false;
+    bool open_decided = false;              // the device's decision block belongs to the sums of `r` as they stand
     for (;;) {
-        h_argmax = stage_results(r, U, S, sums_out != nullptr, argmax_out != nullptr, fll_n, stage_fll, frame_ll_out);
+        h_argmax = stage_results(r, feat, U, S, sums_out != nullptr, argmax_out != nullptr, fll_n, stage_fll, frame_ll_out, open, open_decided);
         if (r.d_oor && st.oor.p[0] != 0) return false;
         int n_flush = st.oor.p[1];
         if (n_flush == 0) break;
@@ -600,9 +615,10 @@ bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult 
             reset_cap.armed = true;
             const bool own = r.d_frame_ll && r.d_frame_ll != ws().frame_ll.p;
             r = score_device(set, feat, r.d_frame_ll != nullptr, flags, own ? const_cast<float *>(r.d_frame_ll) : nullptr);
+            open_decided = false;
             continue;
         }
-        if (!fll_n && sums_out && argmax_out && U) {
+        if (!fll_n && sums_out && argmax_out && U && !open) {
             // Sums and argmax are already here: complete the HOST copies (one more wait for the tiles' exact sums; what sr_multi's
             // pieces do) instead of patching the device's and copying everything a second time -- two waits, two uploads, two
             // kernels and a copy of all U x S sums less per call.
@@ -612,9 +628,16 @@ bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult 
             flush_resolve_host(set, feat, *r.tiles, r.d_flush_list, n_flush, st.sums.p, const_cast<int *>(h_argmax));
             break;
         }
+        // (an open-set fetch: the decision staged above was taken on sums without the noted pairs and goes nowhere -- the
+        // patched utterances are decided again behind the patch, and the next turn of the loop stages the block afresh)
         flush_resolve(set, feat, *r.tiles, r.d_flush_list, n_flush, const_cast<double *>(r.d_sums),
-                      const_cast<int *>(r.d_argmax), const_cast<float *>(r.d_frame_ll));
+                      const_cast<int *>(r.d_argmax), const_cast<float *>(r.d_frame_ll), open ? &open->rule : nullptr,
+                      open ? ws().open.p : nullptr, open ? open_set_labels(ws().open.p, U) : nullptr);
         r.d_flush_count = nullptr;          // resolved: copy the patched results out
+    }
+    if (open && U) {
+        std::memcpy(open->margin_out, st.open.p, U * sizeof(double));
+        std::memcpy(open->label_out, open_set_labels(st.open.p, U), U * sizeof(int));
     }
     if (sums_out && U) std::memcpy(sums_out, st.sums.p, U * S * sizeof(double));
     if (argmax_out && U) std::memcpy(argmax_out, h_argmax, U * sizeof(int));
@@ -628,6 +651,13 @@ void score_batch_set(SRModelSet &set, SRBatch &feat, double *sums_out, int *argm
     // (either result alone too: the legacy ABI's score_all wants one sum, pygmm.cc:98-104, and so does every second EM iteration)
     const int deliver = (!frame_ll_out && (sums_out || argmax_out) && host_deliverable((size_t)feat.n_utt, (size_t)set.host.n_models)) ? SCORE_HOST_DELIVER : 0;
     score_resolved(set, feat, frame_ll_out != nullptr, flags, deliver, sums_out, argmax_out, frame_ll_out);
+}
+
+// The sibling of score_batch_set with the open-set decision: the same pass, the decision kernel behind finalize (and behind the
+// patch of gmm_flush.hip), labels and margins back with the sums in the fetch's one wait.  No SCORE_HOST_DELIVER: the decision
+// reads the device's sums.
+void score_batch_set_open(SRModelSet &set, SRBatch &feat, double *sums_out, const OpenSetFetch &open, int flags) {
+    score_resolved(set, feat, false, flags, 0, sums_out, nullptr, nullptr, &open);
 }
 
 }  // namespace sr

@@ -67,6 +67,10 @@ struct SRMulti {
         DevBuf<int2> d_list;
         const TileTable *tiles = nullptr;
         int flush_cap = 0;
+        // sr_multi_predict_pcm_open: the piece's open-set decision -- margins, then labels (open_set.hip) -- on the device and where
+        // it lands
+        DevBuf<double> d_open;
+        PinnedBuf<double> h_open;
     };
     struct Slot {
         int device = 0;
@@ -178,8 +182,11 @@ bool host_pinned(const void *p) {
 // flushes (lse.hpp) -- is noticed in the piece's flags afterwards and that piece is scored again, synchronously, from its
 // features, which are still on the device (as csrc/stream.cpp does for a serving tick).
 // The device's lock is taken piece by piece, so slots that share a GPU interleave on its stream.
+// `open`: every piece also decides its utterances against the background column on this slot's device, behind its finalize
+// (label_out / margin_out: the caller's arrays); a piece that needs the host -- saturation, or pairs in the band, which the closed-set
+// call completes in host memory -- is then scored again from its features, and decided on the device behind gmm_flush.hip's patch.
 void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *off, int nd, int flags, bool pinned,
-              double *sums_out, int *argmax_out) {
+              double *sums_out, int *argmax_out, const OpenSetRule *open, int *label_out, double *margin_out) {
     auto drain = [&]() {                   // nothing of this call may still be reading the caller's buffer when it returns
         try {
             (void)hipStreamSynchronize(ctx().copy);
@@ -307,6 +314,10 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
                 ch.h_sums.ensure((size_t)std::max(1, nu) * S + ((size_t)std::max(1, nu) + 1) / 2);
                 ch.h_argmax.ensure((size_t)std::max(1, nu));
                 ch.h_flags.ensure(2);
+                if (open) {
+                    ch.d_open.ensure(open_set_doubles((size_t)std::max(1, nu)));
+                    ch.h_open.ensure(open_set_doubles((size_t)std::max(1, nu)));
+                }
                 ch.h_flags.p[0] = ch.h_flags.p[1] = 0;         // (nothing of this piece is in flight: the previous call waited for it)
             }
             if (!pinned) ch.staging.ensure((size_t)std::max<int64_t>(1, n_samp));
@@ -346,6 +357,10 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             // (the pass's two counters and its sums + argmax lie side by side in the workspace: one copy each instead of two -- a copy
             // is ~8 us on the stream, and eight pieces' small operations are what keeps the call above max(copy, kernels))
             copy_pass_flags(r, ch.h_flags.p, ctx().stream);
+            if (open) {
+                launch_open_set(r.d_sums, S, *open, ch.feat.d_offsets.p, nullptr, nullptr, nu, ch.d_open.p, open_set_labels(ch.d_open.p, (size_t)nu));
+                SR_HIP(hipMemcpyAsync(ch.h_open.p, ch.d_open.p, open_set_bytes((size_t)nu), hipMemcpyDeviceToHost, ctx().stream));
+            }
             ch.tiles = r.tiles;
             ch.flush_cap = 0;
             if (r.d_flush_count) {
@@ -371,7 +386,13 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
             const int nu = ch.u1 - ch.u0;
             if (nu == 0) continue;
             SR_HIP(hipEventSynchronize(ch.done));
-            if (ch.h_flags.p[0] == 0 && ch.h_flags.p[1] > 0 && ch.h_flags.p[1] <= ch.flush_cap) {
+            if (open && (ch.h_flags.p[0] != 0 || ch.h_flags.p[1] != 0)) {
+                std::lock_guard<std::recursive_mutex> lock(api_mutex());
+                const int fl = flags | (ch.h_flags.p[0] != 0 ? SCORE_PRECISE : 0);
+                ch.h_arg = ch.h_argmax.p;
+                const OpenSetFetch of{*open, open_set_labels(ch.h_open.p, (size_t)nu), ch.h_open.p};
+                score_resolved(*s.set, ch.feat, false, fl, 0, ch.h_sums.p, ch.h_argmax.p, nullptr, &of);
+            } else if (ch.h_flags.p[0] == 0 && ch.h_flags.p[1] > 0 && ch.h_flags.p[1] <= ch.flush_cap) {
                 // pairs in the band, nothing else: re-evaluate exactly those with the reference's arithmetic and complete the
                 // piece's results where they are, in host memory -- on the device's SECOND stream (what it reads -- the piece's
                 // features, the models, the list -- is nobody else's), so that its one host wait does not wait for the later
@@ -395,6 +416,10 @@ void run_slot(SRMulti *m, SRMulti::Slot &s, const int16_t *pcm, const int64_t *o
                 else std::memcpy(s.sums.data() + (size_t)i * S, ch.h_sums.p + at * S, n * S * sizeof(double));
                 if (argmax_out) std::memcpy(argmax_out + s.utts[i], ch.h_arg + at, n * sizeof(int));
                 else std::memcpy(s.argmax.data() + i, ch.h_arg + at, n * sizeof(int));
+                if (open) {
+                    std::memcpy(margin_out + s.utts[i], ch.h_open.p + at, n * sizeof(double));
+                    std::memcpy(label_out + s.utts[i], open_set_labels(ch.h_open.p, (size_t)nu) + at, n * sizeof(int));
+                }
                 i = j + 1;
             }
         }
@@ -538,6 +563,7 @@ void sr_multi_free(SRMulti *m) {
                 ch.scratch = nullptr;
                 ch.feat = SRBatch();
                 ch.d_list.release();
+                ch.d_open.release();
             }
         } catch (...) {
         }
@@ -577,15 +603,21 @@ int sr_multi_slot_device(SRMulti *m, int slot) {
     return (m && slot >= 0 && slot < (int)m->slots.size()) ? m->slots[slot].device : -1;
 }
 
-int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt,
-                         int nd, double *sums_out, int *argmax_out, double *slot_seconds_out, int flags) {
+static int multi_predict(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt, int nd, double *sums_out,
+                         int *argmax_out, double *slot_seconds_out, int flags, const OpenSetRule *open, int *label_out,
+                         double *margin_out) {
     try {
         if (!m || !sample_offsets || n_utt < 0) fail("bad arguments to sr_multi_predict_pcm");
+        if (open) {
+            if (!label_out || !margin_out) fail("sr_multi_predict_pcm_open: null output (labels and margins are both required)");
+            if (m->full) fail("sr_multi_predict_pcm_open: a full-covariance predictor has no open-set decision (no UBM column: diagonal sets only)");
+            open_set_check(*open, m->n_models);
+        }
         if (sample_offsets[0] != 0) fail("sample_offsets[0] must be 0");
         for (int u = 0; u < n_utt; u++)
             if (sample_offsets[u + 1] < sample_offsets[u]) fail("sample_offsets must be non-decreasing");
         if (sample_offsets[n_utt] > 0 && !pcm) fail("null PCM pointer");
-        if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_multi_predict_pcm");
+        if (gpu_runtime_lost()) fail_gpu_runtime_lost(open ? "sr_multi_predict_pcm_open" : "sr_multi_predict_pcm");
         if (m->full) {
             if (nd < 0 || nd > 2) fail("delta order must be 0, 1 or 2");
             if (m->mfcc->n_lpc > 0 && nd != 0) fail("LPC columns (mix_feature) come without deltas: use nd = 0");
@@ -611,7 +643,7 @@ int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_o
         std::vector<std::thread> th;
         for (auto &s : m->slots) s.error.clear();
         // (every slot writes its utterances' rows into the caller's arrays itself: disjoint rows)
-        for (auto *s : active) th.emplace_back(run_slot, m, std::ref(*s), pcm, sample_offsets, nd, flags, pinned, sums_out, argmax_out);
+        for (auto *s : active) th.emplace_back(run_slot, m, std::ref(*s), pcm, sample_offsets, nd, flags, pinned, sums_out, argmax_out, open, label_out, margin_out);
         for (auto &t : th) t.join();
         for (auto &s : m->slots)
             if (!s.error.empty()) fail("device %d: %s", s.device, s.error.c_str());
@@ -622,6 +654,17 @@ int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_o
         set_error("%s", e.what());
         return -1;
     }
+}
+
+int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt,
+                         int nd, double *sums_out, int *argmax_out, double *slot_seconds_out, int flags) {
+    return multi_predict(m, pcm, sample_offsets, n_utt, nd, sums_out, argmax_out, slot_seconds_out, flags, nullptr, nullptr, nullptr);
+}
+
+int sr_multi_predict_pcm_open(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt, int nd, int bg, double threshold,
+                              double *sums_out, int *label_out, double *margin_out, double *slot_seconds_out, int flags) {
+    const OpenSetRule rule{bg, threshold};
+    return multi_predict(m, pcm, sample_offsets, n_utt, nd, sums_out, nullptr, slot_seconds_out, flags, &rule, label_out, margin_out);
 }
 
 }  // extern "C"

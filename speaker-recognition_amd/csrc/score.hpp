@@ -133,6 +133,36 @@ struct ScoreResult {
     unsigned deliver_seq = 0;
 };
 
+// ---- the open-set decision (open_set.hip): best speaker's per-frame margin over the background column against a threshold ----
+struct OpenSetRule {
+    int bg;                // the background (UBM) column of the sums
+    double threshold;      // margin < threshold: rejected (label -1)
+};
+// the decision of U utterances as one block: double margin[U], then int label[U] -- one copy
+inline size_t open_set_bytes(size_t n_utt) { return n_utt * (sizeof(double) + sizeof(int)); }
+inline size_t open_set_doubles(size_t n_utt) { return n_utt + (n_utt + 1) / 2; }
+inline int *open_set_labels(double *block, size_t n_utt) { return reinterpret_cast<int *>(block + n_utt); }
+// bg inside [0, n_models), threshold not a NaN: checked by every entry point before it touches the device
+inline void open_set_check(const OpenSetRule &rule, int n_models) {
+    if (rule.bg < 0 || rule.bg >= n_models) fail("open-set decision: background column %d outside [0, %d)", rule.bg, n_models);
+    if (rule.threshold != rule.threshold) fail("open-set decision: the threshold is a NaN");
+}
+// The kernel, enqueued on the current stream, over final sums [U][n_models] on the device.  Frame counts: `d_counts` (ints, per
+// utterance) when given, else the row offsets `d_off` [U + 1].  `d_utts` (or null: 0 .. n_items - 1) lists the utterances decided.
+void launch_open_set(const double *d_sums, int n_models, const OpenSetRule &rule, const int64_t *d_off, const int *d_counts,
+                     const int *d_utts, int n_items, double *d_margin, int *d_label);
+// sums in host memory: upload, kernel, one copy back
+void open_set_decide_host(const double *sums, int U, int S, const OpenSetRule &rule, const int64_t *n_frames, int *label_out,
+                          double *margin_out);
+// What a fetch carries when the caller wants the decision with the sums: the kernel runs behind finalize over every utterance, and
+// again -- over the patched utterances only, as gmm_flush_argmax_kernel does -- behind gmm_flush.hip's patch; labels and margins
+// reach the host with the sums of the pass whose results stand.  Such a fetch never takes the host-side patch.
+struct OpenSetFetch {
+    OpenSetRule rule;
+    int *label_out;        // [U], host
+    double *margin_out;    // [U], host
+};
+
 // Scores every utterance of `feat` against every model of `set`; leaves results on the device.
 // `frame_ll_dst`: device buffer [S][n_frames] the per-frame values go to instead of the workspace's own.
 ScoreResult score_device(SRModelSet &set, SRBatch &feat, bool want_frame_ll, int flags, float *frame_ll_dst = nullptr);
@@ -146,16 +176,17 @@ void score_batch_set(SRModelSet &set, SRBatch &feat, double *sums_out, int *argm
 // Returns false when the fp16 engine reported saturated frames (nothing was copied out: score again
 // with SCORE_PRECISE).
 bool fetch_results(SRModelSet &set, SRBatch &feat, int flags, const ScoreResult &r, double *sums_out,
-                   int *argmax_out, float *frame_ll_out);
+                   int *argmax_out, float *frame_ll_out, const OpenSetFetch *open = nullptr);
 // score_device + fetch_results; when the fp16 engine reported saturated frames, the whole batch again on the fp32-grade engines.
 // `flags`: what the first pass and both fetches run with; `deliver`: SCORE_HOST_DELIVER or 0, for the first pass only.
 // Returns the pass whose results stand.
+// `open`: the open-set decision of the utterances with it (then `deliver` must be 0: the decision is taken on the device's sums).
 inline ScoreResult score_resolved(SRModelSet &set, SRBatch &feat, bool want_frame_ll, int flags, int deliver, double *sums_out, int *argmax_out,
-                           float *frame_ll_out) {
+                           float *frame_ll_out, const OpenSetFetch *open = nullptr) {
     const ScoreResult r = score_device(set, feat, want_frame_ll, flags | deliver);
-    if (fetch_results(set, feat, flags, r, sums_out, argmax_out, frame_ll_out)) return r;
+    if (fetch_results(set, feat, flags, r, sums_out, argmax_out, frame_ll_out, open)) return r;
     const ScoreResult r2 = score_device(set, feat, want_frame_ll, flags | SCORE_PRECISE);
-    fetch_results(set, feat, flags | SCORE_PRECISE, r2, sums_out, argmax_out, frame_ll_out);
+    fetch_results(set, feat, flags | SCORE_PRECISE, r2, sums_out, argmax_out, frame_ll_out, open);
     return r2;
 }
 // The pass's saturation flag and partial-product count -> h_flags[0], [1] (page-locked), left in flight on `stream`: one copy when
@@ -174,8 +205,10 @@ inline size_t results_bytes(size_t n_utt, size_t n_models, size_t ints_per_utt =
 }
 // gmm_flush.hip: the frames of the noted (tile, model) pairs again with the reference's own linear-domain arithmetic;
 // adds the tiles' sums to `d_sums`, redoes the argmax of the utterances touched, overwrites the per-frame values
+// (`open`: the open-set decision of the utterances touched is redone too, into `d_open_margin` / `d_open_label`)
 void flush_resolve(SRModelSet &set, SRBatch &feat, const TileTable &tt, const int2 *d_list, int count, double *d_sums,
-                   int *d_argmax, float *d_frame_ll);
+                   int *d_argmax, float *d_frame_ll, const OpenSetRule *open = nullptr, double *d_open_margin = nullptr,
+                   int *d_open_label = nullptr);
 // the same for results that already sit in host memory (sums[U][S], argmax[U] of the batch `feat`): patched on the host, one wait
 void flush_resolve_host(SRModelSet &set, SRBatch &feat, const TileTable &tt, const int2 *d_list, int count, double *h_sums,
                         int *h_argmax);
@@ -186,7 +219,10 @@ void flush_stats(long *calls, long *pairs, long *frames);
 }  // namespace sr
 struct SRMfcc;
 namespace sr {
-void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out, int flags);
+void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_out, int *argmax_out, int flags,
+                 const OpenSetFetch *open = nullptr);
+// score_device + fetch with the open-set decision (gmm_score_host.cpp)
+void score_batch_set_open(SRModelSet &set, SRBatch &feat, double *sums_out, const OpenSetFetch &open, int flags);
 // Packs + uploads a model set on the current device.
 void upload_model_set(SRModelSet &s);
 // a GMM handle's own one-model set on the current device, packed and uploaded once (abi.cpp; invalidated by GMM::drop_single)

@@ -21,6 +21,10 @@
 // per-frame values and sums them with that same kernel (the engines' own per-utterance sums cover the padding rows too and are
 // not used); when the pass's flags come back set, collect re-scores the slot's features synchronously as below, resolves the
 // partial-product band on the per-frame values (flush_resolve overwrites them) and sums again.
+// sr_stream_set_open (diagonal sessions, before the first submit) adds the open-set decision to every tick: open_set_decision_kernel
+// (open_set.hip) behind the tick's finalize -- over the windows' row offsets, or over the VAD session's device-side frame counts --
+// and one more small copy (margins, labels) into the slot's pinned block; a captured tick holds both.  Rule and threshold are part
+// of the capture and fixed for the session's life.  A tick that collect re-scores is decided again on its final sums.
 #include "../../include/pygmm_hip.h"
 
 #include "batch.hpp"
@@ -54,6 +58,8 @@ struct SRStream {
         SRBatch vpcm;
         sr::DevBuf<double> d_res;
         int *h_voiced = nullptr;         // pinned, behind h_argmax in the same allocation
+        sr::DevBuf<double> d_open;       // sr_stream_set_open: the tick's margins [n_windows], then labels [n_windows] ...
+        double *h_open = nullptr;        // ... and where they land (pinned)
         hipEvent_t h2d_done = nullptr, done = nullptr, t_submit = nullptr;
         hipGraphExec_t exec = nullptr;   // SR_STREAM_GRAPH: the captured tick
         long exec_epoch = -1;
@@ -62,6 +68,8 @@ struct SRStream {
     std::deque<int> in_flight;           // slot indices, oldest first
     long submitted = 0;
     int device = 0;                      // the GPU the session lives on
+    bool open = false;                   // sr_stream_set_open: every tick carries the open-set decision
+    sr::OpenSetRule open_rule{0, 0.0};
 };
 
 using namespace sr;
@@ -82,6 +90,7 @@ void stream_destroy(SRStream *s) {
         if (sl.h_pcm) (void)hipHostFree(sl.h_pcm);
         if (sl.h_sums) (void)hipHostFree(sl.h_sums);        // (h_argmax lives behind the sums in the same allocation)
         if (sl.h_oor) (void)hipHostFree(sl.h_oor);
+        if (sl.h_open) (void)hipHostFree(sl.h_open);
         if (sl.h2d_done) (void)hipEventDestroy(sl.h2d_done);
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.t_submit) (void)hipEventDestroy(sl.t_submit);
@@ -102,6 +111,15 @@ void vad_sum_frames(SRStream *s, SRStream::Slot &sl, const ScoreResult &r) {
     if (!r.d_frame_ll) fail("serving stream: the scoring pass left no per-frame values");
     masked_finalize(r.d_frame_ll, (long)sl.feat.n_rows, sl.feat.d_offsets.p, vad_frames(s, sl), s->n_windows, s->n_models, true, sl.d_res.p,
                     vad_argmax(s, sl));
+}
+
+// the open-set decision of a tick behind its final sums (`d_counts`: the VAD session's frame counts, else the windows' row offsets)
+// and the copy of the block into the slot's pinned memory, left in flight
+void enqueue_open(SRStream *s, SRStream::Slot &sl, const double *d_sums, const int *d_counts) {
+    const size_t U = (size_t)s->n_windows;
+    launch_open_set(d_sums, s->n_models, s->open_rule, sl.feat.d_offsets.p, d_counts, nullptr, s->n_windows, sl.d_open.p,
+                    open_set_labels(sl.d_open.p, U));
+    SR_HIP(hipMemcpyAsync(sl.h_open, sl.d_open.p, open_set_bytes(U), hipMemcpyDeviceToHost, ctx().stream));
 }
 
 // the diagonal pass of a tick, plain or VAD: the scoring launches and the copies of its two flags, left in flight
@@ -126,6 +144,7 @@ void enqueue_vad_tick(SRStream *s, SRStream::Slot &sl) {
         fullset_score_device_masked(*s->fset, sl.feat, d_frames, sl.d_res.p);
     } else {
         vad_sum_frames(s, sl, score_tick(s, sl, true));
+        if (s->open) enqueue_open(s, sl, sl.d_res.p, d_frames);
     }
     SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, results_bytes(s->n_windows, s->n_models, 2), hipMemcpyDeviceToHost, ctx().stream));
 }
@@ -140,6 +159,7 @@ void enqueue_tick(SRStream *s, SRStream::Slot &sl) {
         return;
     }
     const ScoreResult r = score_tick(s, sl, false);
+    if (s->open) enqueue_open(s, sl, r.d_sums, nullptr);
     const size_t n_sums = (size_t)s->n_windows * s->n_models;
     if ((const void *)r.d_argmax == (const void *)(r.d_sums + n_sums)) {
         SR_HIP(hipMemcpyAsync(sl.h_sums, r.d_sums, results_bytes(s->n_windows, s->n_models), hipMemcpyDeviceToHost, ctx().stream));
@@ -375,10 +395,13 @@ int sr_stream_submit(SRStream *s, const int16_t *pcm) {
     }
 }
 
-static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms) {
+static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms, int *label_out = nullptr,
+                          double *margin_out = nullptr, bool want_open = false) {
     try {
         std::lock_guard<std::recursive_mutex> _api_lock(api_mutex());
         if (!s) fail("null stream");
+        if (want_open && !s->open) fail("sr_stream_collect_open: the session carries no open-set decision (sr_stream_set_open before the first submit)");
+        if (want_open && (!label_out || !margin_out)) fail("sr_stream_collect_open: null output (labels and margins are both required)");
         if (s->device != current_device()) fail("stream lives on device %d, the calling thread is on device %d", s->device, current_device());
         ensure_device();
         if (voiced_out && !s->vad) fail("not a voice-activity session: no voiced counts (sr_stream_create_vad)");
@@ -396,8 +419,14 @@ static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *v
                 // per-frame values again; fetch_results without host destinations resolves the band ON THE DEVICE (flush_resolve
                 // overwrites the per-frame values of the noted pairs), then the same sum over each window's first T rows
                 vad_sum_frames(s, sl, score_resolved(*s->set, sl.feat, true, fl, 0, nullptr, nullptr, nullptr));
+                if (s->open) enqueue_open(s, sl, sl.d_res.p, vad_frames(s, sl));       // the decision again, on the final sums
                 SR_HIP(hipMemcpyAsync(sl.h_sums, sl.d_res.p, results_bytes(s->n_windows, s->n_models), hipMemcpyDeviceToHost, ctx().stream));
                 sync_stream();
+            } else if (s->open) {
+                // (the decision with the re-scored sums: taken on the device behind finalize and, for the utterances
+                // gmm_flush.hip patches, behind the patch)
+                const OpenSetFetch open{s->open_rule, open_set_labels(sl.h_open, (size_t)s->n_windows), sl.h_open};
+                score_resolved(*s->set, sl.feat, false, fl, 0, sl.h_sums, sl.h_argmax, nullptr, &open);
             } else {
                 score_resolved(*s->set, sl.feat, false, fl, 0, sl.h_sums, sl.h_argmax, nullptr);
             }
@@ -406,6 +435,10 @@ static int stream_collect(SRStream *s, double *sums_out, int *argmax_out, int *v
         if (sums_out) std::memcpy(sums_out, sl.h_sums, (size_t)s->n_windows * s->n_models * sizeof(double));
         if (argmax_out) std::memcpy(argmax_out, sl.h_argmax, (size_t)s->n_windows * sizeof(int));
         if (voiced_out) std::memcpy(voiced_out, sl.h_voiced, (size_t)s->n_windows * sizeof(int));
+        if (want_open) {
+            std::memcpy(margin_out, sl.h_open, (size_t)s->n_windows * sizeof(double));
+            std::memcpy(label_out, open_set_labels(sl.h_open, (size_t)s->n_windows), (size_t)s->n_windows * sizeof(int));
+        }
         if (device_ms) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, sl.t_submit, sl.done);
@@ -425,6 +458,35 @@ int sr_stream_collect(SRStream *s, double *sums_out, int *argmax_out, double *de
 
 int sr_stream_collect_vad(SRStream *s, double *sums_out, int *argmax_out, int *voiced_out, double *device_ms) {
     return stream_collect(s, sums_out, argmax_out, voiced_out, device_ms);
+}
+
+int sr_stream_set_open(SRStream *s, int bg, double threshold) {
+    try {
+        if (!s) fail("sr_stream_set_open: null stream");
+        if (s->fset) fail("sr_stream_set_open: a full-covariance session has no open-set decision (no UBM column: diagonal sets only)");
+        const OpenSetRule rule{bg, threshold};
+        open_set_check(rule, s->n_models);
+        if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_stream_set_open");
+        std::lock_guard<std::recursive_mutex> _api_lock(api_mutex());
+        if (s->submitted > 0) fail("sr_stream_set_open: ticks were submitted already (rule and threshold belong to the captured tick: set them before the first submit)");
+        if (s->device != current_device()) fail("stream lives on device %d, the calling thread is on device %d", s->device, current_device());
+        ensure_device();
+        const size_t U = (size_t)s->n_windows;
+        for (auto &sl : s->slot) {
+            if (!sl.d_open.p) sl.d_open.alloc(open_set_doubles(U));
+            if (!sl.h_open) SR_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_open), open_set_doubles(U) * sizeof(double), hipHostMallocDefault));
+        }
+        s->open_rule = rule;
+        s->open = true;
+        return 0;
+    } catch (const std::exception &e) {
+        set_error("%s", e.what());
+        return -1;
+    }
+}
+
+int sr_stream_collect_open(SRStream *s, double *sums_out, int *label_out, double *margin_out, int *voiced_out, double *device_ms) {
+    return stream_collect(s, sums_out, nullptr, voiced_out, device_ms, label_out, margin_out, true);
 }
 
 }  // extern "C"

@@ -52,6 +52,45 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return tot;
 }
 
+// First maximum of the pairs (v, idx) over the 64 lanes: the larger value wins, equal values the lower index; the result is
+// valid in every lane (it comes back through SGPRs).  Same walk as wave_sum_f64 -- DPP row_shr 1/2/4/8, then the four row
+// results in order -- with the lanes a shift has no source for keeping their own pair (bound_ctrl off, old = own).  The
+// order is total as long as no value is a NaN: the caller keeps those out.  All 64 lanes must be active.
+__device__ __forceinline__ void wave_first_max_f64(double &v, int &idx) {
+    union { double d; int i[2]; } a, b;
+    auto take = [&](double ov, int oi) {
+        if (ov > v || (ov == v && oi < idx)) {
+            v = ov;
+            idx = oi;
+        }
+    };
+#define SR_DPP_STEP(CTRL)                                                              \
+    {                                                                                  \
+        a.d = v;                                                                       \
+        b.i[0] = __builtin_amdgcn_update_dpp(a.i[0], a.i[0], CTRL, 0xf, 0xf, false);   \
+        b.i[1] = __builtin_amdgcn_update_dpp(a.i[1], a.i[1], CTRL, 0xf, 0xf, false);   \
+        const int oi = __builtin_amdgcn_update_dpp(idx, idx, CTRL, 0xf, 0xf, false);   \
+        take(b.d, oi);                                                                 \
+    }
+    SR_DPP_STEP(0x111)   // row_shr:1
+    SR_DPP_STEP(0x112)   // row_shr:2
+    SR_DPP_STEP(0x114)   // row_shr:4
+    SR_DPP_STEP(0x118)   // row_shr:8  -> lane 15 of each 16-lane row holds the row's first maximum
+#undef SR_DPP_STEP
+    a.d = v;
+    const int mine = idx;
+    b.i[0] = __builtin_amdgcn_readlane(a.i[0], 15);
+    b.i[1] = __builtin_amdgcn_readlane(a.i[1], 15);
+    v = b.d;
+    idx = __builtin_amdgcn_readlane(mine, 15);
+#pragma unroll
+    for (int r = 1; r < 4; r++) {
+        b.i[0] = __builtin_amdgcn_readlane(a.i[0], 16 * r + 15);
+        b.i[1] = __builtin_amdgcn_readlane(a.i[1], 16 * r + 15);
+        take(b.d, __builtin_amdgcn_readlane(mine, 16 * r + 15));
+    }
+}
+
 // Value of `x` held by lane (l ^ 32): one v_permlane32_swap.
 __device__ __forceinline__ float other_half(float x) {
     const unsigned u = __float_as_uint(x);

@@ -28,12 +28,15 @@ class GMMSet(object):
         self.gmms, self.y = [], []
         self._set = None
         self._set_key = None            # packed device copy of self.gmms, rebuilt when the list changes
+        self._open_set = None
+        self._open_set_key = None       # the same with the UBM in front (column 0): the batched open-set decision's set
 
     # ---- enrolment ----
     def _append(self, label, gmm):
         self.gmms.append(gmm)
         self.y.append(label)
         self._set = None
+        self._open_set = None
 
     def fit_new(self, x, label):
         """Train one model on the frames ``x`` (EM, or MAP adaptation when a UBM was given)."""
@@ -119,9 +122,40 @@ class GMMSet(object):
         _, winners = self._model_set().score(Batch.from_features(utterances))
         return [None if w < 0 else self.y[w] for w in winners]
 
+    def _open_model_set(self):
+        # [ubm] + speakers, the UBM as column 0; the same key discipline as _model_set, the UBM's state included
+        models = [self.ubm] + list(self.gmms)
+        key = tuple((id(g), getattr(g, "_version", 0)) for g in models)
+        if self._open_set is None or self._open_set_key != key:
+            self._open_set = ModelSet(models)
+            self._open_set_key = key
+        return self._open_set
+
+    def _reject_batch(self, X, threshold=None):
+        if self.ubm is None:
+            raise AssertionError("UBM must be given prior to conduct reject prediction.")
+        utterances = list(X)
+        if not utterances:
+            return np.zeros(0, np.int32), np.zeros(0)
+        _, labels, margins = self._open_model_set().score_open(Batch.from_features(utterances), 0,
+                                                                float(self.reject_threshold if threshold is None else threshold))
+        return labels, margins
+
+    def predict_with_reject_batch(self, X, threshold=None):
+        """``predict_with_reject`` for all utterances in ONE batch, the decision taken on the device
+        (``ModelSet.score_open`` over [UBM] + speakers): a list of labels, None for a rejected utterance.
+        ``threshold``: decide against this value for the call instead of ``reject_threshold``, which stays as it is."""
+        labels, _ = self._reject_batch(X, threshold)
+        return [None if w < 0 else self.y[w - 1] for w in labels]
+
+    def reject_margins(self, X):
+        """The per-frame margin of every utterance's best speaker over the UBM (what ``reject_threshold`` is compared with),
+        from the same batched pass; NaN for an utterance without frames."""
+        return self._reject_batch(X)[1]
+
     def predict_one_with_rejection(self, x):
         """Open-set decision (gmmset.py:69-81): per-frame margin of the best speaker over the UBM
-        below ``reject_threshold`` -> None."""
+        below ``reject_threshold`` -> None.  (``predict_with_reject_batch`` decides a whole list in one device pass.)"""
         if self.ubm is None:
             raise AssertionError("UBM must be given prior to conduct reject prediction.")
         n = float(len(x))
@@ -131,6 +165,7 @@ class GMMSet(object):
         return self.y[best] if margin >= self.reject_threshold else None
 
     def predict_with_reject(self, X):
+        """One utterance at a time, as the reference; ``predict_with_reject_batch`` is the batched form."""
         return [self.predict_one_with_rejection(x) for x in X]
 
 
@@ -142,15 +177,18 @@ class GMMSetPyGMM(GMMSet):
     # models travel through pickle as their text dumps (gmmset.py:101-105)
     def before_pickle(self):
         self._set = None
+        self._open_set = None
         self.__dict__.pop("_scratch", None)
         self.gmms = [m.dumps() for m in self.gmms]
 
     def after_pickle(self):
         self._set = None
+        self._open_set = None
         self.gmms = [GMM.loads(text) for text in self.gmms]
 
     def __getstate__(self):
         state = dict(self.__dict__)
         state["_set"] = None
+        state["_open_set"] = None
         state.pop("_scratch", None)
         return state

@@ -101,14 +101,32 @@ class ModelInterface(object):
         if self.verbose:
             print(time.time() - start, " seconds")
 
-    def predict(self, fs, signal):
-        """return a label (name)"""
+    def predict(self, fs, signal, reject_threshold=None):
+        """return a label (name).  Extension: ``reject_threshold`` (a number) takes the open-set decision instead -- None when
+        the best speaker's per-frame margin over the UBM is below it (``GMMSet.predict_with_reject_batch``: decided on the
+        device); only a model enrolled from a UBM can."""
+        if reject_threshold is not None:
+            self._check_reject()
         try:
             feat = self._features(fs, signal)
         except Exception:
             print(tb.format_exc(), file=sys.stderr)
             return None
-        return self.gmmset.predict_one(feat)
+        if reject_threshold is None:
+            return self.gmmset.predict_one(feat)
+        return self.gmmset.predict_with_reject_batch([feat], threshold=float(reject_threshold))[0]
+
+    def _check_reject(self):
+        if getattr(self, "covariance_type", "diag") == "full" or getattr(self.gmmset, "ubm", None) is None:
+            raise ValueError("a reject threshold needs a model enrolled from a UBM (ModelInterface.UBM_MODEL_FILE at training "
+                             "time, diagonal models): this one has none")
+
+    def predict_many_with_reject(self, items, reject_threshold):
+        """Extension: [(fs, signal), ...] -> labels by the open-set decision of ``predict(reject_threshold=)``, every utterance
+        scored and decided in ONE batch on one GPU (``GMMSet.predict_with_reject_batch``)."""
+        self._check_reject()
+        feats = [self._features(fs, sig) for fs, sig in items]
+        return self.gmmset.predict_with_reject_batch(feats, threshold=float(reject_threshold))
 
     def predict_many(self, items, gpus=1):
         """Extension: [(fs, signal), ...] -> labels, every utterance scored in one batch.  ``gpus`` != 1
