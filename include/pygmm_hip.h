@@ -203,8 +203,15 @@ int sr_mfcc_frame_shift(SRMfcc *m);
 int64_t sr_mfcc_num_frames(SRMfcc *m, int64_t n_samples);   /* MFCC.py:57; 0 if too short (:56) */
 int sr_mfcc_tables(SRMfcc *m, double *window /*[L]*/, double *melbank /*[n_filters][fft/2+1]*/,
                    double *dct /*[n_ceps][n_filters]*/);    /* host float64 tables, for tests */
+/* What a pass of n_frames > 0 frames launches (csrc/mfcc_plan.cpp), for tests: precision 2 / 0 and generic 0 / 1 as the options
+ * mfcc_precision and mfcc_generic take them, pcm_kind 0 = int16, 1 = float32; n_cu > 0: that many compute units (host only, no GPU
+ * needed), n_cu <= 0: the current device's.  Writes 16 fields (n_out >= 16) and returns 16: kernel (0 fp32 fast, 1 fp32 generic,
+ * 2 float64 fast, 3 float64 generic), N1, NZ1, mel preset, waves per workgroup, dynamic LDS bytes, frames per wave, grid,
+ * cmvn_delta_kernel's column padding, floats of the padded mel table, its four pass lengths, the largest float index of the power
+ * spectrum a padded sweep reads, the number of empty mel bands. */
+int sr_mfcc_plan(SRMfcc *m, int precision, int generic, int pcm_kind, int64_t n_frames, int n_cu, int32_t *out, int n_out);
 /* PCM batch -> feature batch (CMVN per utterance, then delta order nd in {0,1,2});
- * cmvn=0 skips the normalisation (raw cepstra, for tests). Returns a new device batch. */
+ * cmvn=0 skips the normalisation (raw cepstra and their plain differences, for tests). Returns a new device batch. */
 SRBatch *sr_mfcc_extract_batch(SRMfcc *m, SRBatch *pcm, int nd, int cmvn);
 
 /* Fused serving step on resident inputs: PCM batch -> MFCC -> CMVN/delta -> scoring -> argmax. */

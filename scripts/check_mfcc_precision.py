@@ -29,7 +29,7 @@ for generic in (0, 1):
             print("generic %d precision %d speaker %3d: statics max %.2e mean %.2e | 39 dims max %.2e mean %.2e | finite %s"
                   % (generic, mode, s, d[:, :13].max(), d[:, :13].mean(), d.max(), d.mean(), bool(np.all(np.isfinite(got)))), flush=True)
 _lib.set_option("mfcc_generic", 0)
-# other shapes through the float64 kernels (8 kHz preset, FFT 512 -> generic float64)
+# other shapes through the float64 kernels (8 kHz: run-time mel sweep lengths, FFT 512 -> generic float64)
 _lib.set_option("mfcc_precision", 2)
 for fs2, kw in ((8000, {}), (16000, {}), (16000, dict(win_length_ms=25, win_shift_ms=10, FFT_SIZE=512)), (44100, dict(win_length_ms=25, win_shift_ms=10))):
     pcm = synth.synth_speech(50, 2.0, fs2)

@@ -27,7 +27,7 @@ EXT_SYMBOLS = [
     "sr_batch_from_features", "sr_batch_update_pcm", "sr_batch_reset_pcm", "sr_batch_reset_features", "sr_batch_free", "sr_batch_num_utterances", "sr_batch_num_rows",
     "sr_batch_dim", "sr_batch_offsets", "sr_batch_download", "sr_score_batch_set",
     "sr_mfcc_create", "sr_mfcc_set_lpc", "sr_mfcc_free", "sr_mfcc_frame_len", "sr_mfcc_frame_shift",
-    "sr_mfcc_num_frames", "sr_mfcc_tables", "sr_mfcc_extract_batch", "sr_predict_pcm_batch",
+    "sr_mfcc_num_frames", "sr_mfcc_tables", "sr_mfcc_plan", "sr_mfcc_extract_batch", "sr_predict_pcm_batch",
     "sr_train_f32", "sr_profile_enable", "sr_profile_reset", "sr_profile_get", "sr_set_option",
     "sr_last_score_kernel", "sr_last_em_stats_engine", "sr_ltsd_num_windows", "sr_ltsd_noise_spectrum", "sr_ltsd_compute", "sr_stream_create", "sr_stream_submit", "sr_stream_collect", "sr_stream_free",
     "sr_multi_create", "sr_multi_free", "sr_multi_slots", "sr_multi_slot_device", "sr_multi_predict_pcm",
@@ -140,6 +140,7 @@ def lib():
         "sr_mfcc_frame_shift": (i32, [vp]),
         "sr_mfcc_num_frames": (i64, [vp, i64]),
         "sr_mfcc_tables": (i32, [vp, dp, dp, dp]),
+        "sr_mfcc_plan": (i32, [vp, i32, i32, i32, i64, i32, C.POINTER(C.c_int32), i32]),
         "sr_mfcc_extract_batch": (vp, [vp, vp, i32, i32]),
         "sr_predict_pcm_batch": (i32, [vp, vp, vp, i32, dp, C.POINTER(i32), i32]),
         "sr_train_f32": (i32, [vp, vp, fp, C.c_long, i32, C.POINTER(Parameter), C.c_long]),
@@ -340,6 +341,24 @@ def mfma_streamed_probe(ms_target: float = 50.0):
     t, f = C.c_double(0.0), C.c_double(0.0)
     check(lib().sr_mfma_streamed_probe(C.c_double(ms_target), C.byref(t), C.byref(f)), "sr_mfma_streamed_probe")
     return float(t.value), float(f.value)
+
+
+MFCC_KERNELS = ("fp32-fast", "fp32-generic", "f64-fast", "f64-generic")
+
+
+def mfcc_plan(handle, precision: int = 2, generic: int = 0, pcm_kind: int = 0, n_frames: int = 1, n_cu: int = 0) -> dict:
+    """What a pass of `n_frames` frames over the extractor `handle` (an SRMfcc *) launches (csrc/mfcc_plan.cpp): kernel and its
+    template arguments, workgroup shape, LDS bytes, frames per wave, grid, cmvn_delta_kernel's column padding, and the padded mel
+    layout.  n_cu > 0: that many compute units, no GPU needed; n_cu <= 0: the current device's."""
+    v = (C.c_int32 * 16)()
+    check(lib().sr_mfcc_plan(handle, int(precision), int(generic), int(pcm_kind), int(n_frames), int(n_cu), v, 16), "sr_mfcc_plan")
+    names = ("kernel", "N1", "NZ1", "preset", "wpb", "lds", "frames_per_wave", "grid", "cp", "pad_floats")
+    d = dict(zip(names, (int(x) for x in v[:10])))
+    d["kernel"] = MFCC_KERNELS[d["kernel"]]
+    d["pass_len"] = [int(x) for x in v[10:14]]
+    d["max_read"] = int(v[14])
+    d["n_empty"] = int(v[15])
+    return d
 
 
 def last_score_kernel() -> str:

@@ -9,6 +9,7 @@
 #include "gmm_full.hpp"
 #include "gmm_model.hpp"
 #include "mfcc.hpp"
+#include "mfcc_plan.hpp"
 #include "score.hpp"
 
 #include <algorithm>
@@ -684,10 +685,28 @@ int sr_mfcc_tables(SRMfcc *m, double *window, double *melbank, double *dct) {
     SR_CATCH(-1)
 }
 
+int sr_mfcc_plan(SRMfcc *m, int precision, int generic, int pcm_kind, int64_t n_frames, int n_cu, int32_t *out, int n_out) {
+    SR_TRY
+    if (!m || !out) fail("null argument");
+    if (precision != 0 && precision != 2) fail("mfcc_precision must be 0 or 2");
+    if (pcm_kind != 0 && pcm_kind != 1) fail("PCM kind: 0 = int16, 1 = float32");      // (selects the PcmT instance only: no decision hangs on it)
+    if (n_out < 16) fail("sr_mfcc_plan writes 16 fields");
+    if (n_cu <= 0) {
+        ensure_device();
+        n_cu = ctx().n_cu;
+    }
+    const MelLayout mel = mel_layout(*m);
+    const MfccPlan p = plan_mfcc(*m, mel, precision, generic != 0, n_frames, n_cu);
+    const int32_t v[16] = {p.kernel, p.n1, p.nz1, p.preset, p.wpb, (int32_t)p.lds, (int32_t)std::min<int64_t>(p.frames_per_wave, INT32_MAX), p.grid, p.cp,
+                           mel.pad_floats, mel.pass_len[0], mel.pass_len[1], mel.pass_len[2], mel.pass_len[3], mel.max_read, mel.n_empty};
+    std::memcpy(out, v, sizeof v);
+    return 16;
+    SR_CATCH(-1)
+}
+
 SRBatch *sr_mfcc_extract_batch(SRMfcc *m, SRBatch *pcm, int nd, int cmvn) {
     SR_TRY
     if (!m || !pcm) fail("null argument");
-    if (!cmvn && nd != 0) fail("raw cepstra (cmvn=0) come without deltas");
     auto out = std::make_unique<SRBatch>();
     mfcc_extract_batch(*m, *pcm, nd, cmvn, *out);
     return out.release();

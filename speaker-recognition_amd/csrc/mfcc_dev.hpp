@@ -4,6 +4,7 @@
 
 #include "common.hpp"
 #include "mfcc.hpp"
+#include "mfcc_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -33,20 +34,6 @@ struct MelRuns {
     int pass_len[4];        // padded run length of the pass (multiple of 16)
 };
 
-constexpr int MFCC_DCT_LD = 80;     // row stride of the zero-padded DCT table in LDS: 320 B = 64 B mod 256, so the 4 rows x 4
-                                    // parts of a 16-lane ds_read_b128 phase cover 16 distinct 16-byte windows (64 floats would put
-                                    // all 16 rows on the same banks)
-constexpr int WAVE_SLAB_C = 1088;   // complex slots per wave: max(16*68, 64*17, 1024)
-
-// Mel sweep lengths (16-bin steps per pass of 16 bands) of the two common filterbanks, known at
-// compile time so that the sweep unrolls completely and its LDS reads are issued ahead of their use;
-// preset 0 takes the lengths from MelRuns at run time (any other fs / n_filters).
-__host__ __device__ constexpr int mel_preset_steps(int preset, int pass) {
-    return preset == 1 ? (pass == 0 ? 2 : pass == 1 ? 3 : pass == 2 ? 6 : 7)      // fs 16 kHz, 50 filters, FFT 2048
-         : preset == 2 ? (pass == 0 ? 2 : pass == 1 ? 4 : 6)                       // fs  8 kHz, 50 filters, FFT 2048
-                       : 0;
-}
-
 // float64 copies of the host tables for the float64-spectrum path (MFCC.py computes in float64 throughout)
 struct MfccDev64 {
     const double *window;     // [L]
@@ -66,9 +53,7 @@ struct MfccDeviceTables {
     DevBuf<int> mel_row, mel_col, mel_col0, mel_cnt;
     DevBuf<float> mel_pad;
     int device = -1;
-    int nnz = 0, max_cnt = 0;
-    int pass_base[4] = {0, 0, 0, 0}, pass_len[4] = {0, 0, 0, 0}, pad_floats = 0;
-    bool runs_contiguous = true;
+    MelLayout mel;          // what the tables were laid out by (mfcc_plan.cpp)
 };
 
 MfccDev upload_tables(SRMfcc &m);           // creates the calling device's tables on first use
@@ -77,7 +62,7 @@ inline MfccDeviceTables &device_tables(SRMfcc &m) { return *std::static_pointer_
 
 // mfcc_f64.hip
 bool mfcc_force_generic();
-void mfcc_launch_f64(SRMfcc &m, const MfccDev &dev, int pcm_kind, const void *pcm, const int64_t *d_pcm_off, const int64_t *d_raw_off,
+void mfcc_launch_f64(SRMfcc &m, const MfccPlan &plan, const MfccDev &dev, int pcm_kind, const void *pcm, const int64_t *d_pcm_off, const int64_t *d_raw_off,
                      int n_utt, int64_t n_frames, float *raw);
 
 }  // namespace sr

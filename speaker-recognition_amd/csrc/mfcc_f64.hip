@@ -140,8 +140,7 @@ __device__ __forceinline__ double ln_pos_f32(float e) {
     return fma((double)ex, ln2, 2.0 * s * p);
 }
 
-constexpr int F64_WIN_BYTES = 4160;               // 520 float64 window taps in LDS (frames of <= 512 samples)
-constexpr int F64_WPB = 8;                       // waves per workgroup: 8 x 17 KB of exchange slab + the mel table fill a CU's LDS
+// (F64_WIN_BYTES, F64_WPB: mfcc_plan.hpp -- the plan sizes the LDS by them)
 constexpr int F64_U_ELEMS = 576;                 // half-spectrum exchange: [8][64] float64 complex (+ lane 0's displaced read)
 constexpr int F64_PBUF_BYTE = F64_U_ELEMS * 16;  // power spectrum, fp32[1100]
 constexpr int F64_SE_BYTE = F64_PBUF_BYTE + 1100 * 4;    // band energies fp32[64]
@@ -526,48 +525,24 @@ void mfcc_frames_f64_kernel(const PcmT *__restrict__ pcm, const int64_t *__restr
     }
 }
 
-void mfcc_launch_f64(SRMfcc &m, const MfccDev &dev, int pcm_kind, const void *pcm, const int64_t *d_pcm_off, const int64_t *d_raw_off,
-                     int n_utt, int64_t n_frames, float *raw) {
+void mfcc_launch_f64(SRMfcc &m, const MfccPlan &plan, const MfccDev &dev, int pcm_kind, const void *pcm, const int64_t *d_pcm_off,
+                     const int64_t *d_raw_off, int n_utt, int64_t n_frames, float *raw) {
     auto &tabs = device_tables(m);
     const MfccDev64 dev64 = device_tables_f64(m);
-    const size_t mel_bytes = ((size_t)tabs.pad_floats * 4 + 31) & ~(size_t)31;
-    const size_t lds_fast = mel_bytes + F64_WIN_BYTES + (size_t)F64_WPB * WAVE_SLAB_C * sizeof(d2);
-    const bool fast = m.fft_size == 2048 && m.frame_len <= 512 && tabs.runs_contiguous && m.n_ceps <= 16 &&
-                      lds_fast <= (size_t)160 * 1024 && !mfcc_force_generic();
-    if (fast) {
+    const int grid = plan.grid;
+    if (plan.kernel == MFCC_F64_FAST) {
         MelRuns mr;
         mr.col0 = tabs.mel_col0.p;
         mr.pad_val = tabs.mel_pad.p;
-        mr.pad_floats = tabs.pad_floats;
+        mr.pad_floats = tabs.mel.pad_floats;
         for (int ps = 0; ps < 4; ps++) {
-            mr.pass_base[ps] = tabs.pass_base[ps];
-            mr.pass_len[ps] = tabs.pass_len[ps];
+            mr.pass_base[ps] = tabs.mel.pass_base[ps];
+            mr.pass_len[ps] = tabs.mel.pass_len[ps];
         }
         // one contiguous frame range per wave; one 8-wave workgroup per CU (its LDS)
-        // Frames per wave: the chip holds ONE round of waves at a time (a workgroup per CU), every wave walks its frames one after the
-        // other, so a pass costs rounds x frames per wave.  Of 1..4 rounds the cheapest (64 utterances x 300
-        // frames: one round of 10 frames per wave, not 1.17 rounds of 8 -- 0.108 -> 0.07 ms); large batches end up with four rounds
-        // of equal waves, which evens out what the scheduler does to them.
-        const int64_t one_round = (int64_t)ctx().n_cu * F64_WPB;
-        int64_t frames_per_wave = 1, best_cost = -1;
-        for (int64_t r = 1; r <= 4; r++) {
-            const int64_t fpw = std::max<int64_t>(1, (n_frames + r * one_round - 1) / (r * one_round));
-            const int64_t waves = (n_frames + fpw - 1) / fpw;
-            const int64_t cost = ((waves + one_round - 1) / one_round) * fpw;
-            // (more rounds of shorter waves are preferred within 2 % while a wave still has >= 32 frames to amortise its start on)
-            if (best_cost < 0 || cost < best_cost - best_cost / 50 || (cost <= best_cost + best_cost / 50 && fpw >= 32)) {
-                best_cost = cost;
-                frames_per_wave = fpw;
-            }
-        }
-        const int64_t n_waves = (n_frames + frames_per_wave - 1) / frames_per_wave;
-        const int grid = (int)((n_waves + F64_WPB - 1) / F64_WPB);
-        int preset = 0;
-        for (int pr = 1; pr <= 2 && !preset; pr++) {
-            bool same = true;
-            for (int ps = 0; ps < 4; ps++) same = same && tabs.pass_len[ps] == 16 * mel_preset_steps(pr, ps);
-            if (same) preset = pr;
-        }
+        const size_t lds_fast = plan.lds;
+        const int64_t frames_per_wave = plan.frames_per_wave;
+        const int preset = plan.preset;
 #define SR_LAUNCH_F64(PT, MPV)                                                                              \
     do {                                                                                                     \
         auto kern = mfcc_frames_fft2048_f64_kernel<PT, MPV>;                                                 \
@@ -577,21 +552,16 @@ void mfcc_launch_f64(SRMfcc &m, const MfccDev &dev, int pcm_kind, const void *pc
     } while (0)
 #define SR_LAUNCH_F64_P(PT)                                                                                 \
     do {                                                                                                     \
-        if (preset == 1) SR_LAUNCH_F64(PT, 1); else if (preset == 2) SR_LAUNCH_F64(PT, 2); else SR_LAUNCH_F64(PT, 0); \
+        if (preset == 1) SR_LAUNCH_F64(PT, 1); else SR_LAUNCH_F64(PT, 0); \
     } while (0)
         if (pcm_kind == SRBatch::PCM16) SR_LAUNCH_F64_P(int16_t); else SR_LAUNCH_F64_P(float);
 #undef SR_LAUNCH_F64_P
 #undef SR_LAUNCH_F64
         return;
     }
-    const int nc = m.fft_size / 2;
-    // waves per workgroup: as many as the LDS takes (float64 twiddles + two slabs per wave)
-    auto lds_for = [&](int w) { return (size_t)nc * sizeof(d2) * (1 + 2 * w) + (size_t)w * 64 * sizeof(double); };
-    const int wpb = lds_for(4) <= (size_t)160 * 1024 ? 4 : lds_for(2) <= (size_t)160 * 1024 ? 2 : 1;
-    const size_t lds = lds_for(wpb);
-    const int64_t blocks_needed = (n_frames + wpb - 1) / wpb;
-    const int blocks_per_cu = std::max<int>(1, (int)(160 * 1024 / lds));
-    const int grid = (int)std::min<int64_t>(blocks_needed, (int64_t)ctx().n_cu * std::min(blocks_per_cu, 8));
+    if (plan.kernel != MFCC_F64_GENERIC) fail("MFCC plan names no float64 kernel");
+    const int wpb = plan.wpb;
+    const size_t lds = plan.lds;
 #define SR_LAUNCH_G64(PT, W)                                                                                \
     do {                                                                                                     \
         auto kern = mfcc_frames_f64_kernel<PT, W>;                                                           \

@@ -1,7 +1,9 @@
-// Host-side checks of csrc/gmm_model.cpp and csrc/score_plan.cpp (the dispatcher's decisions: mode "plan"; model packers, text format, tail packing, the MFCC kernels' mel sweep starts), built by tests/test_host_sanitizers.py with -fsanitize=address,undefined (and once
+// Host-side checks of csrc/gmm_model.cpp, csrc/score_plan.cpp (the dispatcher's decisions: mode "plan") and csrc/mfcc_plan.cpp (the MFCC
+// stage's table layout and launch decisions: mode "mfcc"); model packers, text format, tail packing, the MFCC kernels' mel sweep starts), built by tests/test_host_sanitizers.py with -fsanitize=address,undefined (and once
 // with -fsanitize=thread): the model packers (every layout, threaded and not), the text parser on mutated model texts, and
 // the printf / strtod-free number conversions against libc.  Test infrastructure: not part of lib/pygmm.so.
 #include "gmm_model.hpp"
+#include "mfcc_plan.hpp"
 #include "score_plan.hpp"
 
 #include <cmath>
@@ -347,7 +349,112 @@ static int check_plan() {
     return bad;
 }
 
+// ---- mode "mfcc": the MFCC stage's mel-table layout and launch decisions (csrc/mfcc_plan.cpp) ----
+// Pinned rows: what upload_tables / mfcc_extract_with / mfcc_launch_f64 computed inline before the plan became a function of its
+// own, on 256 compute units and 100 frames (tests/mfcc_cases.py holds the full table; these are its corner stones).  Then a sweep
+// over every FFT size and bank width for the invariants the kernels rely on.
+struct MfccRow {
+    double fs, win_ms, shift_ms;
+    int fft, n_filters, n_ceps;
+    int k2, wpb2, k0, n1, nz1, preset, wpb0, cp, pad_floats, pass_len[4], max_read;
+    long lds0, lds2;
+};
+static const MfccRow kMfccRows[] = {
+    // the reference's defaults: the 16 kHz lengths are mel preset 1; the 8 kHz bank has 32/48/96/96 and takes the run-time sweep
+    {16000, 32, 16, 2048, 50, 13, MFCC_F64_FAST, 8, MFCC_F32_FAST, 16, 4, 1, 12, 16, 4608, {32, 48, 96, 112}, 1031, 144384, 161856},
+    {8000, 32, 16, 2048, 50, 13, MFCC_F64_FAST, 8, MFCC_F32_FAST, 16, 4, 0, 12, 16, 4352, {32, 48, 96, 96}, 1031, 143360, 160832},
+    // a 2-filter bank: 14592 padded floats -- 4-wave fp32 workgroups and the generic float64 kernel, both because of LDS
+    {16000, 25, 10, 2048, 2, 1, MFCC_F64_GENERIC, 4, MFCC_F32_FAST, 16, 4, 0, 4, 16, 14592, {912, 0, 0, 0}, 1027, 106496, 149504},
+    // 22050 Hz: 5120 padded floats -- 16 over what the float64 fast kernel has room for; fp32 keeps 12 waves
+    {22050, 20, 10, 2048, 50, 13, MFCC_F64_GENERIC, 4, MFCC_F32_FAST, 16, 4, 0, 12, 16, 5120, {32, 48, 112, 128}, 1035, 146432, 149504},
+    // frames of 513 samples: the NZ1 = 16 instance, 4 waves
+    {16000, 32.0625, 16, 2048, 50, 13, MFCC_F64_GENERIC, 4, MFCC_F32_FAST, 16, 16, 1, 4, 16, 4608, {32, 48, 96, 112}, 1031, 91136, 149504},
+    // 17 cepstra: both generic kernels, 32 CMVN columns
+    {16000, 32, 16, 2048, 50, 17, MFCC_F64_GENERIC, 4, MFCC_F32_GENERIC, 0, 0, 0, 4, 32, 4608, {32, 48, 96, 112}, 1031, 74752, 149504},
+    // FFT 1024 with frames of 640 samples (NZ1 8), FFT 512, FFT 4096 (one float64 wave per workgroup)
+    {16000, 40, 20, 1024, 24, 13, MFCC_F64_GENERIC, 4, MFCC_F32_FAST, 8, 8, 0, 4, 16, 2560, {48, 112, 0, 0}, 515, 66560, 75776},
+    {16000, 25, 10, 512, 64, 13, MFCC_F64_GENERIC, 4, MFCC_F32_FAST, 4, 4, 0, 12, 16, 1280, {16, 16, 16, 32}, 267, 118784, 38912},
+    {16000, 25, 10, 4096, 50, 13, MFCC_F64_GENERIC, 1, MFCC_F32_GENERIC, 0, 0, 0, 4, 16, 8960, {48, 96, 192, 224}, 2059, 148480, 98816},
+};
+
+static int check_mfcc_plan() {
+    const int n_cu = 256;
+    int bad = 0, row = 0;
+    for (const MfccRow &r : kMfccRows) {
+        SRMfcc m(r.fs, r.win_ms, r.shift_ms, r.fft, r.n_filters, r.n_ceps, 0.95);
+        const MelLayout mel = mel_layout(m);
+        const MfccPlan p2 = plan_mfcc(m, mel, 2, false, 100, n_cu), p0 = plan_mfcc(m, mel, 0, false, 100, n_cu);
+        const bool ok = p2.kernel == r.k2 && p2.wpb == r.wpb2 && p0.kernel == r.k0 && p0.n1 == r.n1 && p0.nz1 == r.nz1 && p0.preset == r.preset &&
+                        p0.wpb == r.wpb0 && p0.cp == r.cp && p2.cp == r.cp && mel.pad_floats == r.pad_floats &&
+                        std::memcmp(mel.pass_len, r.pass_len, sizeof r.pass_len) == 0 && mel.max_read == r.max_read &&
+                        (long)p0.lds == r.lds0 && (long)p2.lds == r.lds2 && mel.n_empty == 0;
+        if (!ok) {
+            printf("mfcc row %d: k2 %d w2 %d k0 %d N1 %d NZ1 %d preset %d w0 %d cp %d pad %d len {%d, %d, %d, %d} max_read %d lds %zu %zu\n", row,
+                   p2.kernel, p2.wpb, p0.kernel, p0.n1, p0.nz1, p0.preset, p0.wpb, p0.cp, mel.pad_floats, mel.pass_len[0], mel.pass_len[1],
+                   mel.pass_len[2], mel.pass_len[3], mel.max_read, p0.lds, p2.lds);
+            bad++;
+        }
+        // forced generic: never a fast kernel
+        if (plan_mfcc(m, mel, 2, true, 100, n_cu).kernel != MFCC_F64_GENERIC || plan_mfcc(m, mel, 0, true, 100, n_cu).kernel != MFCC_F32_GENERIC) bad++;
+        row++;
+    }
+    {   // frames per wave of the two fast kernels on the default extractor: one round is 256 x 12 (fp32) or 256 x 8 (float64) waves
+        SRMfcc m(16000, 32, 16, 2048, 50, 13, 0.95);
+        const MelLayout mel = mel_layout(m);
+        const struct { int64_t n; int fpw0, fpw2; } want[] = {{1, 1, 1}, {3072, 1, 2}, {3073, 2, 2}, {2048, 1, 1}, {2049, 1, 2},
+                                                               {8 * 3072 + 1, 8, 13}, {40 * 3072, 10, 60}, {200 * 2048, 34, 50}};
+        for (const auto &w : want) {
+            const MfccPlan p0 = plan_mfcc(m, mel, 0, false, w.n, n_cu), p2 = plan_mfcc(m, mel, 2, false, w.n, n_cu);
+            if (p0.frames_per_wave != w.fpw0 || p2.frames_per_wave != w.fpw2) {
+                printf("mfcc frames per wave at %lld frames: fp32 %lld, float64 %lld\n", (long long)w.n, (long long)p0.frames_per_wave, (long long)p2.frames_per_wave);
+                bad++;
+            }
+        }
+    }
+    // every FFT size x bank width x a few rates and frame lengths: the invariants the kernels rely on
+    const double rates[] = {8000, 11025, 16000, 22050, 44100, 48000};
+    for (int fft = 32; fft <= 4096; fft *= 2)
+        for (int B = 2; B <= 64; B++)
+            for (double fs : rates) {
+                const int L = std::min(fft, (int)(0.02 * fs));
+                const int C = std::min(B - 1, B % 3 == 0 ? 17 : 13);
+                SRMfcc m(fs, (L + 0.5) * 1000.0 / fs, (L / 2 + 0.5) * 1000.0 / fs, fft, B, C, 0.97);
+                if (m.frame_len != L) return printf("mfcc sweep: frame of %d samples, wanted %d\n", m.frame_len, L), 1;
+                const MelLayout mel = mel_layout(m);
+                std::vector<char> used((size_t)std::max(4, mel.pad_floats), 0);
+                for (int b = 0; b < B; b++) {
+                    if (mel.cnt[b] == 0) continue;
+                    if (mel.start[b] < 0 || (mel.start[b] & 3) || mel.start[b] > mel.first[b]) return printf("mfcc sweep: start of band %d\n", b), 2;
+                    const int lead = mel.first[b] - mel.start[b];
+                    if (lead + mel.cnt[b] > mel.pass_len[b / 16]) return printf("mfcc sweep: run of band %d leaves its pass\n", b), 3;
+                    for (int e = 0; e < mel.pass_len[b / 16]; e++) {
+                        const size_t i = mel.pad_index(b, e);
+                        if (i >= used.size() || used[i]++) return printf("mfcc sweep: padded slot of band %d, element %d\n", b, e), 4;
+                    }
+                }
+                if (mel.runs_contiguous && mel.max_read >= MFCC_PBUF_FLOATS) return printf("mfcc sweep: sweep reads float %d\n", mel.max_read), 5;
+                for (int precision = 0; precision <= 2; precision += 2)
+                    for (int64_t n : {(int64_t)1, (int64_t)5000, (int64_t)300000}) {
+                        const MfccPlan p = plan_mfcc(m, mel, precision, false, n, n_cu);
+                        const bool fast = p.kernel == MFCC_F32_FAST || p.kernel == MFCC_F64_FAST;
+                        if (p.lds > (size_t)MFCC_LDS_BYTES || p.grid <= 0 || p.wpb <= 0) return printf("mfcc sweep: launch shape\n"), 6;
+                        if (fast && (int64_t)p.grid * p.wpb * p.frames_per_wave < n) return printf("mfcc sweep: frames left over\n"), 7;
+                        if (fast && ((int64_t)p.grid - 1) * p.wpb * p.frames_per_wave >= n) return printf("mfcc sweep: an idle workgroup\n"), 8;
+                        if (fast && (C > 16 || !mel.runs_contiguous)) return printf("mfcc sweep: fast kernel outside its range\n"), 9;
+                        if (p.preset != 0 && (p.n1 != 16 || mel.pass_len[0] != 32 || mel.pass_len[1] != 48 || mel.pass_len[2] != 96 || mel.pass_len[3] != 112))
+                            return printf("mfcc sweep: preset\n"), 10;
+                    }
+            }
+    return bad;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "mfcc") == 0) {
+        const int bad = check_mfcc_plan();
+        if (bad) return printf("mfcc plan: %d\n", bad), 90;
+        printf("host checks ok\n");
+        return 0;
+    }
     if (argc > 1 && std::strcmp(argv[1], "plan") == 0) {
         const int bad = check_plan();
         if (bad) return printf("plan: %d cases differ\n", bad), 80;

@@ -180,7 +180,7 @@ def test_no_hot_kernel_spills(built_lib):
     # the float64-spectrum kernel (the feature stage's default since round 5): 16 float64 complex points per lane + the butterflies'
     # temporaries fill the 256 registers two waves per SIMD leave each other; the int16 variants must stay out of scratch
     f64 = {n: r for n, r in _kernel_resources("mfcc_f64").items() if "mfcc_frames_fft2048_f64_kernelIs" in n}
-    assert len(f64) == 3
+    assert len(f64) == 2                          # mel presets 0 and 1: every instance there is
     for name, r in f64.items():
         assert r["scratch"] == 0 and r["occupancy"] >= 2, (name, r)
 

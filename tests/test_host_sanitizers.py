@@ -1,4 +1,5 @@
-"""csrc/gmm_model.cpp (text format, number conversions, every packer) and csrc/score_plan.cpp (the dispatcher) under AddressSanitizer + UBSan, and the threaded
+"""csrc/gmm_model.cpp (text format, number conversions, every packer), csrc/score_plan.cpp (the dispatcher) and csrc/mfcc_plan.cpp (the MFCC
+stage's table layout and launch decisions) under AddressSanitizer + UBSan, and the threaded
 packers under ThreadSanitizer: tests/host/host_checks.cpp, built here with g++ (host code only, no GPU, no HIP runtime)."""
 import os
 import shutil
@@ -14,7 +15,7 @@ def _build_and_run(tmp_path, flags, args, env=None):
     exe = str(tmp_path / "host_checks")
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer", *flags, "-I", CSRC, "-I", "/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", os.path.join(ROOT, "tests", "host", "host_checks.cpp"), os.path.join(CSRC, "gmm_model.cpp"),
-           os.path.join(CSRC, "score_plan.cpp"),
+           os.path.join(CSRC, "score_plan.cpp"), os.path.join(CSRC, "mfcc_plan.cpp"),
            "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-2000:]
@@ -33,6 +34,15 @@ def test_score_plan_under_asan_ubsan(tmp_path):
     """The dispatcher's decisions (engine, shapes, model groups) on sets packed by the library's own pack_model_set, against the
     values recorded from the commit before the plan became a function of its own (tests/host/host_checks.cpp, mode "plan")."""
     _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], ["plan"],
+                   env={"ASAN_OPTIONS": "detect_leaks=1"})
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_mfcc_plan_under_asan_ubsan(tmp_path):
+    """The MFCC stage's mel-table layout and launch decisions (kernel, template arguments, workgroup shape, LDS, frames per wave)
+    against the values its launchers computed inline before, and the layout's invariants over every FFT size and bank width
+    (tests/host/host_checks.cpp, mode "mfcc")."""
+    _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], ["mfcc"],
                    env={"ASAN_OPTIONS": "detect_leaks=1"})
 
 
