@@ -183,6 +183,28 @@ int64_t sr_batch_num_rows(SRBatch *b);           /* samples (PCM) or frames (fea
 int sr_batch_dim(SRBatch *b);                    /* 0 for PCM */
 int sr_batch_offsets(SRBatch *b, int64_t *offsets_out /* [U+1] */);
 int sr_batch_download(SRBatch *b, float *out);   /* features -> host, [rows][dim] */
+int sr_batch_download_pcm16(SRBatch *b, int16_t *out);   /* PCM16 batches -> host, [rows] */
+
+/* Energy-threshold silence removal (csrc/silence.hip), the reference's src/filters/silence.py:11-50 -- what its corpus
+ * preparation applies to every recording -- on every utterance of a PCM16 batch; the result is a new PCM16 batch on the same
+ * device, fit for sr_mfcc_extract_batch / sr_predict_pcm_batch without a host round trip.  Per utterance of n samples, with
+ * L = int(frame_duration * fs) and S = int(frame_shift * fs): A = (sum x^2) / n; from i = 0 while i < n the frame x[i : i + L]
+ * (clipped at n, len samples) is silent when (sum frame^2) / len < A * perc -- exact integer sums, the comparison strict and in
+ * float64 -- and i += L; otherwise its first min(S, len) samples are appended and i += S.  Bit-identical to the reference for
+ * int16 input (the reference's defaults: 0.02, 0.01, 0.15).  An utterance may come out with 0 samples (perc >= 1); the feature
+ * stage gives it 0 frames and the fused calls argmax -1.
+ * kept_out: [U] kept samples per utterance, or NULL.  NULL + sr_last_error() on refusal: a PCMF32 or FEATURES batch, a batch
+ * without utterances, an utterance without samples, L < 1 or S < 1 (the reference loops forever or raises there).
+ * sr_set_option("silence_block", B): positions (multiples of gcd(L, S) samples) per block of the walk, 0 = automatic. */
+SRBatch *sr_silence_remove_batch(SRBatch *pcm, double fs, double frame_duration, double frame_shift, double perc,
+                                 int64_t *kept_out);
+/* What such a call decides for a longest utterance of max_samples (csrc/silence_plan.cpp; host only, no GPU needed), for tests.
+ * Writes 12 fields (n_out >= 12; values above INT32_MAX saturate) and returns 12, -1 on refusal: L, S, g = gcd(L, S),
+ * E = entries of a block's transfer map = min(max(L, S) / g, positions), B = positions per block, blocks of that utterance,
+ * variant (0: a lane per (block, entry), several blocks per workgroup; 1: E above the workgroup, lanes loop over the entries),
+ * blocks per workgroup, kept frames a block can list, grid of the maps launch for that utterance alone, lanes per position of
+ * the energy kernel, positions of that utterance. */
+int sr_silence_plan(double fs, double frame_duration, double frame_shift, int64_t max_samples, int32_t *out, int n_out);
 
 /* Score every utterance of a feature batch against every model of the set in one fused pass:
  * sums_out[U][S] = sum_t LL_s(x_t) (double), argmax_out[U] = first maximum (gmmset.py:62-64),
@@ -303,6 +325,7 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    node, intersected with the mask the thread already has),
  *   "multi_merge_same_device" 0: slots that share a device get a host thread each (default 1: one queue per device).
  *   "full_fit_batch_bytes" the workspace bound, in bytes (>= 1; default 1 GiB), of a group of speakers in sr_fullgmm_fit_batch.
+ *   "silence_block"  positions per block of sr_silence_remove_batch's walk (1 .. 2^30; 0 = automatic: max(256, 4 E, positions of the longest utterance / 2048)).
  * The rest select kernel variants for A/B runs and tests. */
 int sr_set_option(const char *key, long value);
 /* Counters of the partial-product path since the library was loaded: resolve calls, (frame tile, model) pairs

@@ -39,6 +39,7 @@ EXT_SYMBOLS = [
     "sr_fullgmm_fit_batch", "sr_fullgmm_fit_batch_error", "sr_full_fit_batch_stats", "sr_full_fit_batch_bytes",
     "sr_open_set_decide", "sr_score_batch_set_open", "sr_predict_pcm_batch_open", "sr_stream_set_open", "sr_stream_collect_open",
     "sr_multi_predict_pcm_open",
+    "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -132,6 +133,9 @@ def lib():
         "sr_batch_dim": (i32, [vp]),
         "sr_batch_offsets": (i32, [vp, C.POINTER(i64)]),
         "sr_batch_download": (i32, [vp, fp]),
+        "sr_batch_download_pcm16": (i32, [vp, C.POINTER(C.c_int16)]),
+        "sr_silence_remove_batch": (vp, [vp, dbl, dbl, dbl, dbl, C.POINTER(i64)]),
+        "sr_silence_plan": (i32, [dbl, dbl, dbl, i64, C.POINTER(C.c_int32), i32]),
         "sr_score_batch_set": (i32, [vp, vp, dp, C.POINTER(i32), fp, i32]),
         "sr_mfcc_create": (vp, [dbl, dbl, dbl, i32, i32, i32, dbl]),
         "sr_mfcc_set_lpc": (i32, [vp, i32]),
@@ -359,6 +363,16 @@ def mfcc_plan(handle, precision: int = 2, generic: int = 0, pcm_kind: int = 0, n
     d["max_read"] = int(v[14])
     d["n_empty"] = int(v[15])
     return d
+
+
+def silence_plan(fs, frame_duration: float = 0.02, frame_shift: float = 0.01, max_samples: int = 1) -> dict:
+    """What ``sr_silence_remove_batch`` decides for a longest utterance of ``max_samples`` under the current ``silence_block``
+    option (csrc/silence_plan.cpp; no GPU needed): frame length L and shift S in samples, g = gcd(L, S), the width E of a
+    block's transfer map, positions per block B, the blocks of that utterance and the shape of the maps launch."""
+    v = (C.c_int32 * 12)()
+    check(lib().sr_silence_plan(float(fs), float(frame_duration), float(frame_shift), int(max_samples), v, 12), "sr_silence_plan")
+    names = ("L", "S", "g", "E", "B", "blocks", "variant", "blocks_per_wg", "list_cap", "grid", "chunk_lanes", "positions")
+    return dict(zip(names, (int(x) for x in v)))
 
 
 def last_score_kernel() -> str:

@@ -4,6 +4,7 @@
     speaker-recognition.py -t predict -i "./*.wav" -m model.out
     speaker-recognition.py -t predict -i "./*.wav" -m model.out --reject-threshold 0.5
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --covariance full
+    speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --remove-silence
 
 Wav files in each input directory are labelled with the directory's basename; wildcard inputs
 must be quoted (they go to glob).  Extra options (not in the reference) select the feature
@@ -51,6 +52,9 @@ def get_args(argv=None):
     parser.add_argument("--reject-threshold", type=float, default=None,
                         help="predict: open-set decision -- print None for a file whose best speaker's per-frame margin over the "
                              "UBM is below this (only for a model enrolled from a UBM)")
+    parser.add_argument("--remove-silence", action="store_true",
+                        help="drop silent frames before the feature stage (the reference's filters/silence.py, on the GPU). enroll: "
+                             "stored in the model; predict: applied even if the model was enrolled without it")
     return parser.parse_args(argv)
 
 
@@ -85,8 +89,10 @@ def task_enroll(input_dirs, output_model, args=None):
     m.dump(output_model)
 
 
-def task_predict(input_files, input_model, gpus=1, reject_threshold=None):
+def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove_silence=False):
     m = ModelInterface.load(input_model)
+    if remove_silence:              # the flag overrides a model enrolled without it; a model's own setting holds otherwise
+        m.remove_silence = True
     out = []
     files = sorted(glob.glob(os.path.expanduser(input_files)))
     if reject_threshold is not None:
@@ -131,7 +137,8 @@ def _make_interface(args):
         fk["FFT_SIZE"] = args.fft_size
     return ModelInterface(gmm_order=args.mixtures, feature_kwargs=fk, diff=args.deltas > 0,
                           nd=max(1, args.deltas), lpc=not args.no_lpc and args.deltas == 0,
-                          gmm_kwargs={"seed": args.seed}, covariance_type=args.covariance)
+                          gmm_kwargs={"seed": args.seed}, covariance_type=args.covariance,
+                          remove_silence=bool(getattr(args, "remove_silence", False)))
 
 
 def main(argv=None):
@@ -141,7 +148,7 @@ def main(argv=None):
     if args.task == "enroll":
         task_enroll(args.input, args.model, args)
     elif args.task == "predict":
-        task_predict(args.input, args.model, args.gpus, args.reject_threshold)
+        task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence)
     else:
         print('task must be "enroll" or "predict"')
         sys.exit(2)

@@ -112,6 +112,22 @@ class Batch:
         check(lib().sr_batch_download(self._h, _lib.as_fp(out)), "sr_batch_download")
         return out
 
+    def download_pcm(self) -> np.ndarray:
+        """The int16 samples of a PCM batch, concatenated (``offsets()`` cuts them into utterances)."""
+        out = np.empty(self.n_rows, dtype=np.int16)
+        check(lib().sr_batch_download_pcm16(self._h, out.ctypes.data_as(C.POINTER(C.c_int16))), "sr_batch_download_pcm16")
+        return out
+
+    def remove_silence(self, fs, frame_duration=0.02, frame_shift=0.01, perc=0.15) -> "Batch":
+        """The reference's energy-threshold silence removal (src/filters/silence.py:11-50) on every utterance of an int16 PCM
+        batch, on the device (sr_silence_remove_batch): -> a new device-resident PCM batch, bit-identical to the reference's
+        output per utterance, usable by ``MfccExtractor.extract_batch`` / ``predict_batch`` / ``predict_batch_open`` as it is.
+        An utterance may come out empty (``perc`` >= 1): it has no frames and ``predict_batch`` gives it -1."""
+        h = lib().sr_silence_remove_batch(self._h, float(fs), float(frame_duration), float(frame_shift), float(perc), None)
+        if not h:
+            raise SRError("sr_silence_remove_batch failed: %s" % _lib.last_error())
+        return Batch(h)
+
     def __del__(self):
         try:
             if self._owner and self._h:

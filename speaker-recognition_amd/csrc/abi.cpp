@@ -11,6 +11,7 @@
 #include "mfcc.hpp"
 #include "mfcc_plan.hpp"
 #include "score.hpp"
+#include "silence_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -29,6 +30,10 @@ void set_em_small_test_absent(int v);   // em_small.hip
 int last_em_stats_engine();
 void set_reference_side_effects(int v);
 void set_kmeans_assign_engine(int v);
+// silence.hip
+void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
+void set_silence_block(long v);
+long silence_block();
 }
 std::atomic<int> &stream_debug_capture_delay_ms();      // stream.cpp
 std::atomic<int> &multi_merge_option();
@@ -644,6 +649,40 @@ int sr_batch_download(SRBatch *b, float *out) {
     SR_CATCH(-1)
 }
 
+int sr_batch_download_pcm16(SRBatch *b, int16_t *out) {
+    SR_TRY
+    if (!b || (!out && b->n_rows > 0)) fail("null argument");
+    if (b->kind != SRBatch::PCM16) fail("only int16 PCM batches can be downloaded as PCM16");
+    b->bind_device();
+    b->pcm16.download(out, (size_t)b->n_rows);
+    sync_stream();
+    return 0;
+    SR_CATCH(-1)
+}
+
+SRBatch *sr_silence_remove_batch(SRBatch *pcm, double fs, double frame_duration, double frame_shift, double perc, int64_t *kept_out) {
+    SR_TRY
+    if (!pcm) fail("null argument");
+    auto out = std::make_unique<SRBatch>();
+    silence_remove_batch(*pcm, fs, frame_duration, frame_shift, perc, *out, kept_out);
+    return out.release();
+    SR_CATCH(nullptr)
+}
+
+int sr_silence_plan(double fs, double frame_duration, double frame_shift, int64_t max_samples, int32_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 12) fail("sr_silence_plan writes 12 fields");
+    SilencePlan p;
+    std::string why;
+    if (!plan_silence(fs, frame_duration, frame_shift, max_samples, silence_block(), p, why)) fail("remove_silence: %s", why.c_str());
+    const int64_t v[12] = {p.L, p.S, p.g, p.E, p.B, p.blocks_max, p.variant, p.blocks_per_wg, p.list_cap,
+                           silence_grid(p.blocks_max, p.blocks_per_wg), p.chunk_lanes, p.max_pos};
+    for (int i = 0; i < 12; i++) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    return 12;
+    SR_CATCH(-1)
+}
+
 int sr_score_batch_set(SRModelSet *set, SRBatch *features, double *sums_out, int *argmax_out,
                        float *frame_ll_out, int flags) {
     SR_TRY
@@ -958,6 +997,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
         set_full_fit_batch_bytes(value);
+    } else if (k == "silence_block") {
+        if (value < 0 || value > SILENCE_MAX_REL) fail("silence_block must be 0 (automatic) or 1 .. 2^30 positions per block");
+        set_silence_block(value);
     } else if (k == "mfcc_generic") {
         mfcc_set_force_generic(value != 0);
     } else if (k == "mfcc_precision") {

@@ -1,6 +1,7 @@
 """``VAD`` -- same surface as the reference's ``src/filters/VAD.py`` (``init_noise``, ``filter``):
 the LTSD detector only (the reference's noise-reduction and energy-silence stages are commented
-out there too, VAD.py:24-33)."""
+out there too, VAD.py:24-33).  The energy-silence stage itself is ``filters.silence.remove_silence``
+(csrc/silence.hip), what the reference's corpus preparation runs on every recording."""
 from .ltsd import LTSD_VAD
 
 

@@ -11,6 +11,11 @@ Extensions (all keyword-only, defaults = the reference's behaviour): ``gmm_order
 scikit-learn's full-covariance ``GaussianMixture``, as ``skgmm.GMMSet`` -- ``UBM_MODEL_FILE`` is then ignored, as the reference
 ignores it when its set is not ``GMMSetPyGMM``, interface.py:63-75; ``gmm_kwargs`` go to ``skgmm.GMM``, a ``seed`` among them
 becoming its ``random_state``, -1 = the library's default).
+``remove_silence`` (False; True: the reference's defaults; or a dict of ``frame_duration`` / ``frame_shift`` / ``perc``): the
+energy-threshold silence removal of the reference's corpus preparation (``filters.silence``, on the device) in front of the
+feature stage of ``enroll`` and every ``predict*`` -- the setting is stored with the model; int16, int8 or uint8 audio.  A signal
+it leaves too short for a frame gives None from ``predict*`` and raises from ``enroll``, as a short raw signal does.  With it,
+``predict_many(gpus != 1)`` takes the one-GPU path.
 VAD (``init_noise`` / ``filter``) is the LTSD detector of ``filters`` (third-party pyssp in the
 reference: restated, parity unpinned).
 """
@@ -34,10 +39,12 @@ class ModelInterface(object):
     UBM_MODEL_FILE = None
 
     def __init__(self, *, gmm_order=32, feature_kwargs=None, diff=False, nd=1, lpc=True, gmm_kwargs=None,
-                 verbose=True, covariance_type="diag"):
+                 verbose=True, covariance_type="diag", remove_silence=False):
         if covariance_type not in ("diag", "full"):
             raise ValueError("covariance_type must be 'diag' or 'full' (got %r)" % (covariance_type,))
         self.covariance_type = covariance_type
+        self.remove_silence = remove_silence
+        self._silence_kwargs()          # (a bad value fails here, not at the first recording)
         self.features = defaultdict(list)
         self.gmm_order = gmm_order
         self.feature_kwargs = dict(feature_kwargs or {})
@@ -71,8 +78,57 @@ class ModelInterface(object):
             return ret
         return np.array([])
 
+    def _silence_kwargs(self):
+        """None when silence removal is off (also for a model pickled before the setting existed), else its parameters."""
+        rs = getattr(self, "remove_silence", False)
+        if rs is False or rs is None:
+            return None
+        if rs is True:
+            return {}
+        if isinstance(rs, dict) and set(rs) <= {"frame_duration", "frame_shift", "perc"}:
+            return dict(rs)
+        raise ValueError("remove_silence must be False, True or a dict of frame_duration / frame_shift / perc (got %r)" % (rs,))
+
+    def _desilenced(self, items):
+        """[(fs, signal), ...] as they reach the feature stage: unchanged, or through ``filters.silence`` -- one device call
+        per sampling rate."""
+        kw = self._silence_kwargs()
+        items = list(items)
+        if kw is None or not items:
+            return items
+        from .filters.silence import remove_silence_many
+        out = [None] * len(items)
+        for rate in sorted({fs for fs, _ in items}):
+            idx = [i for i, (fs, _) in enumerate(items) if fs == rate]
+            for i, sig in zip(idx, remove_silence_many(rate, [items[i][1] for i in idx], **kw)):
+                out[i] = (rate, sig)
+        return out
+
     def _features(self, fs, signal):
+        fs, signal = self._desilenced([(fs, signal)])[0]
+        return self._features_of(fs, signal)
+
+    def _features_of(self, fs, signal):
         return mix_feature((fs, signal), lpc=self.lpc, diff=self.diff, nd=self.nd, **self.feature_kwargs)
+
+    def _features_many(self, items):
+        """The feature matrices of [(fs, signal), ...] behind the silence removal; a signal it leaves too short for a frame
+        gives None in its place (``predict`` answers None there too)."""
+        feats = []
+        for fs, sig in self._desilenced(items):
+            try:
+                feats.append(self._features_of(fs, sig))
+            except Exception:
+                print(tb.format_exc(), file=sys.stderr)
+                feats.append(None)
+        return feats
+
+    @staticmethod
+    def _spread(feats, predict):
+        """``predict`` over the matrices that exist, None where there is none"""
+        have = [f for f in feats if f is not None]
+        labels = iter(predict(have) if have else [])
+        return [None if f is None else next(labels) for f in feats]
 
     def enroll(self, name, fs, signal):
         """add the signal to this person's training dataset"""
@@ -125,6 +181,9 @@ class ModelInterface(object):
         """Extension: [(fs, signal), ...] -> labels by the open-set decision of ``predict(reject_threshold=)``, every utterance
         scored and decided in ONE batch on one GPU (``GMMSet.predict_with_reject_batch``)."""
         self._check_reject()
+        if self._silence_kwargs() is not None:
+            return self._spread(self._features_many(list(items)),
+                                lambda f: self.gmmset.predict_with_reject_batch(f, threshold=float(reject_threshold)))
         feats = [self._features(fs, sig) for fs, sig in items]
         return self.gmmset.predict_with_reject_batch(feats, threshold=float(reject_threshold))
 
@@ -138,6 +197,8 @@ class ModelInterface(object):
         refuses ("Signal too short!"), is scored when it yields at least one frame and gets ``None`` when it yields none (as on
         the diagonal sharded route)."""
         items = list(items)
+        if self._silence_kwargs() is not None:
+            gpus = 1                # (silence removal is not part of the sharded route: its slots upload raw PCM themselves)
         rates = {fs for fs, _ in items}
         full = getattr(self, "covariance_type", "diag") == "full"
         pcm_ok = len(rates) == 1 and items and all(np.asarray(sig).dtype == np.int16 and np.asarray(sig).ndim == 1 for _, sig in items)
@@ -168,6 +229,8 @@ class ModelInterface(object):
             mp = cached[1]
             _, winners = mp.predict([sig for _, sig in items], nd=self.nd if self.diff else 0)
             return [None if w < 0 else self.gmmset.y[w] for w in winners]
+        if self._silence_kwargs() is not None:
+            return self._spread(self._features_many(items), self.gmmset.predict)
         feats = [self._features(fs, sig) for fs, sig in items]
         return self.gmmset.predict(feats)
 
