@@ -307,7 +307,11 @@ int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
 #define SR_T_FINALIZE 3
 #define SR_T_ESTEP 4
 #define SR_T_SCORE_REF 5   /* reference-offset pre-pass of the split-fp16 shared-sigma engine */
-#define SR_T_COUNT 6
+#define SR_T_TOPC_SELECT 6   /* the four stages of sr_score_batch_set_topc (csrc/gmm_topc.hip) */
+#define SR_T_TOPC_ROUTE 7
+#define SR_T_TOPC_EVAL 8
+#define SR_T_TOPC_COMBINE 9
+#define SR_T_COUNT 10
 int sr_profile_enable(int on);
 int sr_profile_reset(void);
 int sr_profile_get(int kind, double *total_ms, long *launches);
@@ -326,6 +330,7 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *   "multi_merge_same_device" 0: slots that share a device get a host thread each (default 1: one queue per device).
  *   "full_fit_batch_bytes" the workspace bound, in bytes (>= 1; default 1 GiB), of a group of speakers in sr_fullgmm_fit_batch.
  *   "silence_block"  positions per block of sr_silence_remove_batch's walk (1 .. 2^30; 0 = automatic: max(256, 4 E, positions of the longest utterance / 2048)).
+ *   "topc_scratch_mib" the scratch bound of sr_score_batch_set_topc, in MiB (>= 1; default 1024): the pass runs in chunks of frames that fit.
  * The rest select kernel variants for A/B runs and tests. */
 int sr_set_option(const char *key, long value);
 /* Counters of the partial-product path since the library was loaded: resolve calls, (frame tile, model) pairs
@@ -483,6 +488,37 @@ int sr_stream_collect_open(SRStream *s, double *sums_out, int *label_out, double
 int sr_multi_predict_pcm_open(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt, int nd, int bg,
                               double threshold, double *sums_out, int *label_out, double *margin_out, double *slot_seconds_out,
                               int flags);
+
+/* ---- Top-C Gaussian selection (csrc/gmm_topc.hip; Reynolds, Quatieri & Dunn 2000): fast, APPROXIMATE scoring of a set whose
+ * models share sigma and weights -- speakers MAP-adapted from one UBM, means only (gmmubm.cc:40-81) -- with the UBM as column
+ * `bg`.  Opt-in: no other entry point takes this path.  Per frame x, with 1 <= top_c <= K:
+ *   t_k = ln w_k - sum_d ln(sqrt(2 pi) sigma_kd) - sum_d (x_d - mu^bg_kd)^2 / (2 sigma_kd^2), k = 0 .. K - 1;
+ *   top(x) = the top_c indices with the largest t_k, in descending order, equal values to the lower index first;
+ *   LL_bg(x) = logsumexp over all K of t_k (the background column stays exact);
+ *   LL_s(x) = logsumexp over k in top(x) of the same expression with model s's means, for every s != bg.
+ * SR_CLAMP_COMPAT: a per-frame value below ln DBL_MIN = -708.396 becomes ln(1e-15) -- the plain threshold only; the
+ * partial-product re-evaluation of csrc/gmm_flush.hip belongs to the exact path and does not apply here.
+ * sums_out [U][S] = the per-utterance sums in float64 (fixed order: bit-identical from run to run); argmax_out [U] = the first
+ * maximum over all columns as sr_score_batch_set returns it, -1 for an utterance without frames; topc_out [n_frames][top_c]
+ * (or NULL) = top(x) of every frame; frame_ll_out [S][n_frames] (or NULL).  The sums feed sr_open_set_decide as they are.
+ * A frame with a non-finite feature gives NaN sums for its utterance; its selection is still top_c distinct indices in range.
+ * top_c == K reproduces sr_score_batch_set within the parity gate (1e-4 max(1, |LL|) per frame).
+ * Refused, before the device is touched, with a message that names the remedy: a set that does not share sigma and weights, bg
+ * outside [0, S), top_c outside [1, K], a PCM batch given to the feature entry point, rows wider than 64 dimensions, top_c > 8
+ * with K > 8192.  fp32 direct form on the vector engine's packed parameters; the per-set tables are packed on first use.
+ * The pass runs in chunks of frames whose scratch (4 top_c S bytes per frame and a little more) stays under
+ * sr_set_option("topc_scratch_mib", n) (default 1024); the cut shows in the sums' last bits only.
+ * sr_predict_pcm_batch_topc: sr_mfcc_extract_batch (CMVN, nd orders of deltas), then the call above; the features stay on the device.
+ * sr_topc_plan: what such a call decides (csrc/topc_plan.cpp; host only when n_cu > 0, n_cu <= 0: the current device's), for tests.
+ * Writes 16 fields (n_out >= 16; values above INT32_MAX saturate) and returns 16, -1 on refusal: padded row width, register slots
+ * of the running selection (0: the rank kernel), scratch bytes per frame, frames per chunk, chunks, entries per evaluate run, entries
+ * staged at a time, waves per evaluate workgroup, evaluate grid x (an upper bound of a full chunk's runs) and y, select grid, route
+ * grid, lanes of a combine workgroup, frames per combine tile, LDS bytes of the rank kernel, 0. */
+int sr_score_batch_set_topc(SRModelSet *set, SRBatch *features, int bg, int top_c, double *sums_out /*[U][S]*/, int *argmax_out /*[U]*/,
+                            int *topc_out /*[n_frames][top_c] or NULL*/, float *frame_ll_out /*[S][n_frames] or NULL*/, int flags);
+int sr_predict_pcm_batch_topc(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int bg, int top_c, double *sums_out, int *argmax_out,
+                              int flags);
+int sr_topc_plan(int K, int D, int S, int top_c, int64_t n_frames, int64_t scratch_bytes, int n_cu, int32_t *out, int n_out);
 
 #ifdef __cplusplus
 }

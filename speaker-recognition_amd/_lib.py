@@ -40,12 +40,14 @@ EXT_SYMBOLS = [
     "sr_open_set_decide", "sr_score_batch_set_open", "sr_predict_pcm_batch_open", "sr_stream_set_open", "sr_stream_collect_open",
     "sr_multi_predict_pcm_open",
     "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
+    "sr_score_batch_set_topc", "sr_predict_pcm_batch_topc", "sr_topc_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
 SR_SCORE_PRECISE = 0x200
 SR_STREAM_GRAPH = 0x100
 T_SCORE, T_MFCC, T_CMVN, T_FINALIZE, T_ESTEP, T_SCORE_REF = 0, 1, 2, 3, 4, 5
+T_TOPC_SELECT, T_TOPC_ROUTE, T_TOPC_EVAL, T_TOPC_COMBINE = 6, 7, 8, 9      # the four stages of sr_score_batch_set_topc
 
 
 class Parameter(C.Structure):
@@ -199,6 +201,9 @@ def lib():
         "sr_stream_collect_open": (i32, [vp, dp, C.POINTER(i32), dp, C.POINTER(i32), dp]),
         "sr_multi_predict_pcm_open": (i32, [vp, C.POINTER(C.c_int16), C.POINTER(i64), i32, i32, i32, dbl, dp, C.POINTER(i32), dp, dp,
                                             i32]),
+        "sr_score_batch_set_topc": (i32, [vp, vp, i32, i32, dp, C.POINTER(i32), C.POINTER(i32), fp, i32]),
+        "sr_predict_pcm_batch_topc": (i32, [vp, vp, vp, i32, i32, i32, dp, C.POINTER(i32), i32]),
+        "sr_topc_plan": (i32, [i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -373,6 +378,17 @@ def silence_plan(fs, frame_duration: float = 0.02, frame_shift: float = 0.01, ma
     check(lib().sr_silence_plan(float(fs), float(frame_duration), float(frame_shift), int(max_samples), v, 12), "sr_silence_plan")
     names = ("L", "S", "g", "E", "B", "blocks", "variant", "blocks_per_wg", "list_cap", "grid", "chunk_lanes", "positions")
     return dict(zip(names, (int(x) for x in v)))
+
+
+def topc_plan(K: int, D: int, S: int, top_c: int, n_frames: int, scratch_bytes: int = 1 << 30, n_cu: int = 256) -> dict:
+    """What ``sr_score_batch_set_topc`` decides for a set of S models of K mixtures in D dimensions, `n_frames` frames and a scratch
+    bound (csrc/topc_plan.cpp; no GPU needed when n_cu > 0): padded row width, the selection's register slots (0: the rank kernel),
+    scratch bytes per frame, frames per chunk, chunks, and the shapes of the four stages' launches."""
+    v = (C.c_int32 * 16)()
+    check(lib().sr_topc_plan(int(K), int(D), int(S), int(top_c), int(n_frames), int(scratch_bytes), int(n_cu), v, 16), "sr_topc_plan")
+    names = ("tp", "cr", "row_bytes", "chunk", "n_chunks", "run", "stage", "eval_waves", "eval_grid_x", "eval_grid_y", "select_grid",
+             "route_grid", "combine_wg", "tile", "rank_lds")
+    return dict(zip(names, (int(x) for x in v[:15])))
 
 
 def last_score_kernel() -> str:

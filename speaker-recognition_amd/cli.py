@@ -52,6 +52,9 @@ def get_args(argv=None):
     parser.add_argument("--reject-threshold", type=float, default=None,
                         help="predict: open-set decision -- print None for a file whose best speaker's per-frame margin over the "
                              "UBM is below this (only for a model enrolled from a UBM)")
+    parser.add_argument("--top-c", type=int, default=None,
+                        help="predict: top-C Gaussian selection -- per frame only the N best components of the UBM are evaluated in "
+                             "every speaker model (an approximation; default off; only for a diagonal model enrolled from a UBM)")
     parser.add_argument("--remove-silence", action="store_true",
                         help="drop silent frames before the feature stage (the reference's filters/silence.py, on the GPU). enroll: "
                              "stored in the model; predict: applied even if the model was enrolled without it")
@@ -89,12 +92,29 @@ def task_enroll(input_dirs, output_model, args=None):
     m.dump(output_model)
 
 
-def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove_silence=False):
+def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove_silence=False, top_c=None):
     m = ModelInterface.load(input_model)
     if remove_silence:              # the flag overrides a model enrolled without it; a model's own setting holds otherwise
         m.remove_silence = True
     out = []
     files = sorted(glob.glob(os.path.expanduser(input_files)))
+    if top_c is not None:
+        try:
+            m._check_topc()
+            if top_c < 1:
+                raise ValueError("N must be >= 1")
+        except ValueError as e:
+            print("--top-c: %s" % e)
+            sys.exit(2)
+        if gpus != 1:
+            print("--top-c: top-C scoring of a file list runs on one GPU (--gpus 1)")
+            sys.exit(2)
+        # every file in one batch (interface.predict_many_topc); with --reject-threshold the open-set rule decides on its sums
+        labels = m.predict_many_topc([read_wav(f) for f in files], top_c, reject_threshold)
+        for f, label in zip(files, labels):
+            print(f, "->", label)
+            out.append((f, label))
+        return out
     if reject_threshold is not None:
         try:
             m._check_reject()
@@ -148,7 +168,7 @@ def main(argv=None):
     if args.task == "enroll":
         task_enroll(args.input, args.model, args)
     elif args.task == "predict":
-        task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence)
+        task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence, args.top_c)
     else:
         print('task must be "enroll" or "predict"')
         sys.exit(2)

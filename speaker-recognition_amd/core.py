@@ -189,6 +189,23 @@ class ModelSet:
               "sr_score_batch_set_open")
         return sums, labels, margins
 
+    def score_topc(self, feats: Batch, bg: int, top_c: int, frame_ll: bool = False, selection: bool = False, clamp_compat: bool = True):
+        """Top-C Gaussian selection (sr_score_batch_set_topc; Reynolds, Quatieri & Dunn 2000) for a set whose models share sigma
+        and weights with the background model in column ``bg`` (speakers MAP-adapted from one UBM): per frame the ``top_c`` best
+        components of the background model are found and only those are evaluated in every other model; the background column
+        stays exact.  An approximation (``top_c`` = the mixture count reproduces ``score``), so nothing else takes this path.
+        -> (sums[U, S] float64, argmax[U] int32[, frame_ll[S, n] float32][, selection[n, top_c] int32]).  A set that does not
+        qualify, ``bg`` or ``top_c`` out of range, or a PCM batch raise ``SRError`` before the device is touched."""
+        U, S = feats.n_utt, len(self)
+        sums = np.zeros((U, S), dtype=np.float64)
+        arg = np.full(U, -1, dtype=np.int32)
+        fll = np.empty((S, feats.n_rows), dtype=np.float32) if frame_ll else None
+        sel = np.full((feats.n_rows, max(0, int(top_c))), -1, dtype=np.int32) if selection else None
+        check(lib().sr_score_batch_set_topc(self._h, feats._h, int(bg), int(top_c), _lib.as_dp(sums), _lib.as_i32p(arg),
+                                            _lib.as_i32p(sel) if selection else None, _lib.as_fp(fll) if frame_ll else None,
+                                            _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_score_batch_set_topc")
+        return (sums, arg) + ((fll,) if frame_ll else ()) + ((sel,) if selection else ())
+
     def __del__(self):
         try:
             if self._h:
@@ -273,6 +290,16 @@ class MfccExtractor:
                                               _lib.as_i32p(labels), _lib.as_dp(margins),
                                               _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_predict_pcm_batch_open")
         return sums, labels, margins
+
+    def predict_batch_topc(self, models: ModelSet, pcm: Batch, bg: int, top_c: int, nd: int = 0, clamp_compat: bool = True):
+        """``predict_batch`` through ``ModelSet.score_topc`` (sr_predict_pcm_batch_topc): the features stay on the device;
+        -> (sums[U, S], argmax[U] int32), the bits of ``extract_batch`` followed by ``score_topc``."""
+        U, S = pcm.n_utt, len(models)
+        sums = np.zeros((U, S), dtype=np.float64)
+        arg = np.full(U, -1, dtype=np.int32)
+        check(lib().sr_predict_pcm_batch_topc(self._h, models._h, pcm._h, int(nd), int(bg), int(top_c), _lib.as_dp(sums),
+                                              _lib.as_i32p(arg), _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_predict_pcm_batch_topc")
+        return sums, arg
 
     def __del__(self):
         try:

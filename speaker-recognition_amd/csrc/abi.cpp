@@ -12,6 +12,7 @@
 #include "mfcc_plan.hpp"
 #include "score.hpp"
 #include "silence_plan.hpp"
+#include "topc_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -836,6 +837,54 @@ int sr_predict_pcm_batch_open(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, 
     SR_CATCH(-1)
 }
 
+// ---- top-C Gaussian selection (gmm_topc.hip).  Every refusal comes before the device is touched. ----
+
+int sr_score_batch_set_topc(SRModelSet *set, SRBatch *features, int bg, int top_c, double *sums_out, int *argmax_out, int *topc_out,
+                            float *frame_ll_out, int flags) {
+    SR_TRY
+    if (!set || !features) fail("sr_score_batch_set_topc: null argument");
+    score_batch_set_topc(*set, *features, bg, top_c, sums_out, argmax_out, topc_out, frame_ll_out, flags);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_predict_pcm_batch_topc(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int bg, int top_c, double *sums_out, int *argmax_out,
+                              int flags) {
+    SR_TRY
+    if (!m || !set || !pcm) fail("sr_predict_pcm_batch_topc: null argument");
+    if (pcm->kind == SRBatch::FEATURES) fail("sr_predict_pcm_batch_topc takes a PCM batch; score a feature batch with sr_score_batch_set_topc");
+    {   // the set's and the rule's refusals before the feature stage runs (the batch is PCM here: that check is the other entry point's)
+        const int K = set->host.model_mixtures.empty() ? 0 : set->host.model_mixtures[0];
+        std::string why;
+        if (!topc_check(topc_set_tied(*set), set->host.n_models, K, set->host.dim, bg, top_c, true, why)) fail("%s", why.c_str());
+    }
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_predict_pcm_batch_topc");
+    ensure_device();
+    SRBatch *feat_ws = &per_device<SRBatch>();   // the fused calls' feature workspace: nothing leaves the device
+    mfcc_extract_batch(*m, *pcm, nd, 1, *feat_ws);
+    score_batch_set_topc(*set, *feat_ws, bg, top_c, sums_out, argmax_out, nullptr, nullptr, flags);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_topc_plan(int K, int D, int S, int top_c, int64_t n_frames, int64_t scratch_bytes, int n_cu, int32_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 16) fail("sr_topc_plan writes 16 fields");
+    if (n_cu <= 0) {
+        ensure_device();
+        n_cu = ctx().n_cu;
+    }
+    TopcPlan p;
+    std::string why;
+    if (!plan_topc(K, D, S, top_c, n_frames, scratch_bytes, n_cu, p, why)) fail("%s", why.c_str());
+    const int64_t v[16] = {p.tp, p.cr, p.row_bytes, p.chunk, p.n_chunks, p.run, TOPC_STAGE, p.eval_waves, p.eval_grid_x, p.eval_grid_y,
+                           p.select_grid, p.route_grid, p.combine_wg, TOPC_TILE, p.rank_lds, 0};
+    for (int i = 0; i < 16; i++) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    return 16;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY
@@ -994,6 +1043,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "debug_helper_max_models") {
         if (value < 0) fail("debug_helper_max_models must be >= 0 (0: the default)");
         fork_proxy_set_max_models(value);                           // test hook (tests/test_gpu_fork.py): applies in the helper, where it is forwarded
+    } else if (k == "topc_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("topc_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(TOPC_DEFAULT_SCRATCH >> 20));
+        set_topc_scratch_mib(value);
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
         set_full_fit_batch_bytes(value);

@@ -800,6 +800,7 @@ static void upload_em_set(SRModelSet &s) {
     // the matrix-core layout goes up when a kernel asks for it (ensure_bx3_layout), into the same buffers: a speaker-sized model
     // (16 mixtures: half of every 32-mixture tile would be padding) stays on the vector engine and never does
     s.bx3_stale = true;
+    s.topc_state = 0;       // (gmm_topc.hip's tables are packed from the vector layout: again on next use)
     sync_stream();
     s.device = ctx().device;
 }

@@ -288,6 +288,7 @@ PackedModels pack_models(const std::vector<const GMM *> &models) {
             pm.chunks.push_back(cd);
         }
         pm.model_chunk_begin.push_back((int)pm.chunks.size());
+        pm.model_mixtures.push_back(g.nr_mixtures);
         total_f4 += (size_t)n_rec * rec_f4;
     }
     if (total_f4 >= ((size_t)1 << 32)) fail("model set of %zu parameter records of 16 bytes: chunk offsets are 32-bit", total_f4);

@@ -82,6 +82,7 @@ struct PackedModels {
                                     // so that a feature space far from the origin costs no digits in x*s + m
     std::vector<ChunkDesc> chunks;  // all models, in model order
     std::vector<int> model_chunk_begin;  // [S+1]
+    std::vector<int> model_mixtures;     // [S] live mixtures of every model (its records are padded to whole groups of KB)
     // Width (nats) of the band above ln DBL_MIN in which the reference's flushes of PARTIAL products can change a
     // frame's log-likelihood (lse.hpp): max_k sum_d max(0, -ln sigma_kd) + ln K + 17.5 over the set's models.
     double flush_band = 0.0;
@@ -232,6 +233,14 @@ struct SRModelSet {
     };
     std::vector<std::unique_ptr<GroupTable>> group_tables;
     size_t group_table_next = 0;
+    // top-C scoring (gmm_topc.hip), 0 not looked at yet, -1 the set does not qualify, 2 it does, 1 it does and its tables
+    // (packed from the vector layout on first use) stand on the device
+    int topc_state = 0;
+    sr::DevBuf<float> d_topc_scale;  // [K][TP] the shared s_kd, zero-padded
+    sr::DevBuf<float> d_topc_m;      // [K][TP][S] every model's m_skd (a lane per model reads consecutive floats)
+    sr::DevBuf<float> d_topc_c;      // [K] the shared constants
+    sr::DevBuf<float> d_topc_bg;     // [K][TP][2] {s, m} of the background column `topc_bg`, gathered per call when it changes
+    int topc_bg = -1, topc_tp = 0, topc_k = 0;
     sr::DevBuf<int> d_flush_models;  // per model {first record, records} of the vector layout (gmm_flush.hip; built on first use)
     std::unique_ptr<SRModelSet> hy_good, hy_bad;
     int hy_bad_mixtures = 0;         // mixtures of the set's largest model that went to the vector engine

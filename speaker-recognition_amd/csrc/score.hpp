@@ -223,6 +223,14 @@ void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_
                  const OpenSetFetch *open = nullptr);
 // score_device + fetch with the open-set decision (gmm_score_host.cpp)
 void score_batch_set_open(SRModelSet &set, SRBatch &feat, double *sums_out, const OpenSetFetch &open, int flags);
+// gmm_topc.hip: top-C Gaussian selection against the background column `bg` (opt-in; the exact path never calls it).  Refusals --
+// a set that does not share sigma and weights, bg or top_c out of range, a PCM batch -- come before any device work.
+// topc_out [n_frames][top_c] / frame_ll_out [S][n_frames]: host memory or null.
+void score_batch_set_topc(SRModelSet &set, SRBatch &feat, int bg, int top_c, double *sums_out, int *argmax_out, int *topc_out,
+                          float *frame_ll_out, int flags);
+bool topc_set_tied(SRModelSet &set);       // does the set qualify?  (host only; the answer is kept)
+void set_topc_scratch_mib(long v);
+long topc_scratch_mib();
 // Packs + uploads a model set on the current device.
 void upload_model_set(SRModelSet &s);
 // a GMM handle's own one-model set on the current device, packed and uploaded once (abi.cpp; invalidated by GMM::drop_single)

@@ -112,11 +112,23 @@ class GMMSet(object):
     def predict_one(self, x):
         return self._label_of_best(self.predict_one_scores(x))
 
-    def predict(self, X):
-        """All utterances in one batch; the arg max comes back from the device."""
+    def _topc_sums(self, utterances, top_c):
+        # [UBM] + speakers through the top-C path, the UBM as background column 0 (core.ModelSet.score_topc)
+        if self.ubm is None:
+            raise AssertionError("UBM must be given prior to conduct reject prediction.")
+        sums, _ = self._open_model_set().score_topc(Batch.from_features(utterances), 0, int(top_c))
+        return sums
+
+    def predict(self, X, top_c=None):
+        """All utterances in one batch; the arg max comes back from the device.
+        ``top_c``: score through top-C Gaussian selection against the UBM (speakers enrolled from it; an approximation, see
+        ``ModelSet.score_topc``) -- the label is the first maximum over the speakers' columns, as the open-set route maps them."""
         utterances = list(X)
         if not utterances:
             return []
+        if top_c is not None:
+            sums = self._topc_sums(utterances, top_c)
+            return [None if len(x) == 0 or not self.gmms else self.y[int(np.argmax(row[1:]))] for x, row in zip(utterances, sums)]
         if _lib.gpu_runtime_lost():
             return [self.predict_one(x) for x in utterances]
         _, winners = self._model_set().score(Batch.from_features(utterances))
@@ -141,10 +153,22 @@ class GMMSet(object):
                                                                 float(self.reject_threshold if threshold is None else threshold))
         return labels, margins
 
-    def predict_with_reject_batch(self, X, threshold=None):
+    def predict_with_reject_batch(self, X, threshold=None, top_c=None):
         """``predict_with_reject`` for all utterances in ONE batch, the decision taken on the device
         (``ModelSet.score_open`` over [UBM] + speakers): a list of labels, None for a rejected utterance.
-        ``threshold``: decide against this value for the call instead of ``reject_threshold``, which stays as it is."""
+        ``threshold``: decide against this value for the call instead of ``reject_threshold``, which stays as it is.
+        ``top_c``: the sums come from top-C Gaussian selection (``ModelSet.score_topc``) and the same rule decides on them."""
+        if top_c is not None:
+            from .core import open_set_decide
+            utterances = list(X)
+            if self.ubm is None:
+                raise AssertionError("UBM must be given prior to conduct reject prediction.")
+            if not utterances:
+                return []
+            sums = self._topc_sums(utterances, top_c)
+            labels, _ = open_set_decide(sums, [len(x) for x in utterances], 0,
+                                        float(self.reject_threshold if threshold is None else threshold))
+            return [None if w < 0 else self.y[w - 1] for w in labels]
         labels, _ = self._reject_batch(X, threshold)
         return [None if w < 0 else self.y[w - 1] for w in labels]
 

@@ -157,10 +157,14 @@ class ModelInterface(object):
         if self.verbose:
             print(time.time() - start, " seconds")
 
-    def predict(self, fs, signal, reject_threshold=None):
+    def predict(self, fs, signal, reject_threshold=None, top_c=None):
         """return a label (name).  Extension: ``reject_threshold`` (a number) takes the open-set decision instead -- None when
         the best speaker's per-frame margin over the UBM is below it (``GMMSet.predict_with_reject_batch``: decided on the
-        device); only a model enrolled from a UBM can."""
+        device); only a model enrolled from a UBM can.  ``top_c`` (an integer; default off): score through top-C Gaussian
+        selection against the UBM (``GMMSet.predict(top_c=)``: an approximation, far less work per frame for large sets); only a
+        model enrolled from a UBM can."""
+        if top_c is not None:
+            return self.predict_many_topc([(fs, signal)], top_c, reject_threshold)[0]
         if reject_threshold is not None:
             self._check_reject()
         try:
@@ -176,6 +180,27 @@ class ModelInterface(object):
         if getattr(self, "covariance_type", "diag") == "full" or getattr(self.gmmset, "ubm", None) is None:
             raise ValueError("a reject threshold needs a model enrolled from a UBM (ModelInterface.UBM_MODEL_FILE at training "
                              "time, diagonal models): this one has none")
+
+    def _check_topc(self):
+        if getattr(self, "covariance_type", "diag") == "full":
+            raise ValueError("top-C Gaussian selection is for diagonal models enrolled from a UBM: this model is full-covariance")
+        if getattr(self.gmmset, "ubm", None) is None:
+            raise ValueError("top-C Gaussian selection needs a model enrolled from a UBM (ModelInterface.UBM_MODEL_FILE at training "
+                             "time): this one has none")
+
+    def predict_many_topc(self, items, top_c, reject_threshold=None):
+        """Extension: [(fs, signal), ...] -> labels, every utterance scored in ONE batch through top-C Gaussian selection against
+        the UBM (``GMMSet.predict(top_c=)``); with ``reject_threshold`` the open-set rule decides on those sums."""
+        self._check_topc()
+        if int(top_c) < 1:
+            raise ValueError("top_c must be >= 1 (got %r)" % (top_c,))
+        if reject_threshold is not None:
+            run = lambda f: self.gmmset.predict_with_reject_batch(f, threshold=float(reject_threshold), top_c=int(top_c))  # noqa: E731
+        else:
+            run = lambda f: self.gmmset.predict(f, top_c=int(top_c))  # noqa: E731
+        if self._silence_kwargs() is not None:
+            return self._spread(self._features_many(list(items)), run)
+        return run([self._features(fs, sig) for fs, sig in items])
 
     def predict_many_with_reject(self, items, reject_threshold):
         """Extension: [(fs, signal), ...] -> labels by the open-set decision of ``predict(reject_threshold=)``, every utterance
