@@ -311,7 +311,10 @@ int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
 #define SR_T_TOPC_ROUTE 7
 #define SR_T_TOPC_EVAL 8
 #define SR_T_TOPC_COMBINE 9
-#define SR_T_COUNT 10
+#define SR_T_BW_LSE 10       /* the three passes of sr_bw_stats_batch (csrc/bw_stats.hip): per-frame log-sum-exp, */
+#define SR_T_BW_STATS 11     /* the statistics on the fp64 matrix cores, */
+#define SR_T_BW_REDUCE 12    /* the sum of an utterance's slabs */
+#define SR_T_COUNT 13
 int sr_profile_enable(int on);
 int sr_profile_reset(void);
 int sr_profile_get(int kind, double *total_ms, long *launches);
@@ -331,6 +334,10 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *   "full_fit_batch_bytes" the workspace bound, in bytes (>= 1; default 1 GiB), of a group of speakers in sr_fullgmm_fit_batch.
  *   "silence_block"  positions per block of sr_silence_remove_batch's walk (1 .. 2^30; 0 = automatic: max(256, 4 E, positions of the longest utterance / 2048)).
  *   "topc_scratch_mib" the scratch bound of sr_score_batch_set_topc, in MiB (>= 1; default 1024): the pass runs in chunks of frames that fit.
+ *   "bw_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the float64 slabs sr_bw_stats_batch keeps at a time: the range
+ *                    table runs in groups that fit.  Results do not depend on it, bit for bit.
+ *   "bw_range_frames" frames per range of sr_bw_stats_batch (1 .. 2^30; 0 = automatic: max(1024, the utterance's length / 256 rounded
+ *                    up to whole tiles of 128)).  Results depend on it in their last bits only.
  * The rest select kernel variants for A/B runs and tests. */
 int sr_set_option(const char *key, long value);
 /* Counters of the partial-product path since the library was loaded: resolve calls, (frame tile, model) pairs
@@ -519,6 +526,35 @@ int sr_score_batch_set_topc(SRModelSet *set, SRBatch *features, int bg, int top_
 int sr_predict_pcm_batch_topc(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int bg, int top_c, double *sums_out, int *argmax_out,
                               int flags);
 int sr_topc_plan(int K, int D, int S, int top_c, int64_t n_frames, int64_t scratch_bytes, int n_cu, int32_t *out, int n_out);
+
+/* ---- Batched Baum-Welch statistics (csrc/bw_stats.hip): the zero- and first-order statistics of every utterance of a feature
+ * batch against ONE diagonal model of a set -- the UBM --, what the reference's JFA leg computes one session at a time in MATLAB
+ * (src/jfa/collect_suf_stats.m, sc_compute_suf_stats.m) and what supervectors, factor analysis and i-vectors start from.
+ * With gamma_k(t) = w_k N(x_t; mu_k, sigma_k^2) / sum_j w_j N(x_t; mu_j, sigma_j^2) for the frames t of utterance u:
+ *   N [U][K]     N[u][k]         = sum_t gamma_k(t)
+ *   F [U][K * D] F[u][k * D + d] = sum_t gamma_k(t) x_t[d]       (mixture-major: the reference's supervector order)
+ *   ll [U] (or NULL)             = sum_t ln sum_j w_j N(x_t; ...)
+ *   dropped [U] (or NULL)        = the frames of u that contributed nothing.
+ * A frame contributes iff its log-sum-exp is finite: a row holding a NaN or an infinity, or values so large that every density
+ * is -inf, adds nothing to N, F and ll and is counted in dropped.  The posteriors are formed in the log domain, so a frame far
+ * from every mixture contributes normally -- where the reference's linear-domain quotient is 0 / 0 = NaN.
+ * fp32 densities in the vector engine's 2-FMA form, float64 sums on the fp64 matrix cores in a fixed order: an utterance's N,
+ * F and ll are the same bits alone, inside any batch and under any "bw_scratch_mib"; "bw_range_frames" (the cut of an utterance
+ * into ranges that are summed apart) shows in the last bits only.  An utterance without frames gives zeros.
+ * Refused, before the device is touched, with a message that names the remedy: a PCM batch, `model` outside [0, S), rows wider
+ * than 40 dimensions, a feature dimension that is not the model's, a scratch bound below one range's slab.  Refused in a
+ * process forked after the GPU runtime was initialised.
+ * sr_bw_plan: what such a call decides (csrc/bw_plan.cpp; host only when n_cu > 0, n_cu <= 0: the current device's), for tests:
+ * the refusals above from (S, model, K, D, batch_is_features, feat_dim), then for utterances of lengths [n_utt] the range table
+ * -- up to range_cap triples {utterance, first row of the batch, rows} into ranges_out (or NULL) -- and 12 fields (n_out >= 12):
+ * padded row width, blocks of 16 statistic columns, blocks of 64 mixtures, bytes of one range's slab, ranges, ranges per group,
+ * groups, grid of the log-sum-exp pass, LDS bytes of a statistics workgroup, reduce workgroups per (utterance, group), rounds
+ * of the largest statistics launch over the chip, the automatic range length of a short utterance.  Returns 12, -1 on refusal. */
+int sr_bw_stats_batch(SRModelSet *set, int model, SRBatch *feats, double *N /*[U][K]*/, double *F /*[U][K*D]*/,
+                      double *ll /*[U] or NULL*/, int64_t *dropped /*[U] or NULL*/);
+int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_dim, const int64_t *lengths, int64_t n_utt,
+               int64_t range_frames, int64_t scratch_bytes, int n_cu, int64_t *ranges_out /*[range_cap][3] or NULL*/, int64_t range_cap,
+               int64_t *out, int n_out);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ The compute lives in ``lib/pygmm.so`` (HIP kernels for gfx950 behind the C ABI d
 ``include/pygmm_hip.h``); the modules here mirror the reference's Python surface for that
 path: ``pygmm`` (src/gmm/python/pygmm.py), ``gmmset`` (src/testbench/gmmset.py),
 ``feature`` (src/feature/MFCC.py, utils.py, __init__.py), ``interface``
-(src/gui/interface.py) and ``cli`` (src/speaker-recognition.py).
+(src/gui/interface.py) and ``cli`` (src/speaker-recognition.py); ``jfa`` holds the front of
+src/jfa/ (per-session Baum-Welch statistics against a UBM) by the reference's names.
 """
 __version__ = "0.1.0"

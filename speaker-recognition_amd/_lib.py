@@ -41,6 +41,7 @@ EXT_SYMBOLS = [
     "sr_multi_predict_pcm_open",
     "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
     "sr_score_batch_set_topc", "sr_predict_pcm_batch_topc", "sr_topc_plan",
+    "sr_bw_stats_batch", "sr_bw_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -48,6 +49,7 @@ SR_SCORE_PRECISE = 0x200
 SR_STREAM_GRAPH = 0x100
 T_SCORE, T_MFCC, T_CMVN, T_FINALIZE, T_ESTEP, T_SCORE_REF = 0, 1, 2, 3, 4, 5
 T_TOPC_SELECT, T_TOPC_ROUTE, T_TOPC_EVAL, T_TOPC_COMBINE = 6, 7, 8, 9      # the four stages of sr_score_batch_set_topc
+T_BW_LSE, T_BW_STATS, T_BW_REDUCE = 10, 11, 12                             # the three passes of sr_bw_stats_batch
 
 
 class Parameter(C.Structure):
@@ -204,6 +206,8 @@ def lib():
         "sr_score_batch_set_topc": (i32, [vp, vp, i32, i32, dp, C.POINTER(i32), C.POINTER(i32), fp, i32]),
         "sr_predict_pcm_batch_topc": (i32, [vp, vp, vp, i32, i32, i32, dp, C.POINTER(i32), i32]),
         "sr_topc_plan": (i32, [i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), i32]),
+        "sr_bw_stats_batch": (i32, [vp, i32, vp, dp, dp, dp, C.POINTER(i64)]),
+        "sr_bw_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i64), i64, i64, i64, i32, C.POINTER(i64), i64, C.POINTER(i64), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -389,6 +393,25 @@ def topc_plan(K: int, D: int, S: int, top_c: int, n_frames: int, scratch_bytes: 
     names = ("tp", "cr", "row_bytes", "chunk", "n_chunks", "run", "stage", "eval_waves", "eval_grid_x", "eval_grid_y", "select_grid",
              "route_grid", "combine_wg", "tile", "rank_lds")
     return dict(zip(names, (int(x) for x in v[:15])))
+
+
+def bw_plan(K: int, D: int, lengths, range_frames: int = 0, scratch_bytes: int = 1 << 30, n_cu: int = 256, S: int = 1, model: int = 0,
+            features: bool = True, feat_dim=None) -> dict:
+    """What ``sr_bw_stats_batch`` decides for a model of K mixtures in D dimensions (model ``model`` of a set of S) and utterances of
+    ``lengths`` frames (csrc/bw_plan.cpp; no GPU needed when n_cu > 0): the refusals, the padded row width, one range's slab, the
+    range table ``ranges`` [n, 3] = (utterance, first row of the batch, rows), ranges per group, groups and the launch shapes."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    v = (C.c_int64 * 12)()
+    args = (int(S), int(model), int(K), int(D), 1 if features else 0, int(D if feat_dim is None else feat_dim), as_i64p(lengths), len(lengths),
+            int(range_frames), int(scratch_bytes), int(n_cu))
+    check(lib().sr_bw_plan(*args, None, 0, v, 12), "sr_bw_plan")
+    names = ("dp", "ncb", "n_mix_blocks", "slab_bytes", "n_ranges", "group_ranges", "n_groups", "lse_grid", "stats_lds", "reduce_blocks",
+             "stats_rounds", "auto_range")
+    d = dict(zip(names, (int(x) for x in v)))
+    ranges = np.zeros((d["n_ranges"], 3), dtype=np.int64)
+    check(lib().sr_bw_plan(*args, as_i64p(ranges), d["n_ranges"], v, 12), "sr_bw_plan")
+    d["ranges"] = ranges
+    return d
 
 
 def last_score_kernel() -> str:

@@ -206,6 +206,24 @@ class ModelSet:
                                             _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_score_batch_set_topc")
         return (sums, arg) + ((fll,) if frame_ll else ()) + ((sel,) if selection else ())
 
+    def bw_stats(self, feats: Batch, model: int = 0, ll: bool = False):
+        """Baum-Welch statistics of every utterance of a feature batch against model ``model`` of the set, the UBM
+        (sr_bw_stats_batch): -> (N[U, K], F[U, K * D][, ll[U], dropped[U]]), float64 (dropped: int64).  N[u, k] = sum_t gamma_k(t),
+        F[u, k * D + d] = sum_t gamma_k(t) x_t[d] (mixture-major, the supervector order), ll[u] the utterance's log-likelihood;
+        a frame whose log-sum-exp is not finite (a NaN row, values beyond every density's range) contributes nothing and is
+        counted in ``dropped``.  A PCM batch, a model index out of range, rows wider than 40 dimensions or a dimension mismatch
+        raise ``SRError`` before the device is touched."""
+        model = int(model)
+        K = self._keep[model].get_nr_mixtures() if 0 <= model < len(self._keep) else 0
+        U, D = feats.n_utt, self.dim
+        N = np.zeros((U, K), dtype=np.float64)
+        F = np.zeros((U, K * D), dtype=np.float64)
+        lls = np.zeros(U, dtype=np.float64)
+        dropped = np.zeros(U, dtype=np.int64)
+        check(lib().sr_bw_stats_batch(self._h, model, feats._h, _lib.as_dp(N), _lib.as_dp(F), _lib.as_dp(lls), _lib.as_i64p(dropped)),
+              "sr_bw_stats_batch")
+        return (N, F, lls, dropped) if ll else (N, F)
+
     def __del__(self):
         try:
             if self._h:

@@ -13,6 +13,7 @@
 #include "score.hpp"
 #include "silence_plan.hpp"
 #include "topc_plan.hpp"
+#include "bw_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -885,6 +886,43 @@ int sr_topc_plan(int K, int D, int S, int top_c, int64_t n_frames, int64_t scrat
     SR_CATCH(-1)
 }
 
+// ---- batched Baum-Welch statistics (bw_stats.hip).  Every refusal comes before the device is touched. ----
+
+int sr_bw_stats_batch(SRModelSet *set, int model, SRBatch *feats, double *N, double *F, double *ll, int64_t *dropped) {
+    SR_TRY
+    if (!set || !feats) fail("sr_bw_stats_batch: null argument");
+    bw_stats_batch(*set, model, *feats, N, F, ll, dropped);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_dim, const int64_t *lengths, int64_t n_utt,
+               int64_t range_frames, int64_t scratch_bytes, int n_cu, int64_t *ranges_out, int64_t range_cap, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 12) fail("sr_bw_plan writes 12 fields");
+    std::string why;
+    if (!bw_check(batch_is_features != 0, S, model, K, D, feat_dim, why)) fail("%s", why.c_str());
+    if (n_cu <= 0) {
+        ensure_device();
+        n_cu = ctx().n_cu;
+    }
+    BwPlan p;
+    if (!plan_bw(K, D, lengths, n_utt, range_frames, scratch_bytes, n_cu, p, why)) fail("%s", why.c_str());
+    const int64_t n = (int64_t)p.ranges.size();
+    const int64_t v[12] = {p.dp, p.ncb, p.n_mix_blocks, p.slab_bytes, n, p.group_ranges, p.n_groups, p.lse_grid, p.stats_lds,
+                           p.reduce_blocks, p.stats_rounds, bw_range_rows(0, K, D, range_frames)};
+    std::memcpy(out, v, sizeof v);
+    if (ranges_out)
+        for (int64_t i = 0; i < std::min(n, range_cap); i++) {
+            ranges_out[3 * i] = p.ranges[i].utt;
+            ranges_out[3 * i + 1] = p.ranges[i].first;
+            ranges_out[3 * i + 2] = p.ranges[i].rows;
+        }
+    return 12;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY
@@ -1046,6 +1084,12 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "topc_scratch_mib") {
         if (value < 1 || value > (1L << 20)) fail("topc_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(TOPC_DEFAULT_SCRATCH >> 20));
         set_topc_scratch_mib(value);
+    } else if (k == "bw_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("bw_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(BW_DEFAULT_SCRATCH >> 20));
+        set_bw_scratch_mib(value);
+    } else if (k == "bw_range_frames") {
+        if (value < 0 || value > (long)BW_MAX_RANGE_FRAMES) fail("bw_range_frames must be 0 (automatic) or 1 .. %ld frames", (long)BW_MAX_RANGE_FRAMES);
+        set_bw_range_frames(value);
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
         set_full_fit_batch_bytes(value);

@@ -108,7 +108,8 @@ T &per_device() {
 // ---- kernel timing with HIP events on OUR stream ----
 enum TimerKind { T_SCORE = 0, T_MFCC = 1, T_CMVN = 2, T_FINALIZE = 3, T_ESTEP = 4, T_SCORE_REF = 5,
                  T_TOPC_SELECT = 6, T_TOPC_ROUTE = 7, T_TOPC_EVAL = 8, T_TOPC_COMBINE = 9,      // the four stages of gmm_topc.hip
-                 T_COUNT = 10 };
+                 T_BW_LSE = 10, T_BW_STATS = 11, T_BW_REDUCE = 12,                              // the three passes of bw_stats.hip
+                 T_COUNT = 13 };
 struct ScopedKernelTimer {
     explicit ScopedKernelTimer(TimerKind k);
     ~ScopedKernelTimer();

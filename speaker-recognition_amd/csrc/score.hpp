@@ -231,6 +231,13 @@ void score_batch_set_topc(SRModelSet &set, SRBatch &feat, int bg, int top_c, dou
 bool topc_set_tied(SRModelSet &set);       // does the set qualify?  (host only; the answer is kept)
 void set_topc_scratch_mib(long v);
 long topc_scratch_mib();
+// bw_stats.hip: per-utterance Baum-Welch statistics N [U][K], F [U][K * D] (host memory) of the feature batch against model `model`
+// of the set; ll [U] / dropped [U]: host memory or null.  Refusals (bw_plan.cpp: bw_check) come before any device work.
+void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, double *F_out, double *ll_out, int64_t *dropped_out);
+void set_bw_scratch_mib(long v);
+long bw_scratch_mib();
+void set_bw_range_frames(long v);
+long bw_range_frames();
 // Packs + uploads a model set on the current device.
 void upload_model_set(SRModelSet &s);
 // a GMM handle's own one-model set on the current device, packed and uploaded once (abi.cpp; invalidated by GMM::drop_single)

@@ -131,6 +131,17 @@ class GMM(object):
                                         C.byref(s), _lib.SR_CLAMP_COMPAT), "score_all")
         return s.value
 
+    def bw_stats(self, utterances, ll=False):
+        """Baum-Welch statistics of a list of [T_u, dim] matrices against this model as the UBM, in one device pass
+        (core.ModelSet.bw_stats over a one-model set): -> (N[U, K], F[U, K * D][, ll[U], dropped[U]])."""
+        from .core import Batch, ModelSet
+        utts = list(utterances)
+        if utts:
+            feats = Batch.from_features(utts)
+        else:                                           # (an empty list carries no dimension: the model's)
+            feats = Batch.from_features(np.zeros((0, self.get_dim()), np.float32), np.zeros(1, np.int64))
+        return ModelSet([self]).bw_stats(feats, 0, ll=ll)
+
     def get_dim(self):
         return lib().get_dim(self.gmm)
 
