@@ -261,9 +261,18 @@ int sr_host_unregister(void *p);
 int sr_multi_slots(SRMulti *m);
 int sr_multi_slot_device(SRMulti *m, int slot);
 int sr_multi_slot_numa_node(SRMulti *m, int slot);      /* where the slot's host thread was pinned in its last pass (-1: nowhere) */
+int sr_multi_slot_pieces(SRMulti *m, int slot);         /* pieces the slot cut its utterances into in the last call (0: it took no work) */
 int sr_multi_predict_pcm(SRMulti *m, const int16_t *pcm, const int64_t *sample_offsets, int n_utt,
                          int nd, double *sums_out /*[U][S]*/, int *argmax_out /*[U]*/,
                          double *slot_seconds_out, int flags);
+/* sr_multi_plan: what such a call decides before it touches a device (csrc/multi_plan.cpp; host only), for tests.  devices:
+ * [n_slots] the slots' device indices; merge: the option multi_merge_same_device; schedules: [n_slots] every slot's piece schedule
+ * (0 = nearly equal pieces, 1 = growing ones; NULL: 0 for all).  Returns the number A of slots that take work, -1 on bad arguments.
+ * active_out [n_slots]: their slot indices; counts_out [n_slots]: utterances of each; utts_out [n_utt]: their utterance lists, one
+ * after the other, each ascending; pieces_out [n_slots][17]: per active slot the number of pieces n, then (u0, u1) of 8 pieces --
+ * ranges of the slot's list, a contiguous cover of it. */
+int sr_multi_plan(const int64_t *sample_offsets, int n_utt, const int *devices, int n_slots, int merge, const int *schedules,
+                  int *active_out, int *counts_out, int *utts_out, int *pieces_out);
 
 /* Measured device-to-device copy rate (bytes read + written per second, GB/s) of a `bytes`-sized
  * buffer over `iters` copies on the library's stream: the HBM ceiling bench.py quotes beside the

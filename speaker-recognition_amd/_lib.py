@@ -42,6 +42,7 @@ EXT_SYMBOLS = [
     "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
     "sr_score_batch_set_topc", "sr_predict_pcm_batch_topc", "sr_topc_plan",
     "sr_bw_stats_batch", "sr_bw_plan",
+    "sr_multi_slot_pieces", "sr_multi_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -208,6 +209,8 @@ def lib():
         "sr_topc_plan": (i32, [i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), i32]),
         "sr_bw_stats_batch": (i32, [vp, i32, vp, dp, dp, dp, C.POINTER(i64)]),
         "sr_bw_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i64), i64, i64, i64, i32, C.POINTER(i64), i64, C.POINTER(i64), i32]),
+        "sr_multi_slot_pieces": (i32, [vp, i32]),
+        "sr_multi_plan": (i32, [C.POINTER(i64), i32, C.POINTER(i32), i32, i32, C.POINTER(i32)] + [C.POINTER(i32)] * 4),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -412,6 +415,26 @@ def bw_plan(K: int, D: int, lengths, range_frames: int = 0, scratch_bytes: int =
     check(lib().sr_bw_plan(*args, as_i64p(ranges), d["n_ranges"], v, 12), "sr_bw_plan")
     d["ranges"] = ranges
     return d
+
+
+def multi_plan(offsets, devices, merge: bool = True, schedules=None) -> list:
+    """What ``sr_multi_predict_pcm`` decides for utterances at the cumulative sample ``offsets`` over slots on ``devices`` (one device
+    index per slot) before it touches a GPU (csrc/multi_plan.cpp; no GPU needed): for every slot that takes work a dict of its
+    ``slot`` index, its utterances ``utts`` (ascending) and its ``pieces`` [(u0, u1), ...], ranges of that list.  ``schedules``: a
+    slot's piece schedule, 0 (nearly equal pieces, the default) or 1 (growing ones)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    devices = np.ascontiguousarray(devices, dtype=np.int32)
+    n_utt, n_slots = len(offsets) - 1, len(devices)
+    sched = np.ascontiguousarray(schedules if schedules is not None else np.zeros(n_slots), dtype=np.int32)
+    if n_utt < 0 or len(sched) != n_slots:
+        raise ValueError("offsets holds U + 1 values, schedules one per slot")
+    active, counts = np.zeros(max(1, n_slots), np.int32), np.zeros(max(1, n_slots), np.int32)
+    utts, pieces = np.zeros(max(1, n_utt), np.int32), np.zeros((max(1, n_slots), 17), np.int32)
+    n = check(lib().sr_multi_plan(as_i64p(offsets), n_utt, as_i32p(devices), n_slots, 1 if merge else 0, as_i32p(sched), as_i32p(active),
+                                  as_i32p(counts), as_i32p(utts), as_i32p(pieces)), "sr_multi_plan")
+    ends = np.cumsum(counts[:n])
+    return [{"slot": int(active[a]), "utts": utts[ends[a] - counts[a]:ends[a]].tolist(),
+             "pieces": [(int(pieces[a, 1 + 2 * c]), int(pieces[a, 2 + 2 * c])) for c in range(pieces[a, 0])]} for a in range(n)]
 
 
 def last_score_kernel() -> str:

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fullcov_oracle as fo
+from multi_cases import long_utterances
 from conftest import ll_close
 
 pytestmark = pytest.mark.gpu
@@ -130,26 +131,12 @@ def test_stream_matches_the_fused_call_plain_and_graph():
     assert b"without deltas" in raw.sr_last_error()
 
 
-def _long_utterances(fs, n, rng):
-    """n int16 utterances of 0.4-9 s cut from a few synthetic speakers (several M samples in all), plus one without a frame."""
-    from speaker_recognition_amd import synth
-    base = [synth.synth_speech(9 * s, 60.0, fs, seed=300 + s) for s in range(6)]
-    out = []
-    for i in range(n):
-        b = base[i % len(base)]
-        L = int(rng.uniform(0.4, 9.0) * fs)
-        o = int(rng.integers(0, len(b) - L))
-        out.append(np.ascontiguousarray(b[o:o + L]))
-    out.insert(n // 2, np.zeros(100, np.int16))
-    return out
-
-
 def test_multi_predictor_matches_the_fused_call_for_any_slot_count():
     from speaker_recognition_amd import _lib
     from speaker_recognition_amd.core import Batch, MultiPredictor
     ex, gmms, fset = _setup(16000, 28, 15, 0, 7, seed=4)
     rng = np.random.default_rng(4)
-    sigs = _long_utterances(16000, 160, rng)
+    sigs = long_utterances(16000, 160, rng)
     assert sum(len(s) for s in sigs) > 3 * 2.2e6                   # several pieces per slot, also with three slots
     want_s, want_a = fset.predict_pcm(ex, Batch.from_pcm(sigs))
     assert want_a[80] == -1 and np.all(want_s[80] == 0.0)

@@ -668,6 +668,71 @@ def test_multi_slot_prediction_equals_single_device(built_lib):
             _lib.set_thread_device(0)
 
 
+def test_multi_slot_prediction_in_several_pieces_equals_single_device(built_lib):
+    """The same on utterances long enough (just over 3 x 2.2 M samples) that every slot cuts its share into several pieces, also
+    with three slots: the closed-set and the open-set call, from pageable and from page-locked PCM, reproduce the single-device
+    results bit for bit, and every slot cut exactly the pieces the plan (csrc/multi_plan.cpp through sr_multi_plan) says -- a
+    fresh predictor's first two calls run the equal-piece schedule (the estimate for a set this small; the vote needs two passes)."""
+    from multi_cases import long_utterances
+    from speaker_recognition_amd import _lib
+    from speaker_recognition_amd.core import Batch, MfccExtractor, ModelSet, MultiPredictor
+    from speaker_recognition_amd.pygmm import GMM
+    from speaker_recognition_amd import synth
+    kw = dict(win_length_ms=25, win_shift_ms=10)
+    models = [GMM.from_arrays(*synth.synth_gmm(64, 39, 7 + s)) for s in range(5)]
+    sigs = long_utterances(16000, 82, np.random.default_rng(6))
+    off = np.zeros(len(sigs) + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in sigs])
+    assert 3 * 2.2e6 < off[-1] < 3 * 2.2e6 * 1.15
+    ex, ms = MfccExtractor(16000, **kw), ModelSet(models)
+    want_sums, want_arg = ex.predict_batch(ms, Batch.from_pcm(sigs), nd=2)
+    assert want_arg[41] == -1                                       # the utterance without a frame
+    feats = ex.extract_batch(Batch.from_pcm(sigs), nd=2)
+    thr = float(np.nanmedian(ms.score_open(feats, 0, -np.inf)[2]))
+    _, want_lab, want_mar = ms.score_open(feats, 0, thr)
+    assert (want_lab >= 0).any() and (want_lab[np.arange(len(sigs)) != 41] < 0).any() and np.isnan(want_mar[41])
+
+    def pieces_as_planned(mp, merge, schedules=((0,),)):
+        plans = [_lib.multi_plan(off, mp.slot_devices(), bool(merge), list(s) * mp.n_slots) for s in schedules]
+        cut = mp.slot_pieces()
+        said = [[next((len(p["pieces"]) for p in plan if p["slot"] == k), 0) for k in range(mp.n_slots)] for plan in plans]
+        assert all(cut[k] in [s[k] for s in said] for k in range(mp.n_slots)), (merge, mp.n_slots, cut, said)
+        return cut
+
+    try:
+        several = 0
+        for merge in (0, 1):
+            _lib.set_option("multi_merge_same_device", merge)
+            for n_slots in (1, 2, 3):
+                mp, mo = (MultiPredictor(models, 16000, n_slots=n_slots, **kw) for _ in range(2))
+                for _ in range(2):                                   # (the second call reuses every piece's buffers)
+                    sums, arg = mp.predict(sigs, nd=2)
+                    assert np.array_equal(sums, want_sums) and np.array_equal(arg, want_arg), (merge, n_slots)
+                    several += max(pieces_as_planned(mp, merge)) > 1
+                    sums, lab, mar = mo.predict_open(sigs, 0, thr, nd=2)
+                    assert np.array_equal(sums, want_sums), (merge, n_slots)
+                    assert np.array_equal(lab, want_lab) and np.array_equal(mar, want_mar, equal_nan=True), (merge, n_slots)
+                    several += max(pieces_as_planned(mo, merge)) > 1
+        assert several == 24                                         # every call cut several pieces for some slot
+        # two more passes: what the first two measured may have changed the schedule (the vote) -- either shape, the same bits
+        for _ in range(2):
+            sums, arg = mp.predict(sigs, nd=2)
+            assert np.array_equal(sums, want_sums) and np.array_equal(arg, want_arg)
+            pieces_as_planned(mp, 1, ((0,), (1,)))
+    finally:
+        _lib.set_option("multi_merge_same_device", 1)
+    # page-locked PCM: the slots read the caller's buffer in place
+    cat = np.concatenate(sigs)
+    _lib.host_register(cat)
+    try:
+        mp = MultiPredictor(models, 16000, n_slots=2, **kw)
+        sums, arg = mp.predict_concat(cat, off, nd=2)
+    finally:
+        _lib.host_unregister(cat)
+    assert np.array_equal(sums, want_sums) and np.array_equal(arg, want_arg)
+    assert max(pieces_as_planned(mp, 1)) > 1
+
+
 def test_cfg0_at_stated_size_cli_vs_cpu_restatement(built_lib, tmp_path):
     """BASELINE configs[0] at its stated size: 10 speakers x 30 s of 16 kHz mono WAV to enroll, another
     10 x 30 s to predict, 25 ms / 10 ms frames (2998 frames per file), 13 MFCC, a 16-mixture diagonal GMM
