@@ -323,7 +323,14 @@ int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
 #define SR_T_BW_LSE 10       /* the three passes of sr_bw_stats_batch (csrc/bw_stats.hip): per-frame log-sum-exp, */
 #define SR_T_BW_STATS 11     /* the statistics on the fp64 matrix cores, */
 #define SR_T_BW_REDUCE 12    /* the sum of an utterance's slabs */
-#define SR_T_COUNT 13
+#define SR_T_JFA_GRAM 13     /* the stages of sr_jfa_factors / _update / _train (csrc/jfa.hip): W ./ E and the gram matrices P, */
+#define SR_T_JFA_GEMM_L 14   /* the float64 matrix-core GEMM's four products: L = I + N P, */
+#define SR_T_JFA_GEMM_B 15   /* b = Fc (W ./ E)^T, */
+#define SR_T_JFA_GEMM_A 16   /* A += N^T Q, */
+#define SR_T_JFA_GEMM_C 17   /* C += Y^T Fc, */
+#define SR_T_JFA_FACTOR 18   /* the batched factorisation of the groups' blocks, */
+#define SR_T_JFA_UPDATE 19   /* the factorisation and solve of the mixtures' blocks */
+#define SR_T_COUNT 20
 int sr_profile_enable(int on);
 int sr_profile_reset(void);
 int sr_profile_get(int kind, double *total_ms, long *launches);
@@ -347,6 +354,10 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    table runs in groups that fit.  Results do not depend on it, bit for bit.
  *   "bw_range_frames" frames per range of sr_bw_stats_batch (1 .. 2^30; 0 = automatic: max(1024, the utterance's length / 256 rounded
  *                    up to whole tiles of 128)).  Results depend on it in their last bits only.
+ *   "jfa_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the R x R float64 blocks sr_jfa_factors / _train keep at a time:
+ *                    the groups run in chunks that fit.  Results do not depend on it, bit for bit.
+ *   "jfa_lds_rows"   largest R whose blocks the JFA factorisation copies into LDS (1 .. 112; 0 = automatic: 112); above it the
+ *                    block is factored in place in global memory with panels in LDS.  1 forces that path at any R > 1.
  * The rest select kernel variants for A/B runs and tests. */
 int sr_set_option(const char *key, long value);
 /* Counters of the partial-product path since the library was loaded: resolve calls, (frame tile, model) pairs
@@ -564,6 +575,46 @@ int sr_bw_stats_batch(SRModelSet *set, int model, SRBatch *feats, double *N /*[U
 int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_dim, const int64_t *lengths, int64_t n_utt,
                int64_t range_frames, int64_t scratch_bytes, int n_cu, int64_t *ranges_out /*[range_cap][3] or NULL*/, int64_t range_cap,
                int64_t *out, int n_out);
+
+/* ---- JFA factor estimation (csrc/jfa.hip): the reference's estimate_y_and_v.m / estimate_x_and_u.m (src/jfa/; MATLAB there, one
+ * speaker at a time), which are one computation on different groups of rows -- what the statistics of sr_bw_stats_batch are for.
+ * A group g is a speaker (eigenvoices, or the stacked [v; u] of enrolment), or a session (eigenchannels; i-vectors with W = T).
+ * With occupancies N [G][K], CENTRED group-summed first-order statistics Fc [G][K * D] (the caller subtracts what the model
+ * already explains), variances E [K * D], a loading matrix W [R][K * D] (W_c = the D columns of mixture c), all float64:
+ *   P_c = W_c diag(1 / E_c) W_c^T          L_g = I + sum_c N[g][c] P_c          b_g = W (Fc_g ./ E)
+ *   y [G][R]      y_g = L_g^-1 b_g         Q_g = L_g^-1 + y_g y_g^T
+ *   A [K][R][R]   A_c = sum_g N[g][c] Q_g  C [R][K * D] = sum_g y_g Fc_g^T      update: W_c <- A_c^-1 C_c
+ * sr_jfa_open copies N, Fc and E to the device once: they do not change over the iterations of a training run.
+ * sr_jfa_factors: y, with A and C (both or neither) the accumulators; bad_groups (or NULL): groups whose L did not factor.
+ * sr_jfa_update: the update alone, on accumulators in host memory (sums of several sr_jfa_factors calls); W in: old, out: new.
+ * sr_jfa_train: n_iter rounds of factors -> accumulators -> update with W on the device throughout; W and, if asked, the y of the
+ * last round (estimated with the W that round started from, as the reference returns it) come back once.  The same bits as n_iter
+ * chained sr_jfa_factors + sr_jfa_update calls.  skipped (or NULL): mixtures the last round's update left alone.
+ * Stages: the gram matrices P; one float64 GEMM kernel on v_mfma_f64_16x16x4_f64 for L, b, A and C (ragged edges in every
+ * dimension); one workgroup per R x R block for Cholesky, two triangular solves, the explicit inverse and Q written over L.  The
+ * blocks of a chunk of groups live under "jfa_scratch_mib"; chunks are multiples of the GEMM's reduction step (16) and A and C are
+ * summed in group order across them: NO result depends on the bound, bit for bit; a group's y is the same bits alone and inside
+ * any batch; two runs are identical.  R up to 512; blocks of up to "jfa_lds_rows" rows are factored in LDS, larger ones in place.
+ * Degenerate inputs: a group whose N is all zero has L = I, y = b (0 exactly for centred statistics of no frames) and adds nothing
+ * to A; a group whose L does not factor (a pivot <= 0 or not finite: impossible with N >= 0, E > 0 short of overflow) gets y = 0,
+ * adds nothing to A and C and is counted -- nothing non-finite is spread; a mixture whose A_c does not factor (A_c = 0 when no
+ * group occupies c: the reference's inv() returns Inf there) keeps its old W_c and is counted in skipped.
+ * Refused, before the device is touched, with a message that names the remedy: G, K, D or R < 1, R above 512, a non-finite value
+ * in N, Fc, E, W (or in A, C given to sr_jfa_update), a negative N, E <= 0, a scratch bound below one chunk of 16 groups (or of
+ * all G, if fewer).  Refused in a process forked after the GPU runtime was initialised.
+ * sr_jfa_plan: what such a call decides (csrc/jfa_plan.cpp; host only when n_cu > 0, n_cu <= 0: the current device's), for tests.
+ * Writes 32 fields (n_out >= 32) and returns 32, -1 on refusal: groups per chunk, chunks, bytes of N, Fc, E (with 1 / E), P, A, C,
+ * W (with W ./ E), y (with b), bytes of a chunk's blocks, factorisation path (0 LDS, 1 global memory), largest R of the LDS path,
+ * gram grid x y, the grids x y of the L, b, A and C GEMM launches of a full chunk, LDS bytes of the gram, GEMM, factor and update
+ * kernels, rounds of a full chunk's factorisation over the chip, the reduction step, the built limits of R and of the LDS path, 0. */
+typedef struct SRJfa SRJfa;
+SRJfa *sr_jfa_open(int64_t G, int K, int D, const double *N /*[G][K]*/, const double *Fc /*[G][K*D]*/, const double *E /*[K*D]*/);
+int sr_jfa_factors(SRJfa *h, const double *W /*[R][K*D]*/, int R, double *y /*[G][R]*/, double *A /*[K][R][R] or NULL*/,
+                   double *C /*[R][K*D] or NULL*/, int64_t *bad_groups /*or NULL*/);
+int sr_jfa_update(int K, int D, int R, const double *A, const double *C, double *W /*in: old, out: new*/, int64_t *skipped /*or NULL*/);
+int sr_jfa_train(SRJfa *h, double *W /*in/out*/, int R, int n_iter, double *y /*[G][R] or NULL*/, int64_t *skipped /*or NULL*/);
+void sr_jfa_close(SRJfa *h);
+int sr_jfa_plan(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out, int n_out);
 
 #ifdef __cplusplus
 }

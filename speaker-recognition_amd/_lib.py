@@ -42,6 +42,7 @@ EXT_SYMBOLS = [
     "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
     "sr_score_batch_set_topc", "sr_predict_pcm_batch_topc", "sr_topc_plan",
     "sr_bw_stats_batch", "sr_bw_plan",
+    "sr_jfa_open", "sr_jfa_factors", "sr_jfa_update", "sr_jfa_train", "sr_jfa_close", "sr_jfa_plan",
     "sr_multi_slot_pieces", "sr_multi_plan",
 ]
 
@@ -51,6 +52,7 @@ SR_STREAM_GRAPH = 0x100
 T_SCORE, T_MFCC, T_CMVN, T_FINALIZE, T_ESTEP, T_SCORE_REF = 0, 1, 2, 3, 4, 5
 T_TOPC_SELECT, T_TOPC_ROUTE, T_TOPC_EVAL, T_TOPC_COMBINE = 6, 7, 8, 9      # the four stages of sr_score_batch_set_topc
 T_BW_LSE, T_BW_STATS, T_BW_REDUCE = 10, 11, 12                             # the three passes of sr_bw_stats_batch
+T_JFA_GRAM, T_JFA_GEMM_L, T_JFA_GEMM_B, T_JFA_GEMM_A, T_JFA_GEMM_C, T_JFA_FACTOR, T_JFA_UPDATE = 13, 14, 15, 16, 17, 18, 19      # sr_jfa_*'s stages
 
 
 class Parameter(C.Structure):
@@ -209,6 +211,12 @@ def lib():
         "sr_topc_plan": (i32, [i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), i32]),
         "sr_bw_stats_batch": (i32, [vp, i32, vp, dp, dp, dp, C.POINTER(i64)]),
         "sr_bw_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i64), i64, i64, i64, i32, C.POINTER(i64), i64, C.POINTER(i64), i32]),
+        "sr_jfa_open": (vp, [i64, i32, i32, dp, dp, dp]),
+        "sr_jfa_factors": (i32, [vp, dp, i32, dp, dp, dp, C.POINTER(i64)]),
+        "sr_jfa_update": (i32, [i32, i32, i32, dp, dp, dp, C.POINTER(i64)]),
+        "sr_jfa_train": (i32, [vp, dp, i32, i32, dp, C.POINTER(i64)]),
+        "sr_jfa_close": (None, [vp]),
+        "sr_jfa_plan": (i32, [i64, i32, i32, i32, i64, i32, i32, C.POINTER(i64), i32]),
         "sr_multi_slot_pieces": (i32, [vp, i32]),
         "sr_multi_plan": (i32, [C.POINTER(i64), i32, C.POINTER(i32), i32, i32, C.POINTER(i32)] + [C.POINTER(i32)] * 4),
     }
@@ -414,6 +422,24 @@ def bw_plan(K: int, D: int, lengths, range_frames: int = 0, scratch_bytes: int =
     ranges = np.zeros((d["n_ranges"], 3), dtype=np.int64)
     check(lib().sr_bw_plan(*args, as_i64p(ranges), d["n_ranges"], v, 12), "sr_bw_plan")
     d["ranges"] = ranges
+    return d
+
+
+JFA_PLAN_FIELDS = ("chunk", "n_chunks", "bytes_N", "bytes_Fc", "bytes_E", "bytes_P", "bytes_A", "bytes_C", "bytes_W", "bytes_y",
+                   "bytes_scratch", "path", "lds_rows", "gram_grid_x", "gram_grid_y", "gemm_L_x", "gemm_L_y", "gemm_b_x", "gemm_b_y",
+                   "gemm_A_x", "gemm_A_y", "gemm_C_x", "gemm_C_y", "gram_lds", "gemm_lds", "factor_lds", "update_lds", "factor_rounds",
+                   "k_step", "max_R", "max_lds_rows")
+
+
+def jfa_plan(G: int, K: int, D: int, R: int, scratch_bytes: int = 1 << 30, lds_rows: int = 0, n_cu: int = 256) -> dict:
+    """What ``sr_jfa_factors`` / ``sr_jfa_train`` decide for G groups, a K x D model and R factors under a scratch bound and the
+    option ``jfa_lds_rows`` (csrc/jfa_plan.cpp; no GPU needed when n_cu > 0): the refusals, groups per chunk, chunks, the bytes of
+    each resident array, the factorisation ``path`` ("lds" or "global"), the grids of the gram and the four GEMM launches, and
+    every kernel's LDS bytes."""
+    v = (C.c_int64 * 32)()
+    check(lib().sr_jfa_plan(int(G), int(K), int(D), int(R), int(scratch_bytes), int(lds_rows), int(n_cu), v, 32), "sr_jfa_plan")
+    d = dict(zip(JFA_PLAN_FIELDS, (int(x) for x in v)))
+    d["path"] = ("lds", "global")[d["path"]]
     return d
 
 

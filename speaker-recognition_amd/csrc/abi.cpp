@@ -14,6 +14,7 @@
 #include "silence_plan.hpp"
 #include "topc_plan.hpp"
 #include "bw_plan.hpp"
+#include "jfa_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -923,6 +924,65 @@ int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_d
     SR_CATCH(-1)
 }
 
+// ---- JFA factor estimation (jfa.hip).  Every refusal comes before the device is touched. ----
+
+SRJfa *sr_jfa_open(int64_t G, int K, int D, const double *N, const double *Fc, const double *E) {
+    SR_TRY
+    return jfa_open(G, K, D, N, Fc, E);
+    SR_CATCH(nullptr)
+}
+
+int sr_jfa_factors(SRJfa *h, const double *W, int R, double *y, double *A, double *C, int64_t *bad_groups) {
+    SR_TRY
+    if (!h) fail("sr_jfa_factors: null argument");
+    jfa_factors(*h, W, R, y, A, C, bad_groups);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_update(int K, int D, int R, const double *A, const double *C, double *W, int64_t *skipped) {
+    SR_TRY
+    jfa_update(K, D, R, A, C, W, skipped);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_train(SRJfa *h, double *W, int R, int n_iter, double *y, int64_t *skipped) {
+    SR_TRY
+    if (!h) fail("sr_jfa_train: null argument");
+    jfa_train(*h, W, R, n_iter, y, skipped);
+    return 0;
+    SR_CATCH(-1)
+}
+
+void sr_jfa_close(SRJfa *h) {
+    SR_TRY
+    jfa_close(h);
+    SR_CATCH_VOID
+}
+
+int sr_jfa_plan(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 32) fail("sr_jfa_plan writes 32 fields");
+    std::string why;
+    JfaPlan p;
+    if (n_cu > 0) {
+        if (!plan_jfa(G, K, D, R, scratch_bytes, lds_rows, n_cu, p, why)) fail("%s", why.c_str());
+    } else {
+        if (!plan_jfa(G, K, D, R, scratch_bytes, lds_rows, 1, p, why)) fail("%s", why.c_str());      // the refusals first
+        ensure_device();
+        if (!plan_jfa(G, K, D, R, scratch_bytes, lds_rows, ctx().n_cu, p, why)) fail("%s", why.c_str());
+    }
+    const int64_t v[32] = {p.chunk, p.n_chunks, p.bytes_N, p.bytes_Fc, p.bytes_E, p.bytes_P, p.bytes_A, p.bytes_C, p.bytes_W, p.bytes_y,
+                           p.bytes_scratch, p.path, p.lds_rows, p.gram.x, p.gram.y, p.gemm_L.x, p.gemm_L.y, p.gemm_b.x, p.gemm_b.y,
+                           p.gemm_A.x, p.gemm_A.y, p.gemm_C.x, p.gemm_C.y, p.gram_lds, p.gemm_lds, p.factor_lds, p.update_lds,
+                           p.factor_rounds, JFA_KSTEP, JFA_MAX_R, JFA_LDS_MAX_R, 0};
+    std::memcpy(out, v, sizeof v);
+    return 32;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY
@@ -1090,6 +1150,12 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "bw_range_frames") {
         if (value < 0 || value > (long)BW_MAX_RANGE_FRAMES) fail("bw_range_frames must be 0 (automatic) or 1 .. %ld frames", (long)BW_MAX_RANGE_FRAMES);
         set_bw_range_frames(value);
+    } else if (k == "jfa_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("jfa_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(JFA_DEFAULT_SCRATCH >> 20));
+        set_jfa_scratch_mib(value);
+    } else if (k == "jfa_lds_rows") {
+        if (value < 0 || value > JFA_LDS_MAX_R) fail("jfa_lds_rows must be 0 (automatic) or 1 .. %d rows", JFA_LDS_MAX_R);
+        set_jfa_lds_rows(value);
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
         set_full_fit_batch_bytes(value);

@@ -109,7 +109,9 @@ T &per_device() {
 enum TimerKind { T_SCORE = 0, T_MFCC = 1, T_CMVN = 2, T_FINALIZE = 3, T_ESTEP = 4, T_SCORE_REF = 5,
                  T_TOPC_SELECT = 6, T_TOPC_ROUTE = 7, T_TOPC_EVAL = 8, T_TOPC_COMBINE = 9,      // the four stages of gmm_topc.hip
                  T_BW_LSE = 10, T_BW_STATS = 11, T_BW_REDUCE = 12,                              // the three passes of bw_stats.hip
-                 T_COUNT = 13 };
+                 T_JFA_GRAM = 13, T_JFA_GEMM_L = 14, T_JFA_GEMM_B = 15, T_JFA_GEMM_A = 16, T_JFA_GEMM_C = 17,     // the stages of jfa.hip:
+                 T_JFA_FACTOR = 18, T_JFA_UPDATE = 19,                                          // the gram matrices, the four products, the two factorisations
+                 T_COUNT = 20 };
 struct ScopedKernelTimer {
     explicit ScopedKernelTimer(TimerKind k);
     ~ScopedKernelTimer();

@@ -238,6 +238,20 @@ void set_bw_scratch_mib(long v);
 long bw_scratch_mib();
 void set_bw_range_frames(long v);
 long bw_range_frames();
+}  // namespace sr
+struct SRJfa;
+namespace sr {
+// jfa.hip: JFA factor estimation on resident statistics (eigenvoices, eigenchannels; jfa_plan.hpp has the formulas).  Every
+// refusal (jfa_plan.cpp) comes before any device work.  Host pointers throughout; W [R][K D] in / out where it says so.
+SRJfa *jfa_open(int64_t G, int K, int D, const double *N, const double *Fc, const double *E);
+void jfa_factors(SRJfa &h, const double *W, int R, double *y, double *A, double *C, int64_t *bad_groups);
+void jfa_update(int K, int D, int R, const double *A, const double *C, double *W, int64_t *skipped);
+void jfa_train(SRJfa &h, double *W, int R, int n_iter, double *y, int64_t *skipped);
+void jfa_close(SRJfa *h);
+void set_jfa_scratch_mib(long v);
+long jfa_scratch_mib();
+void set_jfa_lds_rows(long v);
+long jfa_lds_rows();
 // Packs + uploads a model set on the current device.
 void upload_model_set(SRModelSet &s);
 // a GMM handle's own one-model set on the current device, packed and uploaded once (abi.cpp; invalidated by GMM::drop_single)

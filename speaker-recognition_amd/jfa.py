@@ -8,8 +8,20 @@ supervector order -- mixture-major, D values per mixture, what ``reshape(F, n_mi
 ``data * gammas'`` is.  One difference in arithmetic: the posteriors are formed in the log domain, so a frame whose linear-domain
 densities would all underflow -- where ``gaussian_posteriors.m`` divides 0 by 0 and every statistic of the session turns NaN --
 contributes like any other frame; only a frame whose log-sum-exp is not finite (a NaN row, values beyond every density's range)
-is left out."""
+is left out.
+
+Past the statistics, the rest of that leg: ``estimate_y_and_v``, ``estimate_x_and_u`` (csrc/jfa.hip through ``FactorEstimator``:
+the gram matrices, the float64 GEMMs and the batched factorisation on the device), ``estimate_z_and_d`` and ``linear_scoring``
+(elementwise work and one small product: host, float64, as ``map_supervectors``), and the four ``sc_*`` driver scripts as the
+functions ``train_v``, ``train_u``, ``train_d`` and ``score_dot_product``.  Names, argument order and orientation are the
+reference's: rows of ``F`` and ``N`` are segments, supervector columns are mixture-major, ``S`` is accepted and ignored, a scalar
+``0`` for ``d``, ``u``, ``z``, ``y`` or ``x`` broadcasts as it does in MATLAB.  One stated difference: ``spk_ids`` are 0-BASED
+integer labels -- row i of ``y`` and ``z`` belongs to label i, rows of labels that do not occur stay zero.  Where the reference's
+``inv`` of an unoccupied mixture's accumulator gives Inf, the update here keeps that mixture's old columns (zeros in the
+two-argument form, which has no old matrix)."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
@@ -69,3 +81,308 @@ def map_supervectors(N, F, ubm, relevance=16.0):
         raise ValueError("relevance must be positive")
     out = (F.reshape(-1, K, D) + relevance * mu[None]) / (N[:, :, None] + relevance)
     return out.reshape(-1, K * D)
+
+
+# ---- factor estimation: eigenvoices, eigenchannels (csrc/jfa.hip) ----
+
+def _f64(a, shape=None, name="array"):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if shape is not None and a.shape != shape:
+        raise ValueError("expected %s of shape %r, got %r" % (name, shape, a.shape))
+    return a
+
+
+class FactorEstimator:
+    """The device handle of one set of groups (speakers, or sessions): occupancies ``N`` [G, K], CENTRED group-summed first-order
+    statistics ``Fc`` [G, K * D] and the variances ``E`` [K * D] are copied to the device once and stay there over the iterations
+    of a training run (``sr_jfa_open``).  A context manager.  ``bad_groups`` / ``skipped``: the counts of the last call."""
+
+    def __init__(self, N, Fc, E):
+        from . import _lib
+        N = _f64(np.atleast_2d(N))
+        Fc = _f64(np.atleast_2d(Fc))
+        E = _f64(np.reshape(E, -1))
+        G, K = N.shape
+        if K < 1 or E.size % max(K, 1) or Fc.shape != (G, E.size):
+            raise ValueError("expected N [G, K], Fc [G, K * D], E [K * D]; got %r, %r, %r" % (N.shape, Fc.shape, E.shape))
+        self.G, self.K, self.D = G, K, E.size // K
+        self.bad_groups = self.skipped = 0
+        self._h = None
+        self._h = _lib.check(_lib.lib().sr_jfa_open(G, K, self.D, _lib.as_dp(N), _lib.as_dp(Fc), _lib.as_dp(E)), "sr_jfa_open")
+
+    def _loadings(self, W):
+        W = np.array(np.atleast_2d(W), dtype=np.float64, order="C")
+        if W.shape[1] != self.K * self.D:
+            raise ValueError("expected W [R, %d], got %r" % (self.K * self.D, W.shape))
+        return W
+
+    def factors(self, W, accumulate=False):
+        """-> ``y`` [G, R], or with ``accumulate`` ``(y, A [K, R, R], C [R, K * D])``."""
+        from . import _lib
+        if self._h is None:
+            raise _lib.SRError("the estimator is closed")
+        W = self._loadings(W)
+        R = W.shape[0]
+        y = np.zeros((self.G, R))
+        A = np.zeros((self.K, R, R)) if accumulate else None
+        Cm = np.zeros_like(W) if accumulate else None
+        bad = C.c_int64(0)
+        _lib.check(_lib.lib().sr_jfa_factors(self._h, _lib.as_dp(W), R, _lib.as_dp(y), _lib.as_dp(A) if accumulate else None,
+                                             _lib.as_dp(Cm) if accumulate else None, C.byref(bad)), "sr_jfa_factors")
+        self.bad_groups = int(bad.value)
+        return (y, A, Cm) if accumulate else y
+
+    def train(self, W, n_iter):
+        """``n_iter`` rounds of factors -> accumulators -> update in one device call.  -> ``(W, y)``, ``y`` of the last round."""
+        from . import _lib
+        if self._h is None:
+            raise _lib.SRError("the estimator is closed")
+        W = self._loadings(W)
+        R = W.shape[0]
+        y = np.zeros((self.G, R))
+        sk = C.c_int64(0)
+        _lib.check(_lib.lib().sr_jfa_train(self._h, _lib.as_dp(W), R, int(n_iter), _lib.as_dp(y), C.byref(sk)), "sr_jfa_train")
+        self.skipped = int(sk.value)
+        return W, y
+
+    def close(self):
+        if self._h is not None:
+            from . import _lib
+            _lib.lib().sr_jfa_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def update_loadings(A, Cm, W_old, return_skipped=False):
+    """The update alone: ``W_c = A_c^-1 C_c`` for every mixture whose ``A_c`` factors; the others keep ``W_old``'s columns.
+    -> W (or ``(W, skipped)``)."""
+    from . import _lib
+    A = _f64(A)
+    Cm = _f64(np.atleast_2d(Cm))
+    if A.ndim != 3 or A.shape[1] != A.shape[2] or A.shape[1] != Cm.shape[0] or A.shape[0] < 1 or Cm.shape[1] % max(A.shape[0], 1):
+        raise ValueError("expected A [K, R, R] and C [R, K * D]; got %r and %r" % (A.shape, Cm.shape))
+    K, R = A.shape[0], A.shape[1]
+    W = np.array(np.broadcast_to(np.asarray(W_old, dtype=np.float64), Cm.shape), dtype=np.float64, order="C")
+    sk = C.c_int64(0)
+    _lib.check(_lib.lib().sr_jfa_update(K, Cm.shape[1] // K, R, _lib.as_dp(A), _lib.as_dp(Cm), _lib.as_dp(W), C.byref(sk)), "sr_jfa_update")
+    return (W, int(sk.value)) if return_skipped else W
+
+
+def _labels(spk_ids, n):
+    ids = np.asarray(spk_ids).reshape(-1)
+    if ids.shape != (n,) or not np.issubdtype(ids.dtype, np.integer) or (n and ids.min() < 0):
+        raise ValueError("spk_ids: %d 0-based integer labels, one per row of F and N" % n)
+    return ids.astype(np.int64)
+
+
+def _rows(a, n, width):
+    """A factor matrix as [n, width]: a scalar, a column of n values or a full matrix -- MATLAB's broadcast of the sc_* scripts."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim < 2:
+        a = a.reshape(-1, 1) if a.size > 1 else a.reshape(1, 1)
+    if a.shape[0] < n and a.shape[0] != 1:
+        raise ValueError("a factor matrix has %d rows, the labels need %d" % (a.shape[0], n))
+    return np.broadcast_to(a[:n] if a.shape[0] >= n else a, (n, width if a.shape[1] == 1 else a.shape[1]))
+
+
+def _times(f, W, n, kd):
+    """f * W as [n, kd]: a matrix product when W is a loading matrix, the elementwise broadcast when it is the scalar 0."""
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim < 2:
+        return np.broadcast_to(_rows(f, n, 1)[:, :1] * W, (n, kd)) if W.size == 1 else _rows(f, n, kd) * W.reshape(1, kd)
+    return _rows(f, n, W.shape[0]) @ W
+
+
+def _zd(z, d, n, kd):
+    """z .* d as [n, kd] (d: the scalar 0 or a vector of kd values)."""
+    return _rows(z, n, kd) * np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (kd,))
+
+
+def _stats(F, N, m, E):
+    F = _f64(np.atleast_2d(F))
+    N = _f64(np.atleast_2d(N))
+    n, K = N.shape
+    if K < 1 or F.shape[0] != n or F.shape[1] % K:
+        raise ValueError("expected N [n, K] and F [n, K * D]; got %r and %r" % (N.shape, F.shape))
+    kd = F.shape[1]
+    return F, N, np.repeat(N, kd // K, axis=1), _f64(np.reshape(m, -1), (kd,), "m"), _f64(np.reshape(E, -1), (kd,), "E")
+
+
+def _speaker_sums(a, ids, n_spk):
+    out = np.zeros((n_spk,) + a.shape[1:])
+    np.add.at(out, ids, a)
+    return out
+
+
+def _finish(est, W, nargout):
+    if nargout == 1:
+        return est.factors(W), None, None
+    f, A, Cm = est.factors(W, accumulate=True)
+    return f, A, Cm
+
+
+def estimate_y_and_v(F, N, S=None, m=None, E=None, d=0, v=None, u=0, z=0, y=0, x=0, spk_ids=None, nargout=1):
+    """estimate_y_and_v.m: speaker factors ``y`` [max label + 1, R] (``nargout`` 1), ``(y, v)`` with the updated eigenvoices (2) or
+    ``(y, A, C)`` with the accumulators (3); ``estimate_y_and_v(A, C)`` updates from accumulators.  Groups are speakers; the
+    centring ``Fs = sum_sessions F - (m + z d) Ns - sum_j (x_j u) N_j`` is done here in float64, the rest on the device."""
+    if m is None:
+        return update_loadings(F, N, 0.0)
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    n, kd = F.shape
+    ids = _labels(spk_ids, n)
+    n_spk = int(ids.max()) + 1 if n else 0
+    W = _f64(np.atleast_2d(v))
+    present = np.unique(ids)
+    Fs = _speaker_sums(F - _times(x, u, n, kd) * Nx, ids, n_spk) - (m + _zd(z, d, n_spk, kd)) * _speaker_sums(Nx, ids, n_spk)
+    Ns = _speaker_sums(N, ids, n_spk)
+    out = np.zeros((n_spk, W.shape[0]))
+    with FactorEstimator(Ns[present], Fs[present], E) as est:
+        f, A, Cm = _finish(est, W, nargout)
+    out[present] = f
+    if nargout == 1:
+        return out
+    return (out, A, Cm) if nargout == 3 else (out, update_loadings(A, Cm, W))
+
+
+def estimate_x_and_u(F, N, S=None, m=None, E=None, d=0, v=0, u=None, z=0, y=0, x=0, spk_ids=None, nargout=1):
+    """estimate_x_and_u.m: channel factors ``x`` [n_sessions, R], ``(x, u)`` or ``(x, A, C)``; ``estimate_x_and_u(A, C)`` updates
+    from accumulators.  Every session is its own group, ``Fh = F_j - N_j (m + y v + z d)`` with its speaker's y and z."""
+    if m is None:
+        return update_loadings(F, N, 0.0)
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    n, kd = F.shape
+    ids = _labels(spk_ids, n)
+    n_spk = int(ids.max()) + 1 if n else 0
+    W = _f64(np.atleast_2d(u))
+    shift = m + _times(y, v, n_spk, kd) + _zd(z, d, n_spk, kd)
+    Fh = F - Nx * shift[ids]
+    with FactorEstimator(N, Fh, E) as est:
+        f, A, Cm = _finish(est, W, nargout)
+    if nargout == 1:
+        return f
+    return (f, A, Cm) if nargout == 3 else (f, update_loadings(A, Cm, W))
+
+
+def estimate_z_and_d(F, N, S=None, m=None, E=None, d=0, v=0, u=0, z=0, y=0, x=0, spk_ids=None, nargout=1):
+    """estimate_z_and_d.m on the host in float64: ``z`` [max label + 1, K * D], ``(z, d)`` or ``(z, a, b)``;
+    ``estimate_z_and_d(a, b)`` gives ``d = b / a``."""
+    if m is None:
+        return np.asarray(N, dtype=np.float64) / np.asarray(F, dtype=np.float64)
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    n, kd = F.shape
+    ids = _labels(spk_ids, n)
+    n_spk = int(ids.max()) + 1 if n else 0
+    dv = np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (kd,))
+    Ns = _speaker_sums(Nx, ids, n_spk)
+    Fs = _speaker_sums(F - _times(x, u, n, kd) * Nx, ids, n_spk) - (m + _times(y, v, n_spk, kd)) * Ns
+    L = 1.0 + Ns / E * dv ** 2
+    zz = Fs / E * dv / L
+    present = np.zeros(n_spk, dtype=bool)
+    present[ids] = True
+    zz[~present] = 0.0
+    if nargout == 1:
+        return zz
+    a = ((1.0 / L + zz ** 2) * Ns)[present].sum(axis=0)
+    b = (zz * Fs)[present].sum(axis=0)
+    return (zz, a, b) if nargout == 3 else (zz, b / a)
+
+
+def linear_scoring(F, N, S=None, m=None, E=None, d=0, v=0, u=0, z=0, y=0, x=0, scores=None):
+    """linear_scoring.m on the host in float64: -> [n_models, n_segments], the models ``z d + y v`` divided by E against the
+    channel-compensated, count-normalised first-order statistics of the segments."""
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    n, kd = F.shape
+    y = np.atleast_2d(np.asarray(y, dtype=np.float64))
+    n_mod = y.shape[0]
+    dv = np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (kd,))
+    M = (_rows(z, n_mod, kd) * dv + _times(y, v, n_mod, kd)) / E
+    Fc = (F - (m + _times(x, u, n, kd)) * Nx) / N.sum(axis=1, keepdims=True)
+    return M @ Fc.T
+
+
+def _ubm_m_E(ubm):
+    """(m, E) supervectors [K * D] of a UBM given as ``as_ubm`` takes it."""
+    if isinstance(ubm, GMM):
+        _, mu, sg = ubm.params()
+        var = np.asarray(sg, dtype=np.float64) ** 2
+    elif hasattr(ubm, "keys"):
+        mu, var = ubm["means"], ubm["variances"]
+    else:
+        mu, var = ubm[1], ubm[2]
+    return np.asarray(mu, dtype=np.float64).reshape(-1), np.asarray(var, dtype=np.float64).reshape(-1)
+
+
+def random_loadings(n_rows, E, seed=0):
+    """The sc_* scripts' random start ``randn(n, K D) * sum(E) * 0.001`` from ``numpy.random.RandomState(seed)`` -- not MATLAB's
+    stream: a run here starts from other numbers than a run of the scripts."""
+    E = np.asarray(E, dtype=np.float64).reshape(-1)
+    return np.random.RandomState(seed).randn(int(n_rows), E.size) * E.sum() * 0.001
+
+
+def train_v(F, N, spk_ids, ubm, ny=300, niter=10, v0=None, seed=0):
+    """sc_train_v_from_files.m: ``niter`` rounds of ``[y, v] = estimate_y_and_v(F, N, S, m, E, 0, v, 0, 0, 0, 0, spk_ids)`` from the
+    random start (or ``v0``), as ONE device call.  -> v [ny, K * D]."""
+    m, E = _ubm_m_E(ubm)
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    ids = _labels(spk_ids, F.shape[0])
+    present = np.unique(ids)
+    n_spk = int(ids.max()) + 1
+    Ns = _speaker_sums(N, ids, n_spk)
+    Fs = _speaker_sums(F, ids, n_spk) - m * _speaker_sums(Nx, ids, n_spk)
+    v = random_loadings(ny, E, seed) if v0 is None else v0
+    with FactorEstimator(Ns[present], Fs[present], E) as est:
+        return est.train(v, niter)[0]
+
+
+def train_u(F, N, spk_ids, ubm, v, nx=300, niter=10, u0=None, seed=0):
+    """sc_train_u_from_files.m: y once from ``v``, then ``niter`` rounds of ``[x, u] = estimate_x_and_u(...)`` with that y fixed, as
+    one device call.  -> u [nx, K * D]."""
+    m, E = _ubm_m_E(ubm)
+    y = estimate_y_and_v(F, N, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
+    F, N, Nx, m, E = _stats(F, N, m, E)
+    ids = _labels(spk_ids, F.shape[0])
+    Fh = F - Nx * (m + y @ _f64(np.atleast_2d(v)))[ids]
+    u = random_loadings(nx, E, seed) if u0 is None else u0
+    with FactorEstimator(N, Fh, E) as est:
+        return est.train(u, niter)[0]
+
+
+def train_d(F, N, spk_ids, ubm, v, u, niter=10, d0=None, seed=0):
+    """sc_train_d_from_files.m: y and x once, then ``niter`` rounds of ``[z, d] = estimate_z_and_d(...)`` (host).  -> d [K * D]."""
+    m, E = _ubm_m_E(ubm)
+    y = estimate_y_and_v(F, N, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
+    x = estimate_x_and_u(F, N, None, m, E, 0, v, u, 0, y, 0, spk_ids)
+    d = random_loadings(1, E, seed)[0] if d0 is None else np.asarray(d0, dtype=np.float64).reshape(-1)
+    for _ in range(int(niter)):
+        _, d = estimate_z_and_d(F, N, None, m, E, d, v, u, 0, y, x, spk_ids, nargout=2)
+    return d
+
+
+def score_dot_product(trn, tst, ubm, v, u, d):
+    """sc_score_dot_product.m: every enrolment segment a speaker of its own; y and x jointly on the stacked [v; u], z, the test
+    segments' channel factors against the UBM, then ``linear_scoring``.  ``trn`` / ``tst``: ``(F, N)`` pairs or mappings with
+    those keys.  -> scores [n_enrolment, n_test]."""
+    m, E = _ubm_m_E(ubm)
+    tF, tN = (trn["F"], trn["N"]) if hasattr(trn, "keys") else trn
+    sF, sN = (tst["F"], tst["N"]) if hasattr(tst, "keys") else tst
+    v = _f64(np.atleast_2d(v))
+    u = _f64(np.atleast_2d(u))
+    ny = v.shape[0]
+    vu = np.vstack([v, u])
+    trn_ids = np.arange(np.atleast_2d(tN).shape[0])
+    tst_ids = np.arange(np.atleast_2d(sN).shape[0])
+    yx = estimate_y_and_v(tF, tN, None, m, E, d, vu, 0, 0, 0, 0, trn_ids)
+    trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
+    tst_x = estimate_x_and_u(sF, sN, None, m, E, d, v, u, 0, 0, 0, tst_ids)
+    return linear_scoring(sF, sN, None, m, E, d, v, u, trn_z, yx[:, :ny], tst_x)
