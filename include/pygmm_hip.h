@@ -309,7 +309,45 @@ int sr_ltsd_compute(SRBatch *pcm, int winsize, int order, const float *noise_amp
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed);
 
-/* Kernel timing by HIP events on the library's own stream. */
+/* ---- A set of speakers MAP-adapted from ONE UBM in one batched device fit (csrc/map_batch.hip) ----
+ * S >= 1 handles (new_gmm; their mixture count is replaced by the UBM's, as train_model_from_ubm does) fitted together on the
+ * speakers' frames X ([row_offsets[S]][dim] fp32, speaker s owns rows row_offsets[s] .. row_offsets[s + 1]): every pass is one
+ * set of launches for a whole group of speakers, the stop rule (gmm.cc:622-650) is applied per speaker on the device, and the host
+ * reads one word -- the speakers still active -- where the rule is taken.  Every fitted speaker's model and iterations_out[s] are
+ * the bits and the count sr_train_f32(models[s], ubm, its rows, ...) gives for that speaker alone, for every batch size, order of
+ * speakers and scratch bound.  status[s]: 0 fitted in the batch; 1 fitted by the single fit (its shape is outside the float64
+ * iteration engine's, or speaker-sized: the whole-fit kernel's); 2 handed over (a live frame near the underflow boundary or a NaN
+ * density: refitted alone, the iteration-at-a-time path, as its single fit takes it); -1 failed (the handle keeps its parameters;
+ * sr_map_fit_batch_error(s) gives the reason -- a speaker without frames: "X.size() == 0").  A failing speaker fails alone.
+ * Returns the number of speakers fitted, or -1 when the call itself is refused (sr_last_error()); every argument is checked before
+ * the device is touched: no null pointer, S >= 1, offsets from 0 that do not decrease, a trained UBM of `dim` dimensions, no handle
+ * twice.  With param->verbosity >= 1, "reference_side_effects" on or "em_stats_engine" != 0 the whole call runs as single fits.
+ * seed < 0: libc's stream advances by 1 + K per fitted speaker, as the loop of single fits advances it.  The batched speakers run
+ * in groups whose float64 scratch stays under sr_set_option("map_fit_batch_bytes", bytes) (>= 1; default 1 GiB; a speaker above
+ * it is a group of its own); the cut does not show in any result.  Fails in a process forked after GPU initialisation. */
+int sr_map_fit_batch(GMM *const *models, int S, GMM *ubm, const float *X, const int64_t *row_offsets, int dim,
+                     const struct Parameter *param, long seed, int *iterations_out, int *status);
+/* Why speaker s of the calling thread's last sr_map_fit_batch failed ("" when it did not, or s is out of range).  The pointer is
+ * valid until that thread's next sr_map_fit_batch. */
+const char *sr_map_fit_batch_error(int s);
+/* Counters since the library was loaded: sr_map_fit_batch calls that reached the device, the speakers fitted in a batch, by the
+ * single fit (routed there) and handed over, and the passes launched (one per set of launches, whatever the number of speakers in
+ * it).  Any pointer may be NULL. */
+void sr_map_fit_batch_stats(long *calls, long *speakers_batched, long *speakers_single, long *speakers_handed_over, long *passes);
+/* The current value of the option "map_fit_batch_bytes". */
+long sr_map_fit_batch_bytes(void);
+/* What such a call decides (csrc/map_plan.cpp; host only when n_cu > 0, n_cu <= 0: the current device's), for tests.  out [12]:
+ * speakers batched, single, failing, groups, rows of the density table, rows of the chunk table, mixture blocks (the grids' y),
+ * LDS bytes of a density / a statistics workgroup, the largest group's scratch bytes, rounds of its density launch over the chip,
+ * doubles of a speaker's state.  speakers_out [S][6] (may be NULL): route (0 batched, 1 single, -1 failing), group, slot in the
+ * group, frames padded to whole density tiles, 64-frame chunks, scratch bytes.  groups_out [group_cap][6] (may be NULL): first
+ * speaker, speakers, density tiles (grid x), chunks (grid x), scratch bytes, first row of the density table.  tiles_out /
+ * chunks_out [cap][3] (may be NULL): speaker, its first row in the batch, local tile.  Returns 12, or -1 with the reason. */
+int sr_map_fit_plan(int K, int D, const int64_t *lengths, int S, const struct Parameter *param, int64_t scratch_bytes, int n_cu,
+                    int64_t *speakers_out, int64_t *groups_out, int64_t group_cap, int64_t *tiles_out, int64_t tile_cap,
+                    int64_t *chunks_out, int64_t chunk_cap, int64_t *out, int n_out);
+
+/* Kernel timing by HIP events on the library's own stream.  (The batched passes of sr_map_fit_batch count under SR_T_ESTEP.) */
 #define SR_T_SCORE 0
 #define SR_T_MFCC 1
 #define SR_T_CMVN 2
@@ -348,6 +386,8 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    node, intersected with the mask the thread already has),
  *   "multi_merge_same_device" 0: slots that share a device get a host thread each (default 1: one queue per device).
  *   "full_fit_batch_bytes" the workspace bound, in bytes (>= 1; default 1 GiB), of a group of speakers in sr_fullgmm_fit_batch.
+ *   "map_fit_batch_bytes" the bound, in bytes (>= 1; default 1 GiB), of the float64 scratch of a group of speakers in sr_map_fit_batch.
+ *                    Results do not depend on it, bit for bit.
  *   "silence_block"  positions per block of sr_silence_remove_batch's walk (1 .. 2^30; 0 = automatic: max(256, 4 E, positions of the longest utterance / 2048)).
  *   "topc_scratch_mib" the scratch bound of sr_score_batch_set_topc, in MiB (>= 1; default 1024): the pass runs in chunks of frames that fit.
  *   "bw_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the float64 slabs sr_bw_stats_batch keeps at a time: the range

@@ -44,6 +44,7 @@ EXT_SYMBOLS = [
     "sr_bw_stats_batch", "sr_bw_plan",
     "sr_jfa_open", "sr_jfa_factors", "sr_jfa_update", "sr_jfa_train", "sr_jfa_close", "sr_jfa_plan",
     "sr_multi_slot_pieces", "sr_multi_plan",
+    "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -219,6 +220,13 @@ def lib():
         "sr_jfa_plan": (i32, [i64, i32, i32, i32, i64, i32, i32, C.POINTER(i64), i32]),
         "sr_multi_slot_pieces": (i32, [vp, i32]),
         "sr_multi_plan": (i32, [C.POINTER(i64), i32, C.POINTER(i32), i32, i32, C.POINTER(i32)] + [C.POINTER(i32)] * 4),
+        "sr_map_fit_batch": (i32, [C.POINTER(vp), i32, vp, fp, C.POINTER(i64), i32, C.POINTER(Parameter), C.c_long, C.POINTER(i32),
+                                   C.POINTER(i32)]),
+        "sr_map_fit_batch_error": (C.c_char_p, [i32]),
+        "sr_map_fit_batch_stats": (None, [C.POINTER(C.c_long)] * 5),
+        "sr_map_fit_batch_bytes": (C.c_long, []),
+        "sr_map_fit_plan": (i32, [i32, i32, C.POINTER(i64), i32, C.POINTER(Parameter), i64, i32, C.POINTER(i64), C.POINTER(i64), i64,
+                                  C.POINTER(i64), i64, C.POINTER(i64), i64, C.POINTER(i64), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -349,6 +357,46 @@ def full_fit_batch_stats():
 def full_fit_batch_bytes() -> int:
     """The current value of the option ``full_fit_batch_bytes``."""
     return int(lib().sr_full_fit_batch_bytes())
+
+
+def map_fit_batch_stats():
+    """(sr_map_fit_batch calls that reached the device, speakers fitted in a batch, by the single fit, handed over, passes launched)"""
+    v = [C.c_long(0) for _ in range(5)]
+    lib().sr_map_fit_batch_stats(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def map_fit_batch_bytes() -> int:
+    """The current value of the option ``map_fit_batch_bytes``."""
+    return int(lib().sr_map_fit_batch_bytes())
+
+
+def map_fit_plan(K: int, D: int, lengths, nr_iteration: int = 200, verbosity: int = 0, scratch_bytes: int = 1 << 30, n_cu: int = 256) -> dict:
+    """What ``sr_map_fit_batch`` decides for a UBM of K mixtures in D dimensions and speakers of ``lengths`` frames (csrc/map_plan.cpp;
+    no GPU needed when n_cu > 0): ``routes`` [S] (0 batched, 1 single, -1 failing), per speaker ``group``, ``slot``, ``n_pad``,
+    ``n_chunks`` and ``scratch`` bytes, ``groups`` [G, 6] = (first speaker, speakers, density tiles = grid x, chunks = grid x, scratch
+    bytes, first row of the density table), the tables ``tiles`` / ``chunks`` [n, 3] = (speaker, first row in the batch, local tile),
+    the mixture blocks ``n_kb`` (every grid's y) and the LDS bytes of the two large kernels."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    S = len(lengths)
+    p = Parameter()
+    p.nr_iteration, p.verbosity = int(nr_iteration), int(verbosity)
+    v = (C.c_int64 * 12)()
+    spk = np.zeros((max(S, 1), 6), dtype=np.int64)
+    args = (int(K), int(D), as_i64p(lengths), S, C.byref(p), int(scratch_bytes), int(n_cu))
+    check(lib().sr_map_fit_plan(*args, as_i64p(spk), None, 0, None, 0, None, 0, v, 12), "sr_map_fit_plan")
+    names = ("n_batched", "n_single", "n_error", "n_groups", "n_tiles", "n_chunks", "n_kb", "lds_density", "lds_stats", "max_group_bytes",
+             "waves", "state_doubles")
+    d = dict(zip(names, (int(x) for x in v)))
+    groups = np.zeros((max(d["n_groups"], 1), 6), dtype=np.int64)
+    tiles = np.zeros((max(d["n_tiles"], 1), 3), dtype=np.int64)
+    chunks = np.zeros((max(d["n_chunks"], 1), 3), dtype=np.int64)
+    check(lib().sr_map_fit_plan(*args, as_i64p(spk), as_i64p(groups), d["n_groups"], as_i64p(tiles), d["n_tiles"], as_i64p(chunks),
+                                d["n_chunks"], v, 12), "sr_map_fit_plan")
+    spk = spk[:S]
+    d.update(routes=spk[:, 0].copy(), group=spk[:, 1].copy(), slot=spk[:, 2].copy(), n_pad=spk[:, 3].copy(), n_chunks_of=spk[:, 4].copy(),
+             scratch=spk[:, 5].copy(), groups=groups[:d["n_groups"]], tiles=tiles[:d["n_tiles"]], chunks=chunks[:d["n_chunks"]])
+    return d
 
 
 def mfma_peak_probe(ms_target: float = 50.0):

@@ -15,6 +15,7 @@
 #include "topc_plan.hpp"
 #include "bw_plan.hpp"
 #include "jfa_plan.hpp"
+#include "map_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -33,6 +34,12 @@ void set_em_small_test_absent(int v);   // em_small.hip
 int last_em_stats_engine();
 void set_reference_side_effects(int v);
 void set_kmeans_assign_engine(int v);
+// map_batch.hip
+int map_fit_batch(GMM *const *models, int S, const GMM *ubm, const float *X, const int64_t *row_offsets, int dim, const Parameter &param,
+                  long seed, int *iterations_out, int *status, std::vector<std::string> &messages);
+void map_fit_batch_stats(long *calls, long *speakers_batched, long *speakers_single, long *speakers_handed_over, long *passes);
+void set_map_fit_batch_bytes(long v);
+long map_fit_batch_bytes();
 // silence.hip
 void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
 void set_silence_block(long v);
@@ -924,6 +931,91 @@ int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_d
     SR_CATCH(-1)
 }
 
+// ---- a set of speakers MAP-adapted from one UBM in one batched fit (map_batch.hip).  Every refusal comes before the device is touched. ----
+namespace {
+thread_local std::vector<std::string> g_map_batch_messages;      // of the calling thread's last sr_map_fit_batch
+}  // namespace
+
+int sr_map_fit_batch(GMM *const *models, int S, GMM *ubm, const float *X, const int64_t *row_offsets, int dim, const struct Parameter *param,
+                     long seed, int *iterations_out, int *status) {
+    SR_TRY
+    g_map_batch_messages.clear();
+    if (!models || !ubm || !X || !row_offsets || !param || !iterations_out || !status) fail("sr_map_fit_batch: null argument");
+    if (S < 1) fail("sr_map_fit_batch: at least one speaker is needed (got %d)", S);
+    if (row_offsets[0] != 0) fail("sr_map_fit_batch: row_offsets must start at 0 (got %lld)", (long long)row_offsets[0]);
+    for (int s = 0; s < S; s++)
+        if (row_offsets[s + 1] < row_offsets[s]) fail("sr_map_fit_batch: row_offsets must not decrease (speaker %d)", s);
+    if (!ubm->trained()) fail("UBM has no parameters");
+    if (ubm->dim != dim) fail("UBM dim %d != data dim %d", ubm->dim, dim);
+    {
+        std::vector<const GMM *> seen(models, models + S);
+        for (int s = 0; s < S; s++) {
+            if (!seen[(size_t)s]) fail("sr_map_fit_batch: null GMM handle (speaker %d)", s);
+            if (seen[(size_t)s] == ubm) fail("sr_map_fit_batch: speaker %d's handle is the UBM's", s);
+        }
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) fail("sr_map_fit_batch: the same handle is given twice");
+    }
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_map_fit_batch");
+    return map_fit_batch(models, S, ubm, X, row_offsets, dim, *param, seed, iterations_out, status, g_map_batch_messages);
+    SR_CATCH(-1)
+}
+
+const char *sr_map_fit_batch_error(int s) {
+    const auto &m = g_map_batch_messages;
+    return s >= 0 && (size_t)s < m.size() ? m[(size_t)s].c_str() : "";
+}
+
+void sr_map_fit_batch_stats(long *calls, long *speakers_batched, long *speakers_single, long *speakers_handed_over, long *passes) {
+    map_fit_batch_stats(calls, speakers_batched, speakers_single, speakers_handed_over, passes);
+}
+
+long sr_map_fit_batch_bytes(void) { return map_fit_batch_bytes(); }
+
+int sr_map_fit_plan(int K, int D, const int64_t *lengths, int S, const struct Parameter *param, int64_t scratch_bytes, int n_cu,
+                    int64_t *speakers_out, int64_t *groups_out, int64_t group_cap, int64_t *tiles_out, int64_t tile_cap,
+                    int64_t *chunks_out, int64_t chunk_cap, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out || !param) fail("null argument");
+    if (n_out < 12) fail("sr_map_fit_plan writes 12 fields");
+    if (n_cu <= 0) {
+        ensure_device();
+        n_cu = ctx().n_cu;
+    }
+    MapPlan p;
+    std::string why;
+    if (!plan_map_batch(K, D, lengths, S, *param, scratch_bytes, n_cu, p, why)) fail("%s", why.c_str());
+    const int64_t v[12] = {(int64_t)p.batched.size(), p.n_single, p.n_error, (int64_t)p.groups.size(), (int64_t)p.tiles.size(),
+                           (int64_t)p.chunks.size(), p.n_kb, (int64_t)p.lds_density, (int64_t)p.lds_stats, p.max_group_bytes, p.waves,
+                           MAP_STATE};
+    std::memcpy(out, v, sizeof v);
+    if (speakers_out)
+        for (int s = 0; s < S; s++) {
+            const MapSpeakerPlan &sp = p.speakers[(size_t)s];
+            const int64_t r[6] = {sp.route, sp.group, sp.slot, sp.n_pad, sp.n_chunks, sp.scratch_bytes};
+            std::memcpy(speakers_out + 6 * (size_t)s, r, sizeof r);
+        }
+    if (groups_out)
+        for (int64_t g = 0; g < std::min<int64_t>((int64_t)p.groups.size(), group_cap); g++) {
+            const MapGroupPlan &gp = p.groups[(size_t)g];
+            const int64_t r[6] = {p.batched[(size_t)gp.first], gp.count, gp.n_tiles, gp.n_chunks, gp.scratch_bytes, gp.tile0};
+            std::memcpy(groups_out + 6 * g, r, sizeof r);
+        }
+    for (int which = 0; which < 2; which++) {
+        const std::vector<MapTileRow> &rows = which ? p.chunks : p.tiles;
+        int64_t *dst = which ? chunks_out : tiles_out;
+        const int64_t cap = which ? chunk_cap : tile_cap;
+        if (!dst) continue;
+        for (int64_t i = 0; i < std::min<int64_t>((int64_t)rows.size(), cap); i++) {
+            dst[3 * i] = rows[(size_t)i].speaker;
+            dst[3 * i + 1] = rows[(size_t)i].first;
+            dst[3 * i + 2] = rows[(size_t)i].local;
+        }
+    }
+    return 12;
+    SR_CATCH(-1)
+}
+
 // ---- JFA factor estimation (jfa.hip).  Every refusal comes before the device is touched. ----
 
 SRJfa *sr_jfa_open(int64_t G, int K, int D, const double *N, const double *Fc, const double *E) {
@@ -1159,6 +1251,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);
         set_full_fit_batch_bytes(value);
+    } else if (k == "map_fit_batch_bytes") {
+        if (value < 1) fail("map_fit_batch_bytes must be >= 1 (the default is %ld)", (long)MAP_DEFAULT_SCRATCH);
+        set_map_fit_batch_bytes(value);
     } else if (k == "silence_block") {
         if (value < 0 || value > SILENCE_MAX_REL) fail("silence_block must be 0 (automatic) or 1 .. 2^30 positions per block");
         set_silence_block(value);

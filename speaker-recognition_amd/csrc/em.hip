@@ -818,6 +818,7 @@ static int &em_stats_engine_option() {
     return v;
 }
 void set_em_stats_engine(int v) { em_stats_engine_option() = v; }
+int em_stats_engine() { return em_stats_engine_option(); }
 static std::atomic<int> g_last_stats_engine{0};
 int last_em_stats_engine() { return g_last_stats_engine.load(); }
 // The reference's trainers leave traces a drop-in user may be relying on: the parameter block on stdout at every train_model*

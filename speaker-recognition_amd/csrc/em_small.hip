@@ -28,6 +28,7 @@
 // term lies within 110 nats of the underflow boundary -- where the reference's flushes of PARTIAL products decide (lse.hpp,
 // gmm_flush.hip) -- and anything that is not finite.
 #include "score.hpp"
+#include "map_plan.hpp"
 #include "wave_ops.hpp"
 
 #include "../../include/pygmm_hip.h"
@@ -48,11 +49,8 @@ namespace sr {
 
 namespace {
 
-constexpr int EMF_THREADS = 1024;                 // a workgroup: 64 or 128 frames x 16 or 8 mixture groups
-constexpr int EMF_MAX_K = 32, EMF_MAX_D = 40;
-// the iteration's price grows with the workgroups that meet at its barriers (12 us at one, 27 at 47, 46 at 128, 16 x 13); from ~10 k
-// frames on an iteration per launch costs the same (20 000 x 32 x 40: 30 ms either way)
-constexpr long EMF_MAX_FRAMES = 8192;
+// (EMF_THREADS, EMF_MAX_K / _D / _FRAMES and em_small_shape: map_plan.hpp -- the batched enrolment's plan evaluates this path's
+// eligibility without a device)
 constexpr unsigned EMF_POLL_LIMIT = 60000;        // polls of ~1.5 us (a sleep and a device-scope load), ~0.1 s, before a workgroup gives the grid up
 constexpr double EMF_MINLOG = -708.396418532264;  // ln DBL_MIN (fastexp.cc:93,105)
 constexpr double EMF_BAND = -598.0;               // a live frame below this goes to the path that restates the partial-product flushes
@@ -441,34 +439,10 @@ struct EmSmallWorkspace {
 
 }  // namespace
 
-// frames per workgroup, segments of a role's sweep, LDS bytes.  The fewer workgroups meet at the barrier the cheaper the iteration
-// (~0.3 us each) and the longer a workgroup's own arithmetic: 16 x 13 on 2998 frames 26.8 us per iteration at 64 frames per workgroup,
-// 19.5 at 128, 21.5 at 256 -- 128 where the LDS fits and 64 frames would not do with as few workgroups.
-struct EmSmallShape {
-    int fr, seg, grid;
-    size_t lds;
-};
-static EmSmallShape em_small_shape(int K, int D, long n) {
-    EmSmallShape best{0, 1, 0, 0};
-    const int R = K * (D + 1);
-    for (int fr : {128, 64}) {
-        if (fr > 64 && (n + fr / 2 - 1) / (fr / 2) == (n + fr - 1) / fr) continue;      // (half the frames: as many workgroups)
-        int seg = 1;
-        while (seg * 2 <= fr / 64 && R * seg * 2 <= EMF_THREADS) seg *= 2;
-        const size_t lds = (size_t)(3 * K + 3 * K * D + K * fr + EMF_THREADS + fr + K * (2 * D + 1) + 2 + 2 * R * seg) * sizeof(double) +
-                           (size_t)fr * (D + 1) * sizeof(float);
-        if (lds > 150 * 1024) continue;
-        best = {fr, seg, (int)((n + fr - 1) / fr), lds};
-        break;
-    }
-    return best;
-}
-
 void set_em_small_test_absent(int v) { em_small_test_absent().store(v); }
 
 bool em_small_eligible(int K, int dim, long n, const Parameter &param) {
-    return K >= 1 && K <= EMF_MAX_K && dim >= 1 && dim <= EMF_MAX_D && n >= 1 &&
-           n <= EMF_MAX_FRAMES && em_small_shape(K, dim, n).grid >= 1 && em_small_shape(K, dim, n).grid <= ctx().n_cu / 2 && param.nr_iteration >= 1 && param.verbosity < 2;
+    return em_small_shape_eligible(K, dim, n, param, ctx().n_cu);
 }
 
 // The fit of `gmm` (its parameters are the start) on the n resident frames dX.  true: done -- gmm holds the result, *iterations the

@@ -54,10 +54,58 @@ class GMMSet(object):
     def auto_tune_parameter(self, X, y):
         return None                  # unimplemented in the reference as well (gmmset.py:44-47)
 
+    def fit_many(self, xs, labels):
+        """Train one model per matrix ``xs[s]`` and append them under ``labels[s]``, in order: with a UBM every speaker in ONE
+        batched device fit (``sr_map_fit_batch``, csrc/map_batch.hip) -- the models and iteration counts of a loop of ``fit_new``,
+        bit for bit; without one, or in a process that lost its GPU runtime to fork(), that loop.  As in the loop, the speakers
+        before the first failing one are appended and its error is raised."""
+        xs, labels = list(xs), list(labels)
+        if len(xs) != len(labels):
+            raise ValueError("fit_many: %d matrices but %d labels" % (len(xs), len(labels)))
+        if not xs:
+            return
+        if self.ubm is None or _lib.gpu_runtime_lost():
+            for x, label in zip(xs, labels):
+                self.fit_new(x, label)
+            return
+        dim = self.ubm.get_dim()
+        mats, refused = [], None
+        for x in xs:                          # (what the loop would refuse at speaker s is raised after the speakers before it)
+            try:
+                X = _lib.f32_matrix(x)
+                if X.shape[0] > 0 and X.shape[1] != dim:
+                    raise _lib.SRError("train failed: UBM dim %d != data dim %d" % (dim, X.shape[1]))
+            except (ValueError, _lib.SRError) as e:
+                refused = e
+                break
+            mats.append(X)
+        if not mats:
+            raise refused
+        S = len(mats)
+        models = [GMM(self.gmm_order, **self.kwargs) for _ in range(S)]
+        off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum([X.shape[0] for X in mats], out=off[1:])
+        have = [X for X in mats if X.shape[0] > 0]
+        Xall = np.ascontiguousarray(np.concatenate(have, axis=0)) if have else np.zeros((1, dim), np.float32)
+        p = models[0]._gen_param(Xall)
+        handles = (C.c_void_p * S)(*[m.gmm.value for m in models])
+        iters = np.zeros(S, dtype=np.int32)
+        status = np.zeros(S, dtype=np.int32)
+        rc = _lib.lib().sr_map_fit_batch(handles, S, self.ubm.gmm, _lib.as_fp(Xall), _lib.as_i64p(off), dim, C.byref(p), int(models[0].seed),
+                                         _lib.as_i32p(iters), _lib.as_i32p(status))
+        _lib.check(rc, "sr_map_fit_batch")
+        for s, (model, label) in enumerate(zip(models, labels)):
+            if status[s] < 0:
+                raise _lib.SRError("train failed: %s" % _lib.lib().sr_map_fit_batch_error(s).decode("utf-8", "replace"))
+            model.nr_mixture = _lib.lib().get_nr_mixtures(model.gmm)
+            model._version = getattr(model, "_version", 0) + 1      # as GMM.fit: invalidates packed copies (_model_set)
+            self._append(label, model)
+        if refused is not None:
+            raise refused
+
     def fit(self, X, y):
         frames, labels = self.cluster_by_label(X, y)
-        for f, lab in zip(frames, labels):
-            self.fit_new(f, lab)
+        self.fit_many(frames, labels)
         self.auto_tune_parameter(frames, labels)
 
     def load_gmm(self, label, fname):

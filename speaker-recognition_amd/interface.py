@@ -148,12 +148,9 @@ class ModelInterface(object):
         start = time.time()
         if self.verbose:
             print("Start training...")
-        if getattr(self, "covariance_type", "diag") == "full":
-            # every speaker in one batched device EM: the models of a loop of fit_new, bit for bit
-            self.gmmset.fit_many([np.asarray(feats) for feats in self.features.values()], list(self.features.keys()))
-        else:
-            for name, feats in self.features.items():
-                self.gmmset.fit_new(np.asarray(feats), name)
+        # every speaker in one batched device fit -- full covariance: sr_fullgmm_fit_batch; diagonal with a UBM: sr_map_fit_batch
+        # (without one GMMSet.fit_many is the loop of fit_new) -- the models of a loop of fit_new, bit for bit
+        self.gmmset.fit_many([np.asarray(feats) for feats in self.features.values()], list(self.features.keys()))
         if self.verbose:
             print(time.time() - start, " seconds")
 
