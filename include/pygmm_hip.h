@@ -656,6 +656,50 @@ int sr_jfa_train(SRJfa *h, double *W /*in/out*/, int R, int n_iter, double *y /*
 void sr_jfa_close(SRJfa *h);
 int sr_jfa_plan(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out, int n_out);
 
+/* ---- JFA trial scoring (csrc/jfa_score.hip): the score matrix out [J][T] of J models (speaker factors y [J][Ry], z [J][K*D]) against
+ * T test segments (raw statistics N [T][K], F [T][K*D], F NOT centred), by the reference's two scorers (src/jfa/; MATLAB there, a
+ * loop over segments and models), float64 throughout, in one batched call.  d [K*D] and z may be NULL: zeros.
+ * sr_jfa_score_integrated (kscore_famous_19.m: the channel factors integrated out).  M_0 = m, M_j = m + z_j .* d + y_j v:
+ *   lin[t][j]  = sum_i F[t][i] M_j[i] / E[i]        quad[t][j] = sum_c N[t][c] sum_d M_j[c,d]^2 / E[c,d]
+ *   L_t = I + sum_c N[t][c] u_c diag(1 / E_c) u_c^T a_t = u (F[t] ./ E)        h[t][j] = sum_c N[t][c] u_c (M_j,c ./ E_c)
+ *   quad2 = || chol(L_t)^-1 (a_t - h[t][j]) ||^2    s = (lin - quad / 2 + quad2 / 2) / n_t,  n_t = sum_c N[t][c]
+ *   out[j-1][t] = s[t][j] - s[t][0]
+ *   u_c (M_j,c ./ E_c) is formed once per call for every (mixture, model), so h of all pairs is one product over K: K Ru operations a
+ *   pair where the reference spends K D Ru.  One workgroup per segment factors L_t and runs ONE forward substitution over all J + 1
+ *   right-hand sides.  The reference leaves the UBM's score un-subtracted where a score is exactly 0; that is not reproduced.
+ * sr_jfa_score_linear (linear_scoring.m), with the segments' channel factors x [T][Ru]:
+ *   out[j][t] = sum_i ((z_j .* d + y_j v)[i] / E[i]) (F[t][i] - N[t][c(i)] (m + x_t u)[i]) / n_t
+ * The test segments run in chunks whose blocks (Ru^2 + (J + 1) Ru doubles a segment) fit "jfa_scratch_mib"; "jfa_lds_rows" chooses the
+ * factorisation path as for sr_jfa_factors.  No atomics: a (model, segment) score is the same bits for the segment alone or in any
+ * batch, for the model alone or in any model set, under any bound, on either path's chunking, from run to run.
+ * mask (or NULL): uint8 [mask_rows][mask_cols], which must be [J][T]; where it is 0 the score is 0.0 exactly.  A segment with
+ * n_t = 0 gets zeros and is counted in empty_segments (the reference divides by zero there); a segment whose L_t does not factor (a
+ * pivot <= 0 or not finite: impossible short of overflow) gets zeros and is counted in bad_segments.  The counters may be NULL.
+ * Refused, before the device is touched, with a message that names the remedy: T, J, K, D, Ry or Ru < 1, Ry or Ru above 512, a
+ * non-finite value in any input, a negative N, E <= 0, linear mode without x, a mask of another shape, a scratch bound below one
+ * segment's blocks.  Refused in a process forked after the GPU runtime was initialised.
+ * Timer kinds (none is added): SR_T_JFA_GRAM the scalings, P, the cross kernel and the elementwise synthesis / compensation;
+ * SR_T_JFA_GEMM_L L; SR_T_JFA_GEMM_B the reductions over K * D (a, lin, the linear score matrix); SR_T_JFA_GEMM_A the reductions over
+ * K (quad, h); SR_T_JFA_GEMM_C the synthesis products y v and x u; SR_T_JFA_FACTOR the factorisation, substitution and scores.
+ * sr_jfa_score_plan: what such a call decides (csrc/jfa_plan.cpp; host only when n_cu > 0), for tests; mode 0 integrated, 1 linear.
+ * Writes 56 fields (n_out >= 56) and returns 56, -1 on refusal: mode, segments per chunk, chunks, a segment's bytes inside the bound,
+ * a chunk's; bytes of M, M ./ E, u (with u ./ E), P, q, G, N, F, lin, quad, a, out and linear mode's compensated statistics; the
+ * factorisation path and the largest Ru of the LDS path; the grids of the y v product, the synthesis, the two scalings, the gram and
+ * cross (x, y, z) kernels, the L, a, lin, quad and h products, the scoring kernel, linear mode's x u product, compensation and score
+ * product; LDS bytes of the gram, GEMM, cross and scoring kernels; rounds of a chunk's scoring launch over the chip; the built limits
+ * of Ry / Ru, of the LDS path and of J; 0, 0. */
+int sr_jfa_score_integrated(int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N /*[T][K]*/, const double *F /*[T][K*D]*/,
+                            const double *m /*[K*D]*/, const double *E /*[K*D]*/, const double *d /*[K*D] or NULL*/, const double *v /*[Ry][K*D]*/,
+                            const double *u /*[Ru][K*D]*/, const double *z /*[J][K*D] or NULL*/, const double *y /*[J][Ry]*/,
+                            const unsigned char *mask /*or NULL*/, int64_t mask_rows, int64_t mask_cols, double *out /*[J][T]*/,
+                            int64_t *empty_segments /*or NULL*/, int64_t *bad_segments /*or NULL*/);
+int sr_jfa_score_linear(int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
+                        const double *d /*or NULL*/, const double *v, const double *u, const double *z /*or NULL*/, const double *y,
+                        const double *x /*[T][Ru]*/, const unsigned char *mask /*or NULL*/, int64_t mask_rows, int64_t mask_cols,
+                        double *out /*[J][T]*/, int64_t *empty_segments /*or NULL*/);
+int sr_jfa_score_plan(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out,
+                      int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXT_SYMBOLS = [
     "sr_score_batch_set_topc", "sr_predict_pcm_batch_topc", "sr_topc_plan",
     "sr_bw_stats_batch", "sr_bw_plan",
     "sr_jfa_open", "sr_jfa_factors", "sr_jfa_update", "sr_jfa_train", "sr_jfa_close", "sr_jfa_plan",
+    "sr_jfa_score_integrated", "sr_jfa_score_linear", "sr_jfa_score_plan",
     "sr_multi_slot_pieces", "sr_multi_plan",
     "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
 ]
@@ -218,6 +219,11 @@ def lib():
         "sr_jfa_train": (i32, [vp, dp, i32, i32, dp, C.POINTER(i64)]),
         "sr_jfa_close": (None, [vp]),
         "sr_jfa_plan": (i32, [i64, i32, i32, i32, i64, i32, i32, C.POINTER(i64), i32]),
+        "sr_jfa_score_integrated": (i32, [i64, i64, i32, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint8), i64, i64, dp,
+                                          C.POINTER(i64), C.POINTER(i64)]),
+        "sr_jfa_score_linear": (i32, [i64, i64, i32, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint8), i64, i64, dp,
+                                      C.POINTER(i64)]),
+        "sr_jfa_score_plan": (i32, [i64, i64, i32, i32, i32, i32, i32, i64, i32, i32, C.POINTER(i64), i32]),
         "sr_multi_slot_pieces": (i32, [vp, i32]),
         "sr_multi_plan": (i32, [C.POINTER(i64), i32, C.POINTER(i32), i32, i32, C.POINTER(i32)] + [C.POINTER(i32)] * 4),
         "sr_map_fit_batch": (i32, [C.POINTER(vp), i32, vp, fp, C.POINTER(i64), i32, C.POINTER(Parameter), C.c_long, C.POINTER(i32),
@@ -488,6 +494,29 @@ def jfa_plan(G: int, K: int, D: int, R: int, scratch_bytes: int = 1 << 30, lds_r
     check(lib().sr_jfa_plan(int(G), int(K), int(D), int(R), int(scratch_bytes), int(lds_rows), int(n_cu), v, 32), "sr_jfa_plan")
     d = dict(zip(JFA_PLAN_FIELDS, (int(x) for x in v)))
     d["path"] = ("lds", "global")[d["path"]]
+    return d
+
+
+JFA_SCORE_PLAN_FIELDS = ("mode", "chunk", "n_chunks", "seg_bytes", "bytes_scratch", "bytes_M", "bytes_ME", "bytes_uE", "bytes_P", "bytes_q",
+                         "bytes_G", "bytes_N", "bytes_F", "bytes_lin", "bytes_quad", "bytes_a", "bytes_out", "bytes_comp", "path", "lds_rows",
+                         "gemm_yv_x", "gemm_yv_y", "synth_grid", "scale_M_grid", "scale_u_grid", "gram_grid_x", "gram_grid_y", "cross_grid_x",
+                         "cross_grid_y", "cross_grid_z", "gemm_L_x", "gemm_L_y", "gemm_a_x", "gemm_a_y", "gemm_lin_x", "gemm_lin_y", "gemm_quad_x",
+                         "gemm_quad_y", "gemm_h_x", "gemm_h_y", "kscore_grid", "gemm_xu_x", "gemm_xu_y", "comp_grid", "gemm_out_x", "gemm_out_y",
+                         "gram_lds", "gemm_lds", "cross_lds", "kscore_lds", "kscore_rounds", "max_R", "max_lds_rows", "max_J")
+
+
+def jfa_score_plan(T: int, J: int, K: int, D: int, Ry: int, Ru: int, mode: str = "integrated", scratch_bytes: int = 1 << 30, lds_rows: int = 0,
+                   n_cu: int = 256) -> dict:
+    """What ``sr_jfa_score_integrated`` / ``sr_jfa_score_linear`` decide for T test segments, J models, a K x D model, Ry eigenvoices
+    and Ru eigenchannels under a scratch bound and the option ``jfa_lds_rows`` (csrc/jfa_plan.cpp; no GPU needed when n_cu > 0): the
+    refusals, segments per chunk, chunks, a segment's bytes inside the bound, the bytes of every array outside it, the factorisation
+    ``path`` ("lds" or "global"), the grid of every launch and every kernel's LDS bytes."""
+    v = (C.c_int64 * 56)()
+    check(lib().sr_jfa_score_plan(int(T), int(J), int(K), int(D), int(Ry), int(Ru), {"integrated": 0, "linear": 1}.get(mode, -1),
+                                  int(scratch_bytes), int(lds_rows), int(n_cu), v, 56), "sr_jfa_score_plan")
+    d = dict(zip(JFA_SCORE_PLAN_FIELDS, (int(x) for x in v)))
+    d["path"] = ("lds", "global")[d["path"]]
+    d["mode"] = ("integrated", "linear")[d["mode"]]
     return d
 
 

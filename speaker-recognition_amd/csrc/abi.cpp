@@ -1075,6 +1075,51 @@ int sr_jfa_plan(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_r
     SR_CATCH(-1)
 }
 
+// ---- JFA trial scoring (jfa_score.hip) ----
+
+int sr_jfa_score_integrated(int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
+                            const double *d, const double *v, const double *u, const double *z, const double *y, const unsigned char *mask,
+                            int64_t mask_rows, int64_t mask_cols, double *out, int64_t *empty_segments, int64_t *bad_segments) {
+    SR_TRY
+    jfa_score(JFA_SCORE_INTEGRATED, T, J, K, D, Ry, Ru, N, F, m, E, d, v, u, z, y, nullptr, mask, mask_rows, mask_cols, out, empty_segments, bad_segments);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_score_linear(int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
+                        const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
+                        const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, double *out, int64_t *empty_segments) {
+    SR_TRY
+    jfa_score(JFA_SCORE_LINEAR, T, J, K, D, Ry, Ru, N, F, m, E, d, v, u, z, y, x, mask, mask_rows, mask_cols, out, empty_segments, nullptr);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_score_plan(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out,
+                      int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 56) fail("sr_jfa_score_plan writes 56 fields");
+    std::string why;
+    JfaScorePlan p;
+    if (n_cu > 0) {
+        if (!plan_jfa_score(T, J, K, D, Ry, Ru, mode, scratch_bytes, lds_rows, n_cu, p, why)) fail("%s", why.c_str());
+    } else {
+        if (!plan_jfa_score(T, J, K, D, Ry, Ru, mode, scratch_bytes, lds_rows, 1, p, why)) fail("%s", why.c_str());      // the refusals first
+        ensure_device();
+        if (!plan_jfa_score(T, J, K, D, Ry, Ru, mode, scratch_bytes, lds_rows, ctx().n_cu, p, why)) fail("%s", why.c_str());
+    }
+    const int64_t v[56] = {p.mode, p.chunk, p.n_chunks, p.seg_bytes, p.bytes_scratch, p.bytes_M, p.bytes_ME, p.bytes_uE, p.bytes_P, p.bytes_q,
+                           p.bytes_G, p.bytes_N, p.bytes_F, p.bytes_lin, p.bytes_quad, p.bytes_a, p.bytes_out, p.bytes_comp, p.path, p.lds_rows,
+                           p.gemm_yv.x, p.gemm_yv.y, p.synth.x, p.scale_M.x, p.scale_u.x, p.gram.x, p.gram.y, p.cross.x, p.cross.y, p.cross_z,
+                           p.gemm_L.x, p.gemm_L.y, p.gemm_a.x, p.gemm_a.y, p.gemm_lin.x, p.gemm_lin.y, p.gemm_quad.x, p.gemm_quad.y, p.gemm_h.x,
+                           p.gemm_h.y, p.kscore.x, p.gemm_xu.x, p.gemm_xu.y, p.comp.x, p.gemm_out.x, p.gemm_out.y, p.gram_lds, p.gemm_lds,
+                           p.cross_lds, p.kscore_lds, p.kscore_rounds, JFA_MAX_R, JFA_LDS_MAX_R, JFA_SCORE_MAX_J, 0, 0};
+    std::memcpy(out, v, sizeof v);
+    return 56;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY

@@ -5,7 +5,8 @@
 //   P_c = W_c diag(1 / E_c) W_c^T            L_g = I + sum_c N[g][c] P_c           b_g = W (Fc_g ./ E)
 //   y_g = L_g^-1 b_g                         Q_g = L_g^-1 + y_g y_g^T
 //   A_c = sum_g N[g][c] Q_g                  C   = sum_g y_g Fc_g^T                W_c <- A_c^-1 C_c
-// Everything is float64.  Four kernels, none shared with any other path (and none touching the pass counters):
+// Everything is float64.  Four kernels, none touching the pass counters (trial scoring, jfa_score.hip, launches the first three
+// through the launchers declared in jfa_dev.hpp, which also holds the Cholesky of the fourth):
 //   jfa_scale_kernel    W ./ E, once per call (the B operand of the b product).
 //   jfa_gram_kernel     P [K][R][R]: a 16 x 16 tile of one mixture per workgroup, the two row panels of W_c through LDS; the product
 //                       W[i][d] W[j][d] is formed first, so P is symmetric to the bit.
@@ -24,8 +25,7 @@
 // C) and it is counted; a mixture of the update: W_c keeps its old value and it is counted.  Nothing non-finite is spread.
 // Deterministic: no atomics; a group's y depends on its own N, Fc and on W only; A and C are summed in group order whatever the
 // chunking -- the results do not depend on the scratch bound, bit for bit.
-#include "jfa_plan.hpp"
-#include "score.hpp"
+#include "jfa_dev.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -45,7 +45,6 @@ namespace sr {
 
 typedef double jfa_f64x4 __attribute__((ext_vector_type(4)));
 constexpr int JFA_TS = JFA_TILE + 4;                   // row stride of the GEMM operand tiles in LDS
-constexpr int JFA_PS = JFA_NB + 1;                     // row stride of the Cholesky panel in LDS
 
 __global__ __launch_bounds__(JFA_WG)
 void jfa_scale_kernel(const double *__restrict__ W, const double *__restrict__ iE, double *__restrict__ WE, int64_t n, int64_t kd) {
@@ -143,53 +142,6 @@ void jfa_gemm_kernel(const double *__restrict__ A, int64_t sam, int64_t sak, con
                 C[row * ldc + col] = v;
             }
         }
-}
-
-// ---- the factorisation of one R x R block by one workgroup.  M: the block, row stride R, in LDS or in global memory. ----
-
-// Lower Cholesky factor over the lower triangle of M (the upper triangle is not read).  false: a pivot <= 0 or not finite (every
-// lane returns the same: the pivot is read from LDS behind a barrier).
-__device__ bool jfa_cholesky(double *M, int R, double *pan /* [R][JFA_PS] */) {
-    const int tid = threadIdx.x;
-    for (int j0 = 0; j0 < R; j0 += JFA_NB) {
-        const int nb = min(JFA_NB, R - j0), rows = R - j0;
-        for (int e = tid; e < rows * nb; e += JFA_WG) {
-            const int r = e / nb, c = e % nb;
-            pan[r * JFA_PS + c] = M[(int64_t)(j0 + r) * R + j0 + c];
-        }
-        __syncthreads();
-        for (int c = 0; c < nb; c++) {
-            const double p = pan[c * JFA_PS + c];
-            if (!(p > 0.0) || !__builtin_isfinite(p)) return false;
-            const double d = sqrt(p);
-            __syncthreads();                   // every lane has read the pivot
-            for (int r = c + tid; r < rows; r += JFA_WG) pan[r * JFA_PS + c] = r == c ? d : pan[r * JFA_PS + c] / d;
-            __syncthreads();
-            const int w = nb - c - 1;
-            for (int e = tid; e < (rows - c - 1) * w; e += JFA_WG) {
-                const int r = c + 1 + e / w, c2 = c + 1 + e % w;
-                if (r >= c2) pan[r * JFA_PS + c2] = __builtin_fma(-pan[r * JFA_PS + c], pan[c2 * JFA_PS + c], pan[r * JFA_PS + c2]);
-            }
-            __syncthreads();
-        }
-        for (int e = tid; e < rows * nb; e += JFA_WG) {
-            const int r = e / nb, c = e % nb;
-            if (r >= c) M[(int64_t)(j0 + r) * R + j0 + c] = pan[r * JFA_PS + c];
-        }
-        const int t = rows - nb;               // the trailing block, lower triangle: M[i][k] -= sum_c pan[i][c] pan[k][c]
-        for (int e = tid; e < t * t; e += JFA_WG) {
-            const int i = e / t, k = e % t;
-            if (k <= i) {
-                double *dst = M + (int64_t)(j0 + nb + i) * R + j0 + nb + k;
-                const double *pi = pan + (nb + i) * JFA_PS, *pk = pan + (nb + k) * JFA_PS;
-                double s = *dst;
-                for (int c = 0; c < nb; c++) s = __builtin_fma(-pi[c], pk[c], s);
-                *dst = s;
-            }
-        }
-        __syncthreads();                       // the panel is consumed, the trailing block written
-    }
-    return true;
 }
 
 // T [R][nrhs] (row stride ldt; LDS or global memory) <- (F F^T)^-1 T with the factor F in M's lower triangle: two triangular solves.
@@ -333,12 +285,23 @@ struct JfaUpdateScratch {
 };
 }  // namespace
 
-static void launch_gemm(TimerKind kind, hipStream_t st, const double *A, int64_t sam, int64_t sak, const double *B, int64_t sbk, int64_t sbn, double *C,
-                        int64_t ldc, int64_t M, int64_t N, int64_t Kred, bool accumulate, int diag_step) {
+void launch_gemm(TimerKind kind, hipStream_t st, const double *A, int64_t sam, int64_t sak, const double *B, int64_t sbk, int64_t sbn, double *C,
+                 int64_t ldc, int64_t M, int64_t N, int64_t Kred, bool accumulate, int diag_step) {
     ScopedKernelTimer t(kind);
     const dim3 grid((unsigned)((N + JFA_TILE - 1) / JFA_TILE), (unsigned)((M + JFA_TILE - 1) / JFA_TILE));
     hipLaunchKernelGGL(jfa_gemm_kernel, grid, dim3(JFA_WG), 0, st, A, sam, sak, B, sbk, sbn, C, ldc, (int)M, N, Kred, accumulate ? 1 : 0,
                        diag_step);
+    SR_HIP(hipGetLastError());
+}
+
+void launch_scale(hipStream_t st, const double *W, const double *iE, double *WE, int64_t n, int64_t kd) {
+    hipLaunchKernelGGL(jfa_scale_kernel, dim3((unsigned)((n + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, W, iE, WE, n, kd);
+    SR_HIP(hipGetLastError());
+}
+
+void launch_gram(hipStream_t st, const double *W, const double *iE, double *P, int R, int K, int D) {
+    const int64_t gt = (R + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE;
+    hipLaunchKernelGGL(jfa_gram_kernel, dim3((unsigned)K, (unsigned)(gt * gt)), dim3(JFA_WG), 0, st, W, iE, P, R, K, D);
     SR_HIP(hipGetLastError());
 }
 
@@ -380,11 +343,8 @@ static void jfa_run_factors(SRJfa &h, int R, bool accumulate, const JfaPlan &pl)
     }
     {
         ScopedKernelTimer t(T_JFA_GRAM);
-        hipLaunchKernelGGL(jfa_scale_kernel, dim3((unsigned)((R * kd + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, h.W.p, h.iE.p, h.WE.p,
-                           R * kd, kd);
-        SR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(jfa_gram_kernel, dim3((unsigned)pl.gram.x, (unsigned)pl.gram.y), dim3(JFA_WG), 0, st, h.W.p, h.iE.p, h.P.p, R, K, D);
-        SR_HIP(hipGetLastError());
+        launch_scale(st, h.W.p, h.iE.p, h.WE.p, R * kd, kd);
+        launch_gram(st, h.W.p, h.iE.p, h.P.p, R, K, D);
     }
     for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
         const int64_t g0 = ci * pl.chunk, n = std::min(pl.chunk, G - g0);

@@ -1,0 +1,69 @@
+// jfa_dev.hpp -- what jfa.hip (factor estimation) and jfa_score.hip (trial scoring) share: the panel Cholesky of one R x R block by
+// one workgroup, and the host launchers of jfa.hip's kernels that the scoring path reuses (defined in jfa.hip).
+#pragma once
+
+#include "jfa_plan.hpp"
+#include "score.hpp"
+
+namespace sr {
+
+constexpr int JFA_PS = JFA_NB + 1;                     // row stride of the Cholesky panel in LDS
+
+// C [M][N] (+)= A B through jfa_gemm_kernel, booked to `kind`; the operands are addressed by (row stride, column stride).
+void launch_gemm(TimerKind kind, hipStream_t st, const double *A, int64_t sam, int64_t sak, const double *B, int64_t sbk, int64_t sbn, double *C,
+                 int64_t ldc, int64_t M, int64_t N, int64_t Kred, bool accumulate, int diag_step);
+// WE = W .* iE over n elements of rows of kd columns (jfa_scale_kernel); P [K][R][R] from W [R][K D] (jfa_gram_kernel).  No timer of their own.
+void launch_scale(hipStream_t st, const double *W, const double *iE, double *WE, int64_t n, int64_t kd);
+void launch_gram(hipStream_t st, const double *W, const double *iE, double *P, int R, int K, int D);
+
+#ifdef __HIPCC__
+// ---- the factorisation of one R x R block by one workgroup.  M: the block, row stride R, in LDS or in global memory. ----
+
+// Lower Cholesky factor over the lower triangle of M (the upper triangle is not read).  false: a pivot <= 0 or not finite (every
+// lane returns the same: the pivot is read from LDS behind a barrier).
+static __device__ bool jfa_cholesky(double *M, int R, double *pan /* [R][JFA_PS] */) {
+    const int tid = threadIdx.x;
+    for (int j0 = 0; j0 < R; j0 += JFA_NB) {
+        const int nb = min(JFA_NB, R - j0), rows = R - j0;
+        for (int e = tid; e < rows * nb; e += JFA_WG) {
+            const int r = e / nb, c = e % nb;
+            pan[r * JFA_PS + c] = M[(int64_t)(j0 + r) * R + j0 + c];
+        }
+        __syncthreads();
+        for (int c = 0; c < nb; c++) {
+            const double p = pan[c * JFA_PS + c];
+            if (!(p > 0.0) || !__builtin_isfinite(p)) return false;
+            const double d = sqrt(p);
+            __syncthreads();                   // every lane has read the pivot
+            for (int r = c + tid; r < rows; r += JFA_WG) pan[r * JFA_PS + c] = r == c ? d : pan[r * JFA_PS + c] / d;
+            __syncthreads();
+            const int w = nb - c - 1;
+            for (int e = tid; e < (rows - c - 1) * w; e += JFA_WG) {
+                const int r = c + 1 + e / w, c2 = c + 1 + e % w;
+                if (r >= c2) pan[r * JFA_PS + c2] = __builtin_fma(-pan[r * JFA_PS + c], pan[c2 * JFA_PS + c], pan[r * JFA_PS + c2]);
+            }
+            __syncthreads();
+        }
+        for (int e = tid; e < rows * nb; e += JFA_WG) {
+            const int r = e / nb, c = e % nb;
+            if (r >= c) M[(int64_t)(j0 + r) * R + j0 + c] = pan[r * JFA_PS + c];
+        }
+        const int t = rows - nb;               // the trailing block, lower triangle: M[i][k] -= sum_c pan[i][c] pan[k][c]
+        for (int e = tid; e < t * t; e += JFA_WG) {
+            const int i = e / t, k = e % t;
+            if (k <= i) {
+                double *dst = M + (int64_t)(j0 + nb + i) * R + j0 + nb + k;
+                const double *pi = pan + (nb + i) * JFA_PS, *pk = pan + (nb + k) * JFA_PS;
+                double s = *dst;
+                for (int c = 0; c < nb; c++) s = __builtin_fma(-pi[c], pk[c], s);
+                *dst = s;
+            }
+        }
+        __syncthreads();                       // the panel is consumed, the trailing block written
+    }
+    return true;
+}
+
+#endif
+
+}  // namespace sr

@@ -128,4 +128,140 @@ bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_row
     return true;
 }
 
+// ---- trial scoring ----
+
+bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, std::string &why) {
+    if (mode != JFA_SCORE_INTEGRATED && mode != JFA_SCORE_LINEAR) {
+        why = "JFA scoring: the mode is 0 (integrated) or 1 (linear)";
+        return false;
+    }
+    if (T < 1 || J < 1 || K < 1 || D < 1 || Ry < 1 || Ru < 1) {
+        why = fmt("JFA scoring: need at least one test segment, one model, one mixture, one dimension, one eigenvoice and one eigenchannel "
+                  "(T, J, K, D, Ry, Ru >= 1); T x J = %lld x %lld", T, J);
+        return false;
+    }
+    if (Ry > JFA_MAX_R || Ru > JFA_MAX_R) {
+        why = fmt("JFA scoring is built for up to %lld factors, v or u has %lld rows; score with fewer factors", JFA_MAX_R, std::max(Ry, Ru));
+        return false;
+    }
+    const int64_t kd = (int64_t)K * D, cap = (int64_t)1 << 36;
+    if (T > (int64_t)65535 * JFA_TILE || J > JFA_SCORE_MAX_J || kd > ((int64_t)1 << 31) - 1 || T > cap / kd || J + 1 > cap / kd) {
+        why = fmt("JFA scoring: more than %lld test segments or %lld models, or statistics or models of more than 2^36 values; split the trial list",
+                  (int64_t)65535 * JFA_TILE, JFA_SCORE_MAX_J);
+        return false;
+    }
+    return true;
+}
+
+bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F, const double *m,
+                            const double *E, const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
+                            const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why) {
+    if (!jfa_score_check_shape(T, J, K, D, Ry, Ru, mode, why)) return false;
+    if (!N || !F || !m || !E || !v || !u || !y) {
+        why = "JFA scoring: null argument (N, F, m, E, v, u and y are all required; d, z, x and the mask may be absent)";
+        return false;
+    }
+    if (mode == JFA_SCORE_LINEAR && !x) {
+        why = "JFA scoring: linear mode needs the test segments' channel factors x [T][Ru]; estimate them (estimate_x_and_u) or score in integrated mode";
+        return false;
+    }
+    if (mask && (mask_rows != J || mask_cols != T)) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "JFA scoring: the mask is [%lld][%lld], the score matrix [%lld][%lld]; pass one uint8 per (model, segment) pair",
+                 (long long)mask_rows, (long long)mask_cols, (long long)J, (long long)T);
+        why = buf;
+        return false;
+    }
+    const int64_t kd = (int64_t)K * D;
+    if (!jfa_check_finite(N, T * K, "N", why) || !jfa_check_finite(F, T * kd, "F", why) || !jfa_check_finite(m, kd, "m", why) ||
+        !jfa_check_finite(E, kd, "E", why) || (d && !jfa_check_finite(d, kd, "d", why)) || !jfa_check_finite(v, Ry * kd, "v", why) ||
+        !jfa_check_finite(u, Ru * kd, "u", why) || (z && !jfa_check_finite(z, J * kd, "z", why)) || !jfa_check_finite(y, J * Ry, "y", why) ||
+        (x && !jfa_check_finite(x, T * Ru, "x", why)))
+        return false;
+    for (int64_t i = 0; i < T * K; i++)
+        if (N[i] < 0.0) {
+            why = fmt("JFA scoring: N holds a negative occupancy at segment %lld, mixture %lld; occupancies are sums of posteriors", i / K, i % K);
+            return false;
+        }
+    for (int64_t i = 0; i < kd; i++)
+        if (!(E[i] > 0.0)) {
+            why = fmt("JFA scoring: E must be positive, element %lld is not; pass the UBM's variances", i);
+            return false;
+        }
+    return true;
+}
+
+static JfaGrid flat_grid(int64_t n) { return JfaGrid{(n + JFA_WG - 1) / JFA_WG, 1}; }
+
+bool plan_jfa_score(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, JfaScorePlan &p,
+                    std::string &why) {
+    p = JfaScorePlan();
+    if (!jfa_score_check_shape(T, J, K, D, Ry, Ru, mode, why)) return false;
+    if (lds_rows < 0 || lds_rows > JFA_LDS_MAX_R) {
+        why = fmt("jfa_lds_rows must be 0 (automatic) or 1 .. %lld", JFA_LDS_MAX_R);
+        return false;
+    }
+    if (n_cu < 1) {
+        why = "JFA scoring: the plan needs the number of compute units";
+        return false;
+    }
+    const int64_t rr = (int64_t)Ru * Ru, kd = (int64_t)K * D, J1 = J + 1;
+    p.mode = mode;
+    p.lds_rows = jfa_lds_limit(lds_rows);
+    p.path = Ru <= p.lds_rows ? 0 : 1;
+    p.bytes_N = T * K * 8;
+    p.bytes_F = T * kd * 8;
+    p.bytes_uE = 2 * (int64_t)Ru * kd * 8;
+    p.bytes_out = J * T * 8;
+    p.gemm_lds = 2 * JFA_KSTEP * (JFA_TILE + 4) * (int)sizeof(double);
+    p.gemm_yv = gemm_grid(J, kd);
+    if (mode == JFA_SCORE_LINEAR) {
+        p.chunk = T;
+        p.n_chunks = 1;
+        p.bytes_M = p.bytes_ME = J * kd * 8;
+        p.bytes_comp = T * kd * 8;
+        p.synth = p.scale_M = flat_grid(J * kd);
+        p.gemm_xu = gemm_grid(T, kd);
+        p.comp = flat_grid(T * kd);
+        p.gemm_out = gemm_grid(J, T);
+        return true;
+    }
+    p.seg_bytes = (rr + J1 * Ru) * (int64_t)sizeof(double);
+    p.chunk = std::min<int64_t>(std::min<int64_t>(T, scratch_bytes / p.seg_bytes), (int64_t)65535 * JFA_TILE);      // (row tiles: the GEMMs' grid y)
+    if (p.chunk < 1) {
+        why = fmt("JFA scoring: the scratch bound of %lld bytes is below one test segment's blocks of %lld bytes (Ru x Ru and (J + 1) x Ru doubles); "
+                  "raise the option jfa_scratch_mib or score fewer models at a time", scratch_bytes, p.seg_bytes);
+        return false;
+    }
+    if (rr * (int64_t)K > ((int64_t)1 << 40) || (int64_t)K * Ru * J1 > ((int64_t)1 << 40)) {
+        why = "JFA scoring: K x Ru x Ru or K x Ru x (J + 1) exceeds 2^40 elements; score fewer models at a time";
+        return false;
+    }
+    p.n_chunks = (T + p.chunk - 1) / p.chunk;
+    p.bytes_scratch = p.chunk * p.seg_bytes;
+    p.bytes_M = p.bytes_ME = J1 * kd * 8;
+    p.bytes_P = (int64_t)K * rr * 8;
+    p.bytes_q = J1 * K * 8;
+    p.bytes_G = (int64_t)K * Ru * J1 * 8;
+    p.bytes_lin = p.bytes_quad = T * J1 * 8;
+    p.bytes_a = T * Ru * 8;
+    p.synth = p.scale_M = flat_grid(J1 * kd);
+    p.scale_u = flat_grid(Ru * kd);
+    const int64_t gr = (Ru + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE, gj = (J1 + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE;
+    p.gram = JfaGrid{K, gr * gr};
+    p.cross = JfaGrid{K, gj};
+    p.cross_z = gr;
+    p.gemm_L = gemm_grid(p.chunk, rr);
+    p.gemm_a = gemm_grid(p.chunk, Ru);
+    p.gemm_lin = gemm_grid(p.chunk, J1);
+    p.gemm_quad = gemm_grid(p.chunk, J1);
+    p.gemm_h = gemm_grid(p.chunk, Ru * J1);
+    p.kscore = JfaGrid{p.chunk, 1};
+    p.gram_lds = 2 * JFA_GRAM_TILE * (JFA_GRAM_DSTEP + 1) * (int)sizeof(double) + JFA_GRAM_DSTEP * (int)sizeof(double);
+    p.cross_lds = 3 * JFA_GRAM_TILE * (JFA_GRAM_DSTEP + 1) * (int)sizeof(double);
+    p.kscore_lds = jfa_factor_lds_bytes(Ru, p.path);
+    p.kscore_rounds = (p.chunk + n_cu - 1) / n_cu;
+    return true;
+}
+
 }  // namespace sr

@@ -54,4 +54,39 @@ int jfa_factor_lds_bytes(int R, int path);
 // Fills `p` and returns true, or false with the reason.  lds_rows: the option jfa_lds_rows; n_cu: compute units (>= 1).
 bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, JfaPlan &p, std::string &why);
 
+// ---- trial scoring (jfa_score.hip): the score matrix [J][T] of J models against T test segments, with the channel factors
+// integrated out (the reference's kscore_famous_19.m) or by the linear approximation (linear_scoring.m).  With M_0 = m,
+// M_j = m + z_j .* d + y_j v, J1 = J + 1:
+//   q [J1][K] = sum_d M_j^2 / E      G [K][Ru][J1] = u_c (M_j,c ./ E_c)      once per call;
+//   L_t = I + sum_c N[t][c] P_c      a_t = u (F_t ./ E)      lin = F (M ./ E)^T      quad = N q^T      h [t][Ru][J1] = N G
+//   quad2[t][j] = || chol(L_t)^-1 (a_t - h[t][.][j]) ||^2      s = (lin - quad / 2 + quad2 / 2) / n_t      out[j-1][t] = s[t][j] - s[t][0]
+// The segments run in chunks whose L and h blocks fit the bound; nothing is summed over a chunk, so a chunk is any number of segments.
+constexpr int JFA_SCORE_INTEGRATED = 0, JFA_SCORE_LINEAR = 1;
+constexpr int64_t JFA_SCORE_MAX_J = (int64_t)65535 * JFA_GRAM_TILE - 1;       // (the cross kernel's model tiles are its grid y)
+
+struct JfaScorePlan {
+    int mode = 0;
+    int64_t chunk = 0, n_chunks = 0;        // test segments per chunk (linear mode: all T in one)
+    int64_t seg_bytes = 0;                  // inside the bound, per segment: the L block (Ru^2) and the h block ((J + 1) Ru), in doubles x 8
+    int64_t bytes_scratch = 0;              // chunk x seg_bytes
+    // outside the bound
+    int64_t bytes_M = 0, bytes_ME = 0, bytes_uE = 0, bytes_P = 0, bytes_q = 0, bytes_G = 0, bytes_N = 0, bytes_F = 0;
+    int64_t bytes_lin = 0, bytes_quad = 0, bytes_a = 0, bytes_out = 0, bytes_comp = 0;      // comp: linear mode's compensated statistics
+    int path = 0, lds_rows = 0;             // the factorisation path of jfa_kscore_kernel, as JfaPlan's
+    JfaGrid gemm_yv, synth, scale_M, scale_u, gram, cross, gemm_L, gemm_a, gemm_lin, gemm_quad, gemm_h, kscore;      // integrated (yv, synth, scale_M: both)
+    int64_t cross_z = 0;                    // the cross kernel's third grid dimension: tiles of 16 channel factors
+    JfaGrid gemm_xu, comp, gemm_out;        // linear
+    int gram_lds = 0, gemm_lds = 0, cross_lds = 0, kscore_lds = 0;
+    int64_t kscore_rounds = 0;              // rounds a full chunk's kscore launch makes over the chip at one workgroup a unit
+};
+
+// The refusals of the shape; of the arrays (a non-finite value anywhere, a negative N, E <= 0, linear mode without x, a mask that is not
+// [J][T]; d, z, x, mask may be null).  true, or false with the text (it names the remedy).
+bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, std::string &why);
+bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F, const double *m,
+                            const double *E, const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
+                            const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why);
+bool plan_jfa_score(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, JfaScorePlan &p,
+                    std::string &why);
+
 }  // namespace sr

@@ -248,6 +248,11 @@ void jfa_factors(SRJfa &h, const double *W, int R, double *y, double *A, double 
 void jfa_update(int K, int D, int R, const double *A, const double *C, double *W, int64_t *skipped);
 void jfa_train(SRJfa &h, double *W, int R, int n_iter, double *y, int64_t *skipped);
 void jfa_close(SRJfa *h);
+// jfa_score.hip: the score matrix out [J][T] of J models against T test segments, mode 0 integrated (kscore_famous_19.m), 1 linear
+// (linear_scoring.m; needs x).  d, z, x, mask: null = absent.  Every refusal (jfa_plan.cpp) comes before any device work.
+void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
+               const double *d, const double *v, const double *u, const double *z, const double *y, const double *x, const unsigned char *mask,
+               int64_t mask_rows, int64_t mask_cols, double *out, int64_t *empty_segments, int64_t *bad_segments);
 void set_jfa_scratch_mib(long v);
 long jfa_scratch_mib();
 void set_jfa_lds_rows(long v);

@@ -13,7 +13,9 @@ is left out.
 Past the statistics, the rest of that leg: ``estimate_y_and_v``, ``estimate_x_and_u`` (csrc/jfa.hip through ``FactorEstimator``:
 the gram matrices, the float64 GEMMs and the batched factorisation on the device), ``estimate_z_and_d`` and ``linear_scoring``
 (elementwise work and one small product: host, float64, as ``map_supervectors``), and the four ``sc_*`` driver scripts as the
-functions ``train_v``, ``train_u``, ``train_d`` and ``score_dot_product``.  Names, argument order and orientation are the
+functions ``train_v``, ``train_u``, ``train_d`` and ``score_dot_product``.  The score matrix of a verification run on the device
+(csrc/jfa_score.hip through ``score_trials``): ``kscore_famous_19``, the scorer with the channel factors integrated out, in the
+reference's own orientation, and ``score_integrated``, the sibling of ``score_dot_product`` that scores with it.  Names, argument order and orientation are the
 reference's: rows of ``F`` and ``N`` are segments, supervector columns are mixture-major, ``S`` is accepted and ignored, a scalar
 ``0`` for ``d``, ``u``, ``z``, ``y`` or ``x`` broadcasts as it does in MATLAB.  One stated difference: ``spk_ids`` are 0-BASED
 integer labels -- row i of ``y`` and ``z`` belongs to label i, rows of labels that do not occur stay zero.  Where the reference's
@@ -386,3 +388,88 @@ def score_dot_product(trn, tst, ubm, v, u, d):
     trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
     tst_x = estimate_x_and_u(sF, sN, None, m, E, d, v, u, 0, 0, 0, tst_ids)
     return linear_scoring(sF, sN, None, m, E, d, v, u, trn_z, yx[:, :ny], tst_x)
+
+
+# ---- trial scoring on the device (csrc/jfa_score.hip) ----
+
+def score_trials(F, N, m, E, d, v, u, z, y, x=None, mode="integrated", mask=None, return_counts=False):
+    """The score matrix [J, T] of J models against T test segments in ONE device call, float64, row orientation as the rest of
+    this module: raw statistics ``F`` [T, K * D] (not centred) and ``N`` [T, K], ``m``, ``E`` [K * D], ``d`` [K * D] (or None / 0),
+    ``v`` [Ry, K * D], ``u`` [Ru, K * D], the models' ``z`` [J, K * D] (or None / 0) and ``y`` [J, Ry].
+    ``mode`` "integrated": kscore_famous_19.m, the channel factors integrated out; "linear": linear_scoring.m, which needs the
+    segments' channel factors ``x`` [T, Ru].  ``mask``: [J, T], where it is 0 the score is 0.0 exactly.  A segment of no frames
+    scores 0.0 against every model.  ``return_counts``: -> (scores, {"empty_segments": n, "bad_segments": n})."""
+    from . import _lib
+    if mode not in ("integrated", "linear"):
+        raise ValueError("mode is 'integrated' or 'linear', got %r" % (mode,))
+    F = _f64(np.atleast_2d(F))
+    N = _f64(np.atleast_2d(N))
+    T, K = N.shape
+    if K < 1 or F.shape[0] != T or F.shape[1] % K:
+        raise ValueError("expected N [T, K] and F [T, K * D]; got %r and %r" % (N.shape, F.shape))
+    kd = F.shape[1]
+    m, E = _f64(np.reshape(m, -1), (kd,), "m"), _f64(np.reshape(E, -1), (kd,), "E")
+    v = _f64(np.atleast_2d(v))
+    u = _f64(np.atleast_2d(u))
+    y = _f64(np.atleast_2d(y))
+    J = y.shape[0]
+    if v.shape[1] != kd or u.shape[1] != kd or y.shape[1] != v.shape[0]:
+        raise ValueError("expected v [Ry, %d], u [Ru, %d], y [J, Ry]; got %r, %r, %r" % (kd, kd, v.shape, u.shape, y.shape))
+
+    def optional(a, shape, name):
+        if a is None or (np.ndim(a) == 0 and a == 0):
+            return None
+        return _f64(np.reshape(a, shape), shape, name)
+
+    d = optional(d, (kd,), "d")
+    z = optional(z, (J, kd), "z")
+    x = optional(x, (T, u.shape[0]), "x")
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (J, T):
+            raise ValueError("a mask of shape %r for a score matrix [%d, %d]: pass one value per (model, segment) pair" % (mask.shape, J, T))
+        mask = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+    out = np.zeros((J, T))
+    empty, bad = C.c_int64(0), C.c_int64(0)
+    opt = lambda a: _lib.as_dp(a) if a is not None else None                        # noqa: E731
+    mk = (mask.ctypes.data_as(C.POINTER(C.c_uint8)), J, T) if mask is not None else (None, 0, 0)
+    head = (T, J, K, kd // K, v.shape[0], u.shape[0], _lib.as_dp(N), _lib.as_dp(F), _lib.as_dp(m), _lib.as_dp(E), opt(d), _lib.as_dp(v),
+            _lib.as_dp(u), opt(z), _lib.as_dp(y))
+    if mode == "integrated":
+        _lib.check(_lib.lib().sr_jfa_score_integrated(*head, *mk, _lib.as_dp(out), C.byref(empty), C.byref(bad)), "sr_jfa_score_integrated")
+    else:
+        _lib.check(_lib.lib().sr_jfa_score_linear(*head, opt(x), *mk, _lib.as_dp(out), C.byref(empty)), "sr_jfa_score_linear")
+    return (out, {"empty_segments": int(empty.value), "bad_segments": int(bad.value)}) if return_counts else out
+
+
+def kscore_famous_19(F, N, S=None, m=None, E=None, d=0, v=None, u=None, z=0, y=None, x=0, scores=None):
+    """kscore_famous_19.m in that file's OWN orientation, which is columns (its code, not its header comment, decides):
+    ``F`` [K * D, T], ``N`` [K, T], ``m``, ``E``, ``d`` [K * D] (or [K * D, 1]), ``v`` [K * D, Ry], ``u`` [K * D, Ru], ``z`` [K * D, J],
+    ``y`` [Ry, J]; ``S`` and ``x`` are accepted and ignored as there; ``scores``: the mask [J, T], a score where it is 1 (None: all).
+    -> [J, T].  A transposing wrapper of ``score_trials``.  Not reproduced: the reference leaves the UBM's score un-subtracted
+    where a score is exactly 0."""
+    y = np.atleast_2d(np.asarray(y, dtype=np.float64))
+    J = y.shape[1]
+    zt = None if (np.ndim(z) == 0 and z == 0) else np.reshape(np.asarray(z, dtype=np.float64), (-1, J)).T
+    dv = None if (np.ndim(d) == 0 and d == 0) else np.reshape(d, -1)
+    mask = None if scores is None else np.asarray(scores) == 1
+    return score_trials(np.atleast_2d(np.asarray(F, dtype=np.float64)).T, np.atleast_2d(np.asarray(N, dtype=np.float64)).T, np.reshape(m, -1),
+                        np.reshape(E, -1), dv, np.atleast_2d(np.asarray(v, dtype=np.float64)).T, np.atleast_2d(np.asarray(u, dtype=np.float64)).T,
+                        zt, y.T, mode="integrated", mask=mask)
+
+
+def score_integrated(trn, tst, ubm, v, u, d):
+    """The sibling of ``score_dot_product``: the same enrolment factors (every enrolment segment a speaker of its own; y and x jointly
+    on the stacked [v; u], then z), scored against the test segments' raw statistics by the integrated scorer -- no point estimate
+    of the test segments' channel factors.  -> scores [n_enrolment, n_test]."""
+    m, E = _ubm_m_E(ubm)
+    tF, tN = (trn["F"], trn["N"]) if hasattr(trn, "keys") else trn
+    sF, sN = (tst["F"], tst["N"]) if hasattr(tst, "keys") else tst
+    v = _f64(np.atleast_2d(v))
+    u = _f64(np.atleast_2d(u))
+    ny = v.shape[0]
+    vu = np.vstack([v, u])
+    trn_ids = np.arange(np.atleast_2d(tN).shape[0])
+    yx = estimate_y_and_v(tF, tN, None, m, E, d, vu, 0, 0, 0, 0, trn_ids)
+    trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
+    return score_trials(sF, sN, m, E, d, v, u, trn_z, yx[:, :ny], mode="integrated")
