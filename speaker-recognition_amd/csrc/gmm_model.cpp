@@ -1,5 +1,6 @@
 // gmm_model.cpp -- text model format + parameter packing (host, float64 -> fp32 tables).
 #include "gmm_model.hpp"
+#include "score_shapes.hpp"
 
 #include <atomic>
 #include <algorithm>
@@ -824,6 +825,71 @@ PackedH2Shared pack_models_h2_shared(const std::vector<const GMM *> &models) {
     pm.pad_waste = 1.0 - ((double)K * S) / ((double)pm.n_tiles * MT * n_blocks * SHARED_SB);
     pm.ref = pack_models_split({models[0]}, SPLIT_F16X2);
     return pm;
+}
+
+PackedH2Compact pack_h2_compact(const PackedH2Shared &pm, int dim) {
+    PackedH2Compact pc;
+    if (pm.params.empty() || !h2c_applies(dim, pm.klf)) return pc;
+    const int h = h2c_half_steps(dim);
+    const H2cMap m = h2c_map(h);
+    pc.nk = m.nk;
+    pc.nf = m.nf;
+    pc.nb = m.nb;
+    const int c_slot = 8 * h - 1;                        // the constant's place in a part: the last slot of the last half-step
+    // where the flat order keeps part `part` (0 hi, 1 lo) of slot s of a part, as a slot of the flat contraction (-1: nowhere, zero)
+    auto flat_slot = [&](bool linear, int part, int s) {
+        if (s < dim) return part == 1 ? s : linear ? 2 * dim + 1 + s : 2 * dim + s;
+        if (linear && s == c_slot) return part == 1 ? dim : 3 * dim + 1;
+        return -1;
+    };
+    // frame side: descriptor of slot s of part `part` (0 low part of z, 1 high part)
+    auto b_desc = [&](bool linear, int part, int s) -> uint16_t {
+        if (s < dim) return (uint16_t)(s | ((part == 1 ? 1 : 2) << 8));
+        if (linear && s == c_slot && part == 1) return (uint16_t)(3 << 8);
+        return 0;
+    };
+    pc.q_desc.assign((size_t)m.nb * 16, 0);
+    pc.l_desc.assign((size_t)m.nb * 16, 0);
+    for (int r = 0; r < m.nb; r++)
+        for (int hh = 0; hh < 2; hh++)
+            for (int j = 0; j < 8; j++) {
+                const int half = m.b_half[r][hh];
+                if (half < 0) continue;
+                pc.q_desc[16 * r + 8 * hh + j] = b_desc(false, half >> 4, 8 * (half & 15) + j);
+                pc.l_desc[16 * r + 8 * hh + j] = b_desc(true, half >> 4, 8 * (half & 15) + j);
+            }
+    // u16 of a compact image -> u16 of the flat image it copies (-1: zero), for the two kinds of image
+    const size_t flat_u16 = (size_t)std::max(pm.kqf, pm.klf) * 64 * 8, img_u16 = (size_t)m.nf * 64 * 8;
+    std::vector<int> src[2];
+    for (int linear = 0; linear < 2; linear++) {
+        src[linear].assign(img_u16, -1);
+        for (int f = 0; f < m.nf; f++)
+            for (int hh = 0; hh < 2; hh++) {
+                const int half = m.a_half[f][hh];
+                if (half < 0) continue;
+                for (int j = 0; j < 8; j++) {
+                    const int c = flat_slot(linear != 0, half >> 4, 8 * (half & 15) + j);
+                    if (c < 0) continue;
+                    for (int i = 0; i < MT; i++)
+                        src[linear][((size_t)f * 64 + i + 32 * hh) * 8 + j] = (int)((((size_t)(c >> 4)) * 64 + i + 32 * ((c >> 3) & 1)) * 8 + (c & 7));
+                }
+            }
+    }
+    const size_t n_img = pm.params.size() / flat_u16;
+    const size_t per_block = (size_t)pm.n_tiles * (1 + SHARED_SB);
+    pc.params.assign(n_img * img_u16, 0);
+    for (size_t im = 0; im < n_img; im++) {
+        const uint16_t *from = pm.params.data() + im * flat_u16;
+        uint16_t *to = pc.params.data() + im * img_u16;
+        const int j_img = (int)(im % (1 + SHARED_SB));
+        if (j_img > pm.blocks[im / per_block].n_models) continue;           // a phantom model's image: zeros (its sums are never read)
+        const std::vector<int> &sv = src[j_img != 0];
+        for (size_t e = 0; e < img_u16; e++)
+            if (sv[e] >= 0) to[e] = from[sv[e]];
+    }
+    pc.blocks = pm.blocks;
+    for (size_t b = 0; b < pc.blocks.size(); b++) pc.blocks[b].offset_u4 = (uint32_t)((b * per_block * img_u16) / 8);
+    return pc;
 }
 
 // ---- mel gather starts (see gmm_model.hpp) ----

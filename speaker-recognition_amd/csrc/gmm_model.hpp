@@ -174,6 +174,18 @@ struct PackedH2Shared {
     PackedSplit ref;
 };
 PackedH2Shared pack_models_h2_shared(const std::vector<const GMM *> &models);
+// The same set in the pipelined kernel's COMPACT order (score_shapes.hpp: h2c_map): every image `nf` fragments of
+// [lane][8 x fp16] holding hi(A) once, the frame-side tables `nb` registers of 16 slots holding hi(z) once; blocks, mixture tiles
+// and images in the flat layout's order ([Q][L_0]..[L_14] per mixture tile, phantom images zeros).  A rearrangement of the flat
+// image's fp16 values (nothing is rounded again), made on the first use by that kernel.  Empty (nk = 0) where the form does not
+// apply (h2c_applies).  Host-only: tests/host/h2c_checks.cpp.
+struct PackedH2Compact {
+    int nk = 0, nf = 0, nb = 0;
+    std::vector<uint16_t> params;
+    std::vector<SharedBlock> blocks;
+    std::vector<uint16_t> q_desc, l_desc;
+};
+PackedH2Compact pack_h2_compact(const PackedH2Shared &pm, int dim);
 // Work items of the pipelined shared-sigma kernel over a table of tiles with `counts[t]` frames each (<= frames_per_tile): item =
 // {tile, tile or -1, tile or -1, tile or -1}.  Every FULL tile is an item of its own, in order; with `pack_tails` the ragged ones are
 // packed greedily, in order, up to four and up to frames_per_tile columns to an item, and all packed items come LAST (their waves
@@ -221,6 +233,12 @@ struct SRModelSet {
     sr::DevBuf<float> d_h2s_center, d_h2s_scale, d_h2s_ref_center, d_h2s_ref_scale;
     sr::DevBuf<sr::ChunkDesc> d_h2s_ref_chunks;
     sr::DevBuf<int> d_h2s_ref_gcb;
+    // ... and its compact order (PackedH2Compact), packed and uploaded on the first pass that takes the pipelined kernel
+    // (0 not looked at yet, -1 the form does not apply to this set, 1 on the device)
+    int h2c_state = 0;
+    int h2c_nk = 0;
+    sr::DevBuf<uint16_t> d_h2c_params, d_h2c_qdesc, d_h2c_ldesc;
+    sr::DevBuf<sr::SharedBlock> d_h2c_blocks;
     // Hybrid form of an ill-conditioned set (score.hpp): the mixtures whose expanded form would cancel in fp32 (tight and
     // far from the centre) as one sub-set on the direct-form vector engine, the rest as another on the matrix cores;
     // the two per-frame log-likelihoods are merged by a log-add-exp.  Empty unless the set needed it.

@@ -756,7 +756,13 @@ __device__ __forceinline__ void h2p_slot(f32x16 &cur, u32x4 &fu, float &s, float
     }
 }
 
-template <int KQF, int KLF>
+// CPT (the compact order, score_shapes.hpp: h2c_map): the image holds hi(A) once and the wave hi(z) once -- NF = 6 fragments and
+// 6 B registers for the 8 steps of the <8,8> chains instead of 8 and 8: a quarter less streamed into LDS, read from it and held
+// (a stage of four images is 24 pieces, two per wave; the ring 48 KiB, the quadratic-half fragments 72).  Step u multiplies
+// stored fragment a_of[u] by register b_of[u]; the read of the next image's fragment f goes into f's register in the step that
+// uses f last, so the reads leave in fragment order as before and the lgkmcnt counts follow from the map (h2c_younger).  The same
+// products as the flat order, summed in another order: the last bits differ, nothing else.
+template <int KQF, int KLF, bool CPT = false>
 __global__ __launch_bounds__(12 * 64, 3)
 void gmm_score_h2p_kernel(const H2sArgs a) {
     // G images per stage, a ring of NB stages, the LDS-DMA of a stage issued in slot DMA_AT of the image behind the barrier.
@@ -766,12 +772,16 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
     constexpr int SB = SHARED_SB, WAVES = 12, G = 4, NB = 2, DMA_AT = KLF / 2;
     constexpr int KM = KQF > KLF ? KQF : KLF;
     static_assert(KQF <= KLF, "the linear half is never the shorter one");
-    constexpr int IMG_U4 = KM * 64;
+    static_assert(!CPT || (KQF == H2C_KLF && KLF == H2C_KLF), "the compact order is built for the <8,8> chains");
+    static_assert(!CPT || h2c_map_ok(H2C_MAP), "compact order");
+    constexpr int NF = CPT ? H2C_MAP.nf : KM;                       // stored fragments per image
+    constexpr int NBQ = CPT ? H2C_MAP.nb : KQF, NBL = CPT ? H2C_MAP.nb : KLF;      // resident frame fragments per half
+    constexpr int IMG_U4 = NF * 64;
     constexpr int STAGE_U4 = G * IMG_U4;
     constexpr int N_IMG = 1 + SB;
     constexpr int N_STAGES = N_IMG / G;
     static_assert(N_IMG % G == 0 && N_STAGES >= 1, "stages tile the images of a mixture tile");
-    extern __shared__ uint4 h2s_bq_lds[];                                  // [WAVES][KQF][64]
+    extern __shared__ uint4 h2s_bq_lds[];                                  // [WAVES][NBQ][64]
     __shared__ uint4 ring[NB * STAGE_U4];
 
     const int tid = threadIdx.x;
@@ -812,7 +822,7 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
     const int blk_end = a.group_block_begin[g + 1];
 
     // ---- resident B fragments of this lane's frame ----
-    f16x8 bl[KLF];
+    f16x8 bl[NBL];
     float zmax = 0.0f;
     // this wave's work item (h2p_unit).  What describes it is read here and AGAIN at every close: ten more scalar registers held
     // across the image loop spilled 35 of them into vector lanes.
@@ -835,12 +845,12 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
     const bool valid = has && my_col < tile.count;
     const int64_t row = tile.start + (valid ? my_col : 0);
     {
-        f16x8 bq[KQF];
-        h2s_build_b<KQF>(bq, a.X + row * a.dim, a.center, a.scale, a.q_desc, hh, true, zmax);
+        f16x8 bq[NBQ];
+        h2s_build_b<NBQ>(bq, a.X + row * a.dim, a.center, a.scale, a.q_desc, hh, true, zmax);
 #pragma unroll
-        for (int ks = 0; ks < KQF; ks++) h2s_bq_lds[(wave * KQF + ks) * 64 + lane] = __builtin_bit_cast(uint4, bq[ks]);
+        for (int ks = 0; ks < NBQ; ks++) h2s_bq_lds[(wave * NBQ + ks) * 64 + lane] = __builtin_bit_cast(uint4, bq[ks]);
     }
-    h2s_build_b<KLF>(bl, a.X + row * a.dim, a.center, a.scale, a.l_desc, hh, false, zmax);
+    h2s_build_b<NBL>(bl, a.X + row * a.dim, a.center, a.scale, a.l_desc, hh, false, zmax);
     const float off = a.ref_ll[row] * H2S_LOG2E;
     if (zmax >= 255.0f) atomicOr(a.oor_flag, 1);
     const float safe_ll2 = a.clamp ? fmaxf(LSE_MINLOG2 + LSE_NEAR + a.log2_k, a.band_hi * H2S_LOG2E + 1.0f) : -3.0e38f;
@@ -869,7 +879,7 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                 ld_tile++;
             }
         };
-        u32x4 fr[KM];                         // (a native vector: asm operands cannot be HIP's struct vectors)
+        u32x4 fr[NF];                         // (a native vector: asm operands cannot be HIP's struct vectors)
         // fragment `U` of the image at LDS byte address `at`
         auto frag_read = [&](auto U, unsigned at) {
             constexpr int u = decltype(U)::value;
@@ -884,7 +894,7 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
         if (NB > 2 && n_stage_total > 2) stage_load_next(2);
         wait_stages(n_stage_total > NB - 1 ? NB - 1 : n_stage_total - 1);
         barrier();
-        h2p_for<0, KQF>([&](auto U) { frag_read(U, ring_lane); });
+        h2p_for<0, (CPT ? NF : KQF)>([&](auto U) { frag_read(U, ring_lane); });
 
         f32x16 acc[2];
         acc[0] = zero1;
@@ -917,19 +927,28 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                 // LDS-DMA stream in flight, not only for itself)
                 constexpr int BW = KQF < 4 ? KQF : 4;
                 f16x8 bqt[BW];
-                auto bq_load = [&](int ks) { return __builtin_bit_cast(f16x8, h2s_bq_lds[(wave * KQF + ks) * 64 + lane]); };
+                // (CPT: the window goes by steps, so the two registers the chain uses twice are read twice -- once per 16 images)
+                auto bq_load = [&](int ks) { return __builtin_bit_cast(f16x8, h2s_bq_lds[(wave * NBQ + ks) * 64 + lane]); };
                 if constexpr (img == 0) {
+                    if constexpr (CPT) {
+                        h2p_for<0, BW>([&](auto KS) { bqt[decltype(KS)::value] = bq_load(H2C_MAP.b_of[decltype(KS)::value]); });
+                    } else {
 #pragma unroll
-                    for (int ks = 0; ks < BW; ks++) bqt[ks] = bq_load(ks);
+                        for (int ks = 0; ks < BW; ks++) bqt[ks] = bq_load(ks);
+                    }
                 }
                 constexpr bool ONE_ASM = kn >= 5;              // (shorter chains: more than 4 exps per slot)
+                static_assert(!CPT || ONE_ASM, "the compact order is written for the one-statement slots");
                 constexpr int sum_model = carry ? prev_model : 0;          // (an operand has to name something)
                 if constexpr (ONE_ASM) {
                     h2p_for<0, kn>([&](auto U) {
                         constexpr int u = decltype(U)::value;
                         if constexpr (gi == G - 1 && DMA_AT != 0 && u == DMA_AT)
                             if (S + NB < n_stage_total) stage_load_next(slot_cur);
-                        constexpr int younger = (kn - 1 - u) + (u < kn_next ? u : kn_next);
+                        // stored fragment, frame register, "this step reads the next image's fragment into the register it just used"
+                        constexpr int fa = CPT ? H2C_MAP.a_of[u] : u, bi = CPT ? H2C_MAP.b_of[u] : u;
+                        constexpr bool rd = CPT ? H2C_MAP.a_last[fa] == u : (u < kn_next);
+                        constexpr int younger = CPT ? h2c_younger(H2C_MAP, u) : (kn - 1 - u) + (u < kn_next ? u : kn_next);
                         static_assert(younger <= 15, "lgkmcnt is a 4-bit field");
                         constexpr int e0 = carry ? h2p_cum(kn, u - 2) : 0, e1 = carry ? h2p_cum(kn, u - 1) : 0, e2 = carry ? h2p_cum(kn, u) : 0;
                         constexpr int NA = e1 - e0, NX = e2 - e1;
@@ -937,13 +956,13 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                                     p3 = prev[e1 + 3 < 16 ? e1 + 3 : 15];
                         if constexpr (img == 0)
                         {
-                            h2p_slot<u == 0 ? 0 : 2, (u < kn_next), NA, NX, younger, u * 1024>(cur, fr[u], ssum[sum_model], e[0], e[1], e[2], e[3], bqt[u % BW],
-                                                                                               qacc, next_at, p0, p1, p2, p3);
-                            if constexpr (u + BW < KQF) bqt[u % BW] = bq_load(u + BW);
+                            h2p_slot<u == 0 ? 0 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], ssum[sum_model], e[0], e[1], e[2], e[3], bqt[u % BW],
+                                                                                     qacc, next_at, p0, p1, p2, p3);
+                            if constexpr (u + BW < KQF) bqt[u % BW] = bq_load(CPT ? H2C_MAP.b_of[u + BW] : u + BW);
                         }
                         else
-                            h2p_slot<u == 0 ? 1 : 2, (u < kn_next), NA, NX, younger, u * 1024>(cur, fr[u], ssum[sum_model], e[0], e[1], e[2], e[3], bl[u], qacc,
-                                                                                               next_at, p0, p1, p2, p3);
+                            h2p_slot<u == 0 ? 1 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], ssum[sum_model], e[0], e[1], e[2], e[3], bl[bi], qacc,
+                                                                                     next_at, p0, p1, p2, p3);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 } else {
@@ -979,7 +998,7 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 }
-                h2p_for<kn, kn_next>([&](auto U) { frag_read(U, next_at); });          // (a Q image shorter than the L image after it)
+                if constexpr (!CPT) h2p_for<kn, kn_next>([&](auto U) { frag_read(U, next_at); });          // (a Q image shorter than the L image after it)
                 if constexpr (carry) {
                     constexpr int e0 = h2p_cum(kn, kn - 2), e1 = h2p_cum(kn, kn - 1);
                     if constexpr (kn <= 1) {
@@ -1257,8 +1276,11 @@ void gmm_score_h2s_online_kernel(const H2sArgs a) {
     }
 }
 
-template <int KQF, int KLF, int COLS, int WAVES, bool PIN = false, bool MS = false>
+template <int KQF, int KLF, int COLS, int WAVES, bool PIN = false, bool MS = false, bool CPT = false>
 static int launch_h2s(const H2sLaunch &l) {
+    static_assert(!CPT || PIN, "the compact image is the pipelined kernel's");
+    // the main kernel's chain lengths: the compact order runs D = 37 (flat <7,8>) on the <8,8> chains too
+    constexpr int MQ = CPT ? H2C_KLF : KQF, ML = CPT ? H2C_KLF : KLF;
     constexpr bool BQ_LDS = h2s_bq_in_lds(KQF, KLF, WAVES);
     H2sArgs a;
     a.X = l.X;
@@ -1288,6 +1310,12 @@ static int launch_h2s(const H2sLaunch &l) {
     a.force_exc = l.force_exc;
     a.plan_inline = l.n_tiles <= H2S_PLAN_INLINE_MAX_TILES;
     a.band_hi = l.band_hi;
+    if constexpr (CPT) {          // (the exception pass below reads the flat image: put back behind the main launches)
+        a.params = reinterpret_cast<const uint4 *>(l.c_params);
+        a.blocks = l.c_blocks;
+        a.q_desc = l.c_q_desc;
+        a.l_desc = l.c_l_desc;
+    }
     // long grids in launches of ~H2S_ROUNDS_PER_LAUNCH rounds of resident workgroups (see the kernel)
     constexpr int TILES_WG = MS ? 1 : WAVES * COLS;
     const int resident = ctx().n_cu * (WAVES > 4 ? 1 : h2s_waves_per_eu(KQF, KLF, COLS, WAVES, MS));
@@ -1323,12 +1351,14 @@ static int launch_h2s(const H2sLaunch &l) {
         // (the model-split shape: gmm_score_h2m_kernel, fragments straight into registers, where two sets of them fit; the LDS form
         // of round 4 for the longest chains -- D = 46 .. 48 -- whose two sets spill)
         constexpr bool M_DIRECT = MS && KLF <= H2M_MAX_KLF;
-        constexpr size_t dyn = M_DIRECT ? 0 : (BQ_LDS ? (size_t)WAVES * KQF * 64 * sizeof(uint4) : 0) + (MS ? sizeof(uint4) : 0);
+        constexpr size_t dyn = CPT      ? (size_t)WAVES * H2C_MAP.nb * 64 * sizeof(uint4)
+                               : M_DIRECT ? 0
+                                          : (BQ_LDS ? (size_t)WAVES * KQF * 64 * sizeof(uint4) : 0) + (MS ? sizeof(uint4) : 0);
         if constexpr (dyn > 0) {
             static bool attr_set[MAX_DEVICES] = {};
             if (!attr_set[ctx().device]) {
                 if constexpr (PIN)
-                    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2p_kernel<KQF, KLF>),
+                    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2p_kernel<MQ, ML, CPT>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
                 else
                     SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2s_kernel<KQF, KLF, COLS, WAVES, MS>),
@@ -1337,13 +1367,19 @@ static int launch_h2s(const H2sLaunch &l) {
             }
         }
         if constexpr (PIN)
-            hipLaunchKernelGGL((gmm_score_h2p_kernel<KQF, KLF>), grid, dim3(WAVES * 64), dyn, ctx().stream, a);
+            hipLaunchKernelGGL((gmm_score_h2p_kernel<MQ, ML, CPT>), grid, dim3(WAVES * 64), dyn, ctx().stream, a);
         else if constexpr (M_DIRECT)
             hipLaunchKernelGGL((gmm_score_h2m_kernel<KQF, KLF>), grid, dim3(WAVES * 64), 0, ctx().stream, a);
         else
             hipLaunchKernelGGL((gmm_score_h2s_kernel<KQF, KLF, COLS, WAVES, MS>), grid, dim3(WAVES * 64), dyn, ctx().stream, a);
     }
     a.tile_base = 0;
+    if constexpr (CPT) {
+        a.params = reinterpret_cast<const uint4 *>(l.params);
+        a.blocks = l.blocks;
+        a.q_desc = l.q_desc;
+        a.l_desc = l.l_desc;
+    }
     // the exception pass: the plan (one wave per block cuts its list into items of <= 32 listed frames), then 4-wave workgroups over
     // the items (a couple of resident ones per block and CU's worth of the chip; with nothing listed -- the usual case -- they
     // leave at once)
@@ -1357,6 +1393,8 @@ static int launch_h2s(const H2sLaunch &l) {
 int launch_score_h2_shared(const H2sLaunch &l, int KQF, int KLF) {
 #define SR_H2S_CASE(Q, L)                                       \
     if (KQF == Q && KLF == L) {                                 \
+        if constexpr (L == H2C_KLF)                             \
+            if (l.shape == 2 && l.c_params) return launch_h2s<Q, L, 1, 12, true, false, true>(l); \
         if constexpr (h2p_fits(Q, L))                           \
             if (l.shape == 2) return launch_h2s<Q, L, 1, 12, true>(l); \
         if (l.shape == 3) return launch_h2s<Q, L, 1, 4, false, true>(l); \

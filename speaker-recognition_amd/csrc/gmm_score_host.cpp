@@ -148,6 +148,26 @@ static void ensure_h2s_layout(SRModelSet &s) {
     sync_stream();
 }
 
+// The compact order of the same set (PackedH2Compact), for the pipelined kernel: a rearrangement of the flat image, made and
+// uploaded by the first pass that takes that kernel -- a set that only ever serves small batches never pays for it.
+static bool ensure_h2c_layout(SRModelSet &s) {
+    if (s.h2c_state != 0) return s.h2c_state > 0;
+    const PackedH2Shared &h = s.h2s;
+    if (!h2c_built(s.host.dim, h.klf)) {
+        s.h2c_state = -1;
+        return false;
+    }
+    const PackedH2Compact c = pack_h2_compact(h, s.host.dim);
+    s.d_h2c_params.upload(c.params.data(), c.params.size());
+    s.d_h2c_blocks.upload(c.blocks.data(), c.blocks.size());
+    s.d_h2c_qdesc.upload(c.q_desc.data(), c.q_desc.size());
+    s.d_h2c_ldesc.upload(c.l_desc.data(), c.l_desc.size());
+    sync_stream();
+    s.h2c_nk = c.nk;
+    s.h2c_state = 1;
+    return true;
+}
+
 static void ensure_h2_layout(SRModelSet &s) {
     if (s.d_h2_params.p) return;
     s.d_h2_params.upload(s.h2.params.data(), s.h2.params.size());
@@ -262,15 +282,26 @@ static void launch_shared_f16(SRModelSet &set, SRBatch &feat, TileTable &tt, con
     a.log2_k = (float)std::log2((double)h.n_tiles * MT);
     a.force_exc = opt.h2s_force_exc;
     a.shape = h2s_shape;
+    bool compact = false;
     if (h2s_shape == 2) {      // the pipelined kernel walks work items: ragged tail tiles share a wave
         ensure_work_table(tt, opt.h2s_pack_tails != 0);
         a.tiles = tt.d_tiles_work.p;
         a.n_work = tt.n_work;
+        // ... on the compact image where the form applies (score_h2s_shape = 5: on the flat one, for A/B)
+        compact = opt.h2s_shape != 5 && ensure_h2c_layout(set);
+        if (compact) {
+            a.c_params = set.d_h2c_params.p;
+            a.c_blocks = set.d_h2c_blocks.p;
+            a.c_q_desc = set.d_h2c_qdesc.p;
+            a.c_l_desc = set.d_h2c_ldesc.p;
+        }
     }
     snprintf(g_last_kernel, sizeof(LastKernel::name),
-             "%s<%d,%d,%s> (shared sigma: quadratic half once per %d models; split-fp16 MFMA, "
+             "%s<%d,%d,%s>%s (shared sigma: quadratic half once per %d models; split-fp16 MFMA, "
              "3 products as one contraction; reference-offset log-sum-exp)", h2s_shape == 2 ? "gmm_score_h2p_kernel" : (h2s_shape == 3 && h2s_msplit_direct(h.klf)) ? "gmm_score_h2m_kernel" : "gmm_score_h2s_kernel",
-             h.kqf, h.klf, h2s_shape == 2 ? "waves=12, pipelined in the wave" : h2s_shape == 1 ? "waves=12" : h2s_shape == 3 ? "waves=4 on one tile, models split" : "waves=4", SHARED_SB);
+             compact ? set.h2c_nk : h.kqf, compact ? set.h2c_nk : h.klf,
+             h2s_shape == 2 ? "waves=12, pipelined in the wave" : h2s_shape == 1 ? "waves=12" : h2s_shape == 3 ? "waves=4 on one tile, models split" : "waves=4",
+             compact ? "/compact" : "", SHARED_SB);
     ScopedKernelTimer t(T_SCORE);
     const int n_launches = launch_score_h2_shared(a, h.kqf, h.klf);
     const size_t len = strlen(g_last_kernel);

@@ -106,6 +106,11 @@ struct H2sLaunch {
     float log2_k;
     int force_exc;
     int shape = 0;          // 0: 4-wave workgroups; 1: 12-wave workgroups (`tiles` = 32-frame tiles); 2: 12 waves, pipelined (gmm_score_h2p_kernel)
+    // pipelined shape on the COMPACT image (PackedH2Compact; null: on the flat one): what its main kernel reads instead of `params`,
+    // `blocks`, `q_desc`, `l_desc` -- the exception pass behind it keeps the flat ones
+    const uint16_t *c_params = nullptr;
+    const SharedBlock *c_blocks = nullptr;
+    const uint16_t *c_q_desc = nullptr, *c_l_desc = nullptr;
     float band_hi = -__builtin_inff();
 };
 int launch_score_h2_shared(const H2sLaunch &a, int KQF, int KLF);

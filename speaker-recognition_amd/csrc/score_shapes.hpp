@@ -37,6 +37,100 @@ SR_HD constexpr int h2s_waves_per_eu(int kqf, int klf, int cols, int waves, bool
 constexpr int H2M_MAX_KLF = 9;        // two register sets of fragments fit up to here (D <= 45); the longest chains keep the LDS form
 // LDS the pipelined kernel takes: its ring of two stages of four images plus the 12 waves' quadratic-half fragments
 SR_HD constexpr bool h2p_fits(int kqf, int klf) { return klf >= 2 && kqf <= klf && (2 * 4 * klf + 12 * kqf) * 1024 <= 160 * 1024; }
+
+// The COMPACT image and contraction order of the pipelined kernel.  The flat order [lo(A) hi(z) | hi(A) lo(z) | hi(A) hi(z)] stores
+// hi(A) twice and keeps hi(z) twice in every wave's resident fragments.  A part (D dimensions + the constant) is h = ceil((D + 1) / 8)
+// half-steps of 8 slots -- the 8 slots one half-wave holds of a 16-slot MFMA step -- so the duplicates can be lined up with whole
+// fragments and dropped: H_p / L_p = half-step p of hi(A) / lo(A) (the constant's parts in the last slot of the last half-step of the
+// linear half), zh_p / zl_p the same of the frame side (the constant 1 in zh; a 0 in zl where it would meet hi(C)).
+//   even h:  A fragments (H0,H1) .. | (L0,L1) ..;  B registers (zl0,zl1) .. | (zh0,zh1) ..
+//            chain  H x zl | H x zh (the H fragments again) | L x zh (the zh registers again)
+//   odd h:   A fragments (H0,H1) .. (H_{h-1},H_{h-1}) | (L0,L1) .. (L_{h-1},0);  B registers (zl pairs) | (zh pairs) | (zl_{h-1},zh_{h-1}) | (zh_{h-1},0)
+//            chain  H pairs x zl pairs | H pairs x zh pairs | (H,H)_{h-1} x (zl,zh)_{h-1} | L pairs x zh pairs | (L_{h-1},0) x (zh_{h-1},0)
+// The same multiset of products in ceil(3h / 2) steps -- never fewer than the flat order's KLF = ceil((3D + 2) / 16), so the form
+// applies where the two are equal (3h <= 2 KLF: D = 37 .. 39 of the <8,8> chains, not D = 40 .. 42) -- with h or h + 1 stored
+// fragments and as many B registers instead of KLF of each.  A half is part * 16 + p (A: part 0 = hi, 1 = lo; B: 0 = low part of z,
+// 1 = high part), -1 = zeros.
+constexpr int H2C_MAX_STEPS = 16;
+struct H2cMap {
+    int h = 0, nk = 0, nf = 0, nb = 0;                     // half-steps per part, chain steps, stored fragments, B registers
+    int a_of[H2C_MAX_STEPS] = {}, b_of[H2C_MAX_STEPS] = {};         // step -> stored fragment / B register
+    int a_last[H2C_MAX_STEPS] = {}, b_last[H2C_MAX_STEPS] = {};     // stored fragment / B register -> the step that uses it last
+    int a_half[H2C_MAX_STEPS][2] = {}, b_half[H2C_MAX_STEPS][2] = {};
+};
+SR_HD constexpr int h2c_half_steps(int dim) { return (dim + 1 + 7) / 8; }
+SR_HD constexpr int h2c_steps(int h) { return (3 * h + 1) / 2; }
+SR_HD constexpr bool h2c_applies(int dim, int klf) { return dim >= 1 && h2c_steps(h2c_half_steps(dim)) == klf && klf <= H2C_MAX_STEPS; }
+SR_HD constexpr H2cMap h2c_map(int h) {
+    H2cMap m;
+    m.h = h;
+    m.nk = h2c_steps(h);
+    const int np = h / 2, odd = h & 1;                     // whole pairs of half-steps; a single one left over
+    const int nh = np + odd;                               // fragments of hi(A), and of lo(A)
+    m.nf = 2 * nh;
+    m.nb = 2 * nh;
+    for (int i = 0; i < np; i++) {
+        m.a_half[i][0] = 2 * i;                 m.a_half[i][1] = 2 * i + 1;                 // (H_2i, H_2i+1)
+        m.a_half[nh + i][0] = 16 + 2 * i;       m.a_half[nh + i][1] = 16 + 2 * i + 1;       // (L_2i, L_2i+1)
+        m.b_half[i][0] = 2 * i;                 m.b_half[i][1] = 2 * i + 1;                 // (zl_2i, zl_2i+1)
+        m.b_half[np + i][0] = 16 + 2 * i;       m.b_half[np + i][1] = 16 + 2 * i + 1;       // (zh_2i, zh_2i+1)
+    }
+    if (odd) {
+        m.a_half[np][0] = h - 1;                m.a_half[np][1] = h - 1;                    // (H_{h-1}, H_{h-1})
+        m.a_half[nh + np][0] = 16 + h - 1;      m.a_half[nh + np][1] = -1;                  // (L_{h-1}, 0)
+        m.b_half[2 * np][0] = h - 1;            m.b_half[2 * np][1] = 16 + h - 1;           // (zl_{h-1}, zh_{h-1})
+        m.b_half[2 * np + 1][0] = 16 + h - 1;   m.b_half[2 * np + 1][1] = -1;               // (zh_{h-1}, 0)
+    }
+    int k = 0;
+    for (int i = 0; i < np; i++, k++) { m.a_of[k] = i;      m.b_of[k] = i; }                // H pairs x zl pairs
+    for (int i = 0; i < np; i++, k++) { m.a_of[k] = i;      m.b_of[k] = np + i; }           // H pairs x zh pairs
+    if (odd) { m.a_of[k] = np; m.b_of[k] = 2 * np; k++; }                                  // (H,H) x (zl,zh)
+    for (int i = 0; i < np; i++, k++) { m.a_of[k] = nh + i; m.b_of[k] = np + i; }           // L pairs x zh pairs
+    if (odd) { m.a_of[k] = nh + np; m.b_of[k] = 2 * np + 1; k++; }                         // (L,0) x (zh,0)
+    for (int s = 0; s < m.nk; s++) {
+        m.a_last[m.a_of[s]] = s;
+        m.b_last[m.b_of[s]] = s;
+    }
+    return m;
+}
+// The pipelined kernel reads fragment f of the NEXT image into its register in the step that uses f of this image last; LDS returns
+// in order, so the wait in front of step u's MFMA names how many of the wave's own fragment reads were issued after the one that
+// filled a_of[u]: the rest of the previous image's, then this image's so far.
+SR_HD constexpr int h2c_younger(const H2cMap &m, int u) {
+    const int lu = m.a_last[m.a_of[u]];
+    int n = 0;
+    for (int f = 0; f < m.nf; f++) n += (m.a_last[f] > lu) + (m.a_last[f] < u);
+    return n;
+}
+// What the kernel relies on: every step's operands exist, every stored fragment and B register is used, the fragments' last uses
+// come in fragment order (the block's first image is read F0, F1, .. in front of the loop: the same order), and no wait count
+// leaves lgkmcnt's four bits.
+SR_HD constexpr bool h2c_map_ok(const H2cMap &m) {
+    if (m.nk > H2C_MAX_STEPS || m.nf > m.nk || m.nb > m.nk || m.nk != h2c_steps(m.h)) return false;
+    for (int f = 0; f < m.nf; f++) {
+        bool used = false;
+        for (int s = 0; s < m.nk; s++) used = used || m.a_of[s] == f;
+        if (!used || (f > 0 && m.a_last[f] <= m.a_last[f - 1])) return false;
+    }
+    for (int r = 0; r < m.nb; r++) {
+        bool used = false;
+        for (int s = 0; s < m.nk; s++) used = used || m.b_of[s] == r;
+        if (!used) return false;
+    }
+    for (int s = 0; s < m.nk; s++)
+        if (m.a_of[s] < 0 || m.a_of[s] >= m.nf || m.b_of[s] < 0 || m.b_of[s] >= m.nb || h2c_younger(m, s) > 15) return false;
+    return true;
+}
+// the one chain length the compact kernel is built for (KQF = KLF = 8 steps, h = 5: D = 37 .. 39 -- BASELINE configs[2] / [3])
+constexpr int H2C_KLF = 8, H2C_H = 5;
+constexpr H2cMap H2C_MAP = h2c_map(H2C_H);
+static_assert(h2c_map_ok(h2c_map(H2C_H)) && h2c_map(H2C_H).nk == H2C_KLF && h2c_map(H2C_H).nf == 6 && h2c_map(H2C_H).nb == 6, "the compact order of the <8,8> chains");
+static_assert(h2c_map_ok(h2c_map(4)) && h2c_map_ok(h2c_map(3)) && h2c_map_ok(h2c_map(6)) && h2c_map_ok(h2c_map(1)), "even and odd part lengths");
+SR_HD constexpr bool h2c_built(int dim, int klf) { return klf == H2C_KLF && h2c_applies(dim, klf) && h2c_half_steps(dim) == H2C_H; }
+// LDS of the compact form: a ring of two stages of four images of nf fragments plus the 12 waves' nb quadratic-half fragments
+SR_HD constexpr int h2c_lds_bytes(int h) { return (2 * 4 * h2c_map(h).nf + 12 * h2c_map(h).nb) * 1024; }
+static_assert(h2c_lds_bytes(H2C_H) <= 160 * 1024 && (4 * h2c_map(H2C_H).nf) % 12 == 0, "the compact ring fits a CU; a stage is a whole number of pieces per wave");
+
 // workgroups resident per CU, and 32-frame tiles per workgroup, of shape `shape` (0: 4 waves; 1: 12 waves; 2: 12 waves, pipelined;
 // 3: 4 waves on one tile, the block's models split between them)
 constexpr int h2s_resident_per_cu(int kqf, int klf, int shape) { return (shape == 0 || shape == 3) ? h2s_waves_per_eu(kqf, klf, 1, 4, shape == 3) : 1; }
