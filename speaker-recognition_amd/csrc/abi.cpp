@@ -1226,9 +1226,10 @@ int sr_set_option(const char *key, long value) {
                  "(never selected: 1.45-1.8x slower than split-bf16 at the same accuracy)");
         score_options().engine = (int)value;
     } else if (k == "score_h2s_shape") {
-        if (value < 0 || value > 5)
+        if (value < 0 || value > 6)
             fail("score_h2s_shape must be 0 (automatic), 1 (4-wave workgroups), 2 (12-wave workgroups), 3 (12 waves, image loop pipelined inside the wave), "
-                 "4 (4 waves on one tile, the block's models split between them) or 5 (as 3, on the flat image where 3 takes the compact one)");
+                 "4 (4 waves on one tile, the block's models split between them), 5 (as 3, on the flat image where 3 takes the compact one) "
+                 "or 6 (as 3, one quadratic half per block where 3 forms one per two blocks)");
         score_options().h2s_shape = (int)value;
     } else if (k == "flush_list_cap") {
         if (value < 0) fail("flush_list_cap must be >= 0");

@@ -29,7 +29,8 @@
 //     (profiles/r02_h2s_stalls.txt).
 //
 // Stream order per block of 15 models, per mixture tile: [Q][L_0]...[L_14], 16 images of KF KiB
-// ([ks][lane][8 x fp16]: one ds_read_b128 per lane and MFMA).
+// ([ks][lane][8 x fp16]: one ds_read_b128 per lane and MFMA).  (The compact pipelined kernel runs two blocks behind the first
+// one's Q image -- gmm_score_h2p_kernel, PAIR -- on the same stream.)
 #include "lse.hpp"
 #include "score.hpp"
 #include "wave_ops.hpp"
@@ -762,7 +763,20 @@ __device__ __forceinline__ void h2p_slot(f32x16 &cur, u32x4 &fu, float &s, float
 // stored fragment a_of[u] by register b_of[u]; the read of the next image's fragment f goes into f's register in the step that
 // uses f last, so the reads leave in fragment order as before and the lgkmcnt counts follow from the map (h2c_younger).  The same
 // products as the flat order, summed in another order: the last bits differ, nothing else.
-template <int KQF, int KLF, bool CPT = false>
+//
+// PAIR (the compact form only; score_shapes.hpp: h2q_*): Q_k(x) is the same for every model of the set, and one Q image per block of
+// 15 models is 14 of configs[2]'s 216 images per mixture tile that the result does not need.  The workgroup walks its group's blocks
+// two at a time behind ONE Q image -- per mixture tile [Q][L_0 .. L_14][L'_0 .. L'_(m-1)], Q - O held in `qacc` across all of them,
+// 30 running sums live across the mixture-tile loop -- and a group's odd last block alone, as before.  A full pair is 31 images, 7
+// stages of four and one of three (the 32nd slot executes nothing; its image is loaded: the second block's stages start at ITS
+// image 1, so its last stage ends on image 0 of the next tile, or on the device buffer's one image of padding).  What hung on
+// "image G - 1 of the stage" hangs on "last image of the stage"; the last executed image of a tile -- whose epilogue the next tile's
+// Q image carries -- is image 30 in acc[0] for a full pair and an odd one in acc[1] otherwise: wave-uniform per pair; the Q image
+// reads acc[0], and an odd last image is moved there behind one scalar branch per mixture tile.  Each block closes on its own (its index, its SharedBlock, its sums, its
+// exception list).  Every block's Q image holds the same values and a model's products and their order do not change, so the
+// results are those of the unpaired form bit for bit -- but for the model whose image is the last one executed in a tile, in either
+// form (its per-tile contributions are summed apart and added at the close).  210 images instead of 216 at 201 models.
+template <int KQF, int KLF, bool CPT = false, bool PAIR = false>
 __global__ __launch_bounds__(12 * 64, 3)
 void gmm_score_h2p_kernel(const H2sArgs a) {
     // G images per stage, a ring of NB stages, the LDS-DMA of a stage issued in slot DMA_AT of the image behind the barrier.
@@ -774,13 +788,15 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
     static_assert(KQF <= KLF, "the linear half is never the shorter one");
     static_assert(!CPT || (KQF == H2C_KLF && KLF == H2C_KLF), "the compact order is built for the <8,8> chains");
     static_assert(!CPT || h2c_map_ok(H2C_MAP), "compact order");
+    static_assert(!PAIR || (CPT && SB == H2Q_SB && G == H2Q_G), "pairs of blocks: the compact form, blocks of 15, stages of four");
     constexpr int NF = CPT ? H2C_MAP.nf : KM;                       // stored fragments per image
     constexpr int NBQ = CPT ? H2C_MAP.nb : KQF, NBL = CPT ? H2C_MAP.nb : KLF;      // resident frame fragments per half
     constexpr int IMG_U4 = NF * 64;
     constexpr int STAGE_U4 = G * IMG_U4;
-    constexpr int N_IMG = 1 + SB;
-    constexpr int N_STAGES = N_IMG / G;
-    static_assert(N_IMG % G == 0 && N_STAGES >= 1, "stages tile the images of a mixture tile");
+    constexpr int N_IMG_T = 1 + SB;                                 // a block's images per mixture tile, in the stream
+    constexpr int N_IMG = PAIR ? 1 + 2 * SB : 1 + SB;               // images a mixture tile executes at most
+    constexpr int N_STAGES = N_IMG_T / G;                           // a block's stages per mixture tile
+    static_assert(N_IMG_T % G == 0 && N_STAGES >= 1, "stages tile the images of a mixture tile");
     extern __shared__ uint4 h2s_bq_lds[];                                  // [WAVES][NBQ][64]
     __shared__ uint4 ring[NB * STAGE_U4];
 
@@ -857,23 +873,41 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
     const f32x16 zero1 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned ring_lane = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)ring + (unsigned)lane * 16u;   // LDS byte address
 
-    for (int blk = blk_begin; blk < blk_end; blk++) {
+    int n_blk = 1;                                     // blocks this turn of the loop takes: PAIR, two where there are two
+    for (int blk = blk_begin; blk < blk_end; blk += n_blk) {
         const SharedBlock sb = a.blocks[blk];
         const uint4 *stream = a.params + sb.offset_u4;
+        // PAIR: the second block's images of a tile, addressed by the PAIR's stage (4 .. 7: its images 1 .. 16); what describes the
+        // blocks is read again at the close (as the work item is)
+        const uint4 *stream2 = stream;
+        int m2 = 0;
+        if constexpr (PAIR) {
+            if (blk + 1 < blk_end && h2q_pairs(SB, sb.n_models, 1)) {
+                const SharedBlock sb2 = a.blocks[blk + 1];
+                m2 = sb2.n_models;
+                stream2 = a.params + sb2.offset_u4 + (size_t)h2q_stage_image(SB, G, N_STAGES) * IMG_U4 - (size_t)N_STAGES * STAGE_U4;
+            }
+            n_blk = m2 > 0 ? 2 : 1;
+        }
         // ssum[SB]: the LAST executed image of a mixture tile has its epilogue carried by the next tile's Q image (and by the drain
         // behind the loop); which model that is depends on the block (below), so its sum is kept apart until the close
         float ssum[SB + 1];
+        float ssum2[PAIR ? SB : 1];                           // PAIR: the second block's
 #pragma unroll
         for (int si = 0; si <= SB; si++) ssum[si] = 0.0f;
+#pragma unroll
+        for (int si = 0; si < (PAIR ? SB : 1); si++) ssum2[si] = 0.0f;
         // A block of fewer than SB models (the last one of a set: 201 = 13 x 15 + 6) runs only the stages that hold a model: its
         // images are there in the stream (zeros), but 8 of configs[2]'s 224 images per mixture tile are not worth 3.6 % of the pass.
         // Stage by stage -- a scalar test per image, which this loop can afford (its order is pinned; the same test cost the
         // round-2 loop 9 %, profiles/r02_h2s_stalls.txt section 7).
-        const int n_st = (1 + sb.n_models + G - 1) / G;       // stages per mixture tile with a model in them, 1 .. N_STAGES
+        const int n_st = h2q_stages(G, sb.n_models, m2);      // stages per mixture tile with a model in them, 1 .. N_STAGES (a pair: .. 2 N_STAGES)
+        // PAIR: a full pair's last executed image is image 30, in acc[0]; any other last image is the odd last one of a whole stage
+        const bool last_even = PAIR && n_st * G > N_IMG;      // (wave-uniform)
         const int n_stage_total = a.n_mix_tiles * n_st;
         int ld_tile = 0, ld_st = 0;                           // the next stage to load: mixture tile, stage within it
         auto stage_load_next = [&](int slot) {
-            stage_load(slot, stream + (size_t)ld_tile * (N_IMG * IMG_U4) + (size_t)ld_st * STAGE_U4);
+            stage_load(slot, (PAIR && ld_st >= N_STAGES ? stream2 : stream) + (size_t)ld_tile * (N_IMG_T * IMG_U4) + (size_t)ld_st * STAGE_U4);
             if (++ld_st == n_st) {
                 ld_st = 0;
                 ld_tile++;
@@ -900,28 +934,31 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
         acc[0] = zero1;
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[1][r] = -1.0e30f;    // "the image before the first": its epilogue adds 16 zeros to ssum[SB]
+        if constexpr (PAIR) acc[0] = acc[1];                  // (in whichever accumulator the pair's last image lies)
         int S = 0, slot_cur = 0, slot_nxt = 1;                // stage counter of the block and its ring slots
         static_assert(NB == 2 || NB == 3, "ring of two or three stages");
         f32x16 qacc = zero1;
         float e[16] = {0.0f, 0.0f, 0.0f, 0.0f};               // exps on their way from the slot that made them to the slot that adds them up
         for (int t = 0; t < a.n_mix_tiles; t++) {
-            h2p_for<0, N_IMG>([&](auto IMG) {
+            // image IMG with the image before it in acc[PSEL]
+            auto image = [&](auto IMG, auto PSEL) {
                 constexpr int img = decltype(IMG)::value;
                 constexpr int gi = img % G;
+                constexpr bool los = gi == G - 1 || img == N_IMG - 1;      // last image of its stage (a full pair's last stage has three)
                 constexpr int kn = img == 0 ? KQF : KLF;                   // this image's chain
                 constexpr int kn_next = img + 1 == N_IMG ? KQF : KLF;      // fragments of the next one
                 constexpr bool carry = img != 1;                           // image 1 follows Q: nothing to add up
                 constexpr int prev_model = img == 0 ? SB : img - 2;        // sum of the image before (when carry); SB: see ssum
                 if (img / G >= n_st) return;                               // a stage of phantom models only
-                if constexpr (gi == G - 1) {
+                if constexpr (los) {
                     wait_stages(NB > 2 && S + 2 < n_stage_total ? 1 : 0);
                     barrier();
                     if constexpr (DMA_AT == 0)
                         if (S + NB < n_stage_total) stage_load_next(slot_cur);
                 }
-                const unsigned next_at = ring_lane + (unsigned)((gi == G - 1 ? slot_nxt * STAGE_U4 : slot_cur * STAGE_U4 + (gi + 1) * IMG_U4) * 16);
+                const unsigned next_at = ring_lane + (unsigned)((los ? slot_nxt * STAGE_U4 : slot_cur * STAGE_U4 + (gi + 1) * IMG_U4) * 16);
                 f32x16 &cur = img == 0 ? qacc : acc[img & 1];
-                const f32x16 &prev = acc[(img & 1) ^ 1];                   // (image 0 follows image 15: acc[1])
+                const f32x16 &prev = acc[decltype(PSEL)::value];           // (image 0 follows the tile's last executed image)
                 // the wave's own quadratic-half fragments, four at a time (all KQF of them beside fr, bl and three accumulators do
                 // not fit 168 registers: hipcc spilled two bl fragments, and a scratch reload waits with vmcnt(0) -- for the whole
                 // LDS-DMA stream in flight, not only for itself)
@@ -940,10 +977,13 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                 constexpr bool ONE_ASM = kn >= 5;              // (shorter chains: more than 4 exps per slot)
                 static_assert(!CPT || ONE_ASM, "the compact order is written for the one-statement slots");
                 constexpr int sum_model = carry ? prev_model : 0;          // (an operand has to name something)
+                // (PAIR: images SB + 1 .. 2 SB are the second block's models; its last one is only ever a tile's last image: ssum[SB])
+                constexpr bool second = PAIR && carry && img != 0 && img - 2 >= SB;
+                float &sum_ref = second ? ssum2[second ? img - 2 - SB : 0] : ssum[second ? 0 : sum_model];
                 if constexpr (ONE_ASM) {
                     h2p_for<0, kn>([&](auto U) {
                         constexpr int u = decltype(U)::value;
-                        if constexpr (gi == G - 1 && DMA_AT != 0 && u == DMA_AT)
+                        if constexpr (los && DMA_AT != 0 && u == DMA_AT)
                             if (S + NB < n_stage_total) stage_load_next(slot_cur);
                         // stored fragment, frame register, "this step reads the next image's fragment into the register it just used"
                         constexpr int fa = CPT ? H2C_MAP.a_of[u] : u, bi = CPT ? H2C_MAP.b_of[u] : u;
@@ -956,19 +996,19 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                                     p3 = prev[e1 + 3 < 16 ? e1 + 3 : 15];
                         if constexpr (img == 0)
                         {
-                            h2p_slot<u == 0 ? 0 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], ssum[sum_model], e[0], e[1], e[2], e[3], bqt[u % BW],
+                            h2p_slot<u == 0 ? 0 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], sum_ref, e[0], e[1], e[2], e[3], bqt[u % BW],
                                                                                      qacc, next_at, p0, p1, p2, p3);
                             if constexpr (u + BW < KQF) bqt[u % BW] = bq_load(CPT ? H2C_MAP.b_of[u + BW] : u + BW);
                         }
                         else
-                            h2p_slot<u == 0 ? 1 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], ssum[sum_model], e[0], e[1], e[2], e[3], bl[bi], qacc,
+                            h2p_slot<u == 0 ? 1 : 2, rd, NA, NX, younger, fa * 1024>(cur, fr[fa], sum_ref, e[0], e[1], e[2], e[3], bl[bi], qacc,
                                                                                      next_at, p0, p1, p2, p3);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 } else {
                     h2p_for<0, kn>([&](auto U) {
                         constexpr int u = decltype(U)::value;
-                        if constexpr (gi == G - 1 && DMA_AT != 0 && u == DMA_AT)
+                        if constexpr (los && DMA_AT != 0 && u == DMA_AT)
                             if (S + NB < n_stage_total) stage_load_next(slot_cur);
                         // our reads issued after fragment u of this image: the rest of this image's, then the next image's first u
                         constexpr int younger = (kn - 1 - u) + (u < kn_next ? u : kn_next);
@@ -1007,7 +1047,7 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                     } else {
                         asm volatile("s_nop 0");
                         h2p_for<e0, e1>([&](auto R) {
-                            float &sv = ssum[prev_model];
+                            float &sv = sum_ref;
                             const float ev = e[decltype(R)::value - e0];
                             asm volatile("v_add_f32 %0, %0, %1" : "+v"(sv) : "v"(ev));
                         });
@@ -1026,26 +1066,54 @@ void gmm_score_h2p_kernel(const H2sArgs a) {
                     asm volatile("s_nop 1");
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (gi == G - 1) {
+                if constexpr (los) {
                     S++;
                     slot_cur = slot_nxt;
                     slot_nxt = slot_nxt == NB - 1 ? 0 : slot_nxt + 1;
                 }
+            };
+            h2p_for<0, N_IMG>([&](auto IMG) {
+                constexpr int img = decltype(IMG)::value;
+                // image 0 follows the tile's last executed image: unpaired image 15 in acc[1]; PAIR in acc[0] (below)
+                image(IMG, std::integral_constant<int, PAIR && img == 0 ? 0 : (img & 1) ^ 1>{});
             });
+            if constexpr (PAIR) {
+                // The Q image reads the tile's last executed image from acc[0], where a full pair's image 30 lies.  Any other last
+                // image is an odd one: moved over, once per mixture tile of a short pair or a lone block.  (Selecting the
+                // accumulator instead -- two copies of the Q image behind a scalar branch -- made hipcc spill the running sums:
+                // 144-260 bytes of scratch per lane, reloads inside the image loop.)  An asm reader of an MFMA result gets no
+                // hazard handling: s_nop 12 as in front of Q - O, tied to the accumulator so that no read of it moves ahead.
+                if (!last_even) {
+                    f32x16 &from = acc[1];
+                    asm volatile("s_nop 12" : "+v"(from));
+                    h2p_for<0, 16>([&](auto R) {
+                        float x;
+                        const float y = acc[1][decltype(R)::value];
+                        asm volatile("v_mov_b32 %0, %1" : "=v"(x) : "v"(y));
+                        acc[0][decltype(R)::value] = x;
+                    });
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         // the last image's epilogue has no chain to ride on (and its MFMAs were asm: no hazard handling from the compiler)
         asm volatile("s_nop 12");
 #pragma unroll
-        for (int r = 0; r < 16; r++) ssum[SB] += __builtin_amdgcn_exp2f(acc[(N_IMG - 1) & 1][r]);     // (the last image of a stage is an odd one)
-        float fin[SB];
-        const int last_model = n_st * G - 2;                  // image n_st * G - 1
+        for (int r = 0; r < 16; r++) ssum[SB] += __builtin_amdgcn_exp2f(acc[PAIR ? 0 : (N_IMG - 1) & 1][r]);     // (unpaired: the last image of a stage is an odd one)
+        const int last_model = (last_even ? N_IMG : n_st * G) - 2;         // image n_st * G - 1, or a full pair's image 30
+        // each block closes on its own
+        for (int half = 0; half < (PAIR ? n_blk : 1); half++) {
+            const SharedBlock sbh = PAIR ? a.blocks[blk + half] : sb;
+            float fin[SB];
 #pragma unroll
-        for (int si = 0; si < SB; si++) fin[si] = ssum[si] + (si == last_model ? ssum[SB] : 0.0f);
-        {
+            for (int si = 0; si < SB; si++) {
+                const float own = PAIR && half ? ssum2[PAIR ? si : 0] : ssum[si];
+                fin[si] = own + (half * SB + si == last_model ? ssum[SB] : 0.0f);
+            }
             int tids[4], first_col[4], n_seg;
             h2p_unit(a, unit, tids, first_col, n_seg);
-            if (n_seg == 1) h2s_close_block(a, sb, blk, fin, off, valid, has, tids[0], row, lane, hh, safe_ll2);
-            else h2s_close_block_packed(a, sb, blk, fin, off, valid, has, tids, first_col, n_seg, row, lane, hh, safe_ll2);
+            if (n_seg == 1) h2s_close_block(a, sbh, blk + half, fin, off, valid, has, tids[0], row, lane, hh, safe_ll2);
+            else h2s_close_block_packed(a, sbh, blk + half, fin, off, valid, has, tids, first_col, n_seg, row, lane, hh, safe_ll2);
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1276,9 +1344,10 @@ void gmm_score_h2s_online_kernel(const H2sArgs a) {
     }
 }
 
-template <int KQF, int KLF, int COLS, int WAVES, bool PIN = false, bool MS = false, bool CPT = false>
+template <int KQF, int KLF, int COLS, int WAVES, bool PIN = false, bool MS = false, bool CPT = false, bool PAIR = false>
 static int launch_h2s(const H2sLaunch &l) {
     static_assert(!CPT || PIN, "the compact image is the pipelined kernel's");
+    static_assert(!PAIR || CPT, "blocks go in pairs on the compact image only");
     // the main kernel's chain lengths: the compact order runs D = 37 (flat <7,8>) on the <8,8> chains too
     constexpr int MQ = CPT ? H2C_KLF : KQF, ML = CPT ? H2C_KLF : KLF;
     constexpr bool BQ_LDS = h2s_bq_in_lds(KQF, KLF, WAVES);
@@ -1358,7 +1427,7 @@ static int launch_h2s(const H2sLaunch &l) {
             static bool attr_set[MAX_DEVICES] = {};
             if (!attr_set[ctx().device]) {
                 if constexpr (PIN)
-                    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2p_kernel<MQ, ML, CPT>),
+                    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2p_kernel<MQ, ML, CPT, PAIR>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
                 else
                     SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gmm_score_h2s_kernel<KQF, KLF, COLS, WAVES, MS>),
@@ -1367,7 +1436,7 @@ static int launch_h2s(const H2sLaunch &l) {
             }
         }
         if constexpr (PIN)
-            hipLaunchKernelGGL((gmm_score_h2p_kernel<MQ, ML, CPT>), grid, dim3(WAVES * 64), dyn, ctx().stream, a);
+            hipLaunchKernelGGL((gmm_score_h2p_kernel<MQ, ML, CPT, PAIR>), grid, dim3(WAVES * 64), dyn, ctx().stream, a);
         else if constexpr (M_DIRECT)
             hipLaunchKernelGGL((gmm_score_h2m_kernel<KQF, KLF>), grid, dim3(WAVES * 64), 0, ctx().stream, a);
         else
@@ -1394,7 +1463,7 @@ int launch_score_h2_shared(const H2sLaunch &l, int KQF, int KLF) {
 #define SR_H2S_CASE(Q, L)                                       \
     if (KQF == Q && KLF == L) {                                 \
         if constexpr (L == H2C_KLF)                             \
-            if (l.shape == 2 && l.c_params) return launch_h2s<Q, L, 1, 12, true, false, true>(l); \
+            if (l.shape == 2 && l.c_params) return l.pair ? launch_h2s<Q, L, 1, 12, true, false, true, true>(l) : launch_h2s<Q, L, 1, 12, true, false, true>(l); \
         if constexpr (h2p_fits(Q, L))                           \
             if (l.shape == 2) return launch_h2s<Q, L, 1, 12, true>(l); \
         if (l.shape == 3) return launch_h2s<Q, L, 1, 4, false, true>(l); \

@@ -158,7 +158,12 @@ static bool ensure_h2c_layout(SRModelSet &s) {
         return false;
     }
     const PackedH2Compact c = pack_h2_compact(h, s.host.dim);
+    // (one image of padding on the DEVICE only: the paired form's last stage of a block loads -- never executes -- the image behind
+    // the block's last one, score_shapes.hpp: h2q_stage_image)
+    const size_t pad_u16 = (size_t)c.nf * 64 * 8;
+    s.d_h2c_params.ensure(c.params.size() + pad_u16);
     s.d_h2c_params.upload(c.params.data(), c.params.size());
+    SR_HIP(hipMemsetAsync(s.d_h2c_params.p + c.params.size(), 0, pad_u16 * sizeof(uint16_t), ctx().stream));
     s.d_h2c_blocks.upload(c.blocks.data(), c.blocks.size());
     s.d_h2c_qdesc.upload(c.q_desc.data(), c.q_desc.size());
     s.d_h2c_ldesc.upload(c.l_desc.data(), c.l_desc.size());
@@ -287,9 +292,11 @@ static void launch_shared_f16(SRModelSet &set, SRBatch &feat, TileTable &tt, con
         ensure_work_table(tt, opt.h2s_pack_tails != 0);
         a.tiles = tt.d_tiles_work.p;
         a.n_work = tt.n_work;
-        // ... on the compact image where the form applies (score_h2s_shape = 5: on the flat one, for A/B)
+        // ... on the compact image where the form applies (score_h2s_shape = 5: on the flat one, for A/B), two blocks behind one
+        // quadratic-half image (score_h2s_shape = 6: one per block, for A/B)
         compact = opt.h2s_shape != 5 && ensure_h2c_layout(set);
         if (compact) {
+            a.pair = opt.h2s_shape != 6;
             a.c_params = set.d_h2c_params.p;
             a.c_blocks = set.d_h2c_blocks.p;
             a.c_q_desc = set.d_h2c_qdesc.p;
@@ -301,7 +308,7 @@ static void launch_shared_f16(SRModelSet &set, SRBatch &feat, TileTable &tt, con
              "3 products as one contraction; reference-offset log-sum-exp)", h2s_shape == 2 ? "gmm_score_h2p_kernel" : (h2s_shape == 3 && h2s_msplit_direct(h.klf)) ? "gmm_score_h2m_kernel" : "gmm_score_h2s_kernel",
              compact ? set.h2c_nk : h.kqf, compact ? set.h2c_nk : h.klf,
              h2s_shape == 2 ? "waves=12, pipelined in the wave" : h2s_shape == 1 ? "waves=12" : h2s_shape == 3 ? "waves=4 on one tile, models split" : "waves=4",
-             compact ? "/compact" : "", SHARED_SB);
+             compact ? "/compact" : "", a.pair ? 2 * SHARED_SB : SHARED_SB);
     ScopedKernelTimer t(T_SCORE);
     const int n_launches = launch_score_h2_shared(a, h.kqf, h.klf);
     const size_t len = strlen(g_last_kernel);

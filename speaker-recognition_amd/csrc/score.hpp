@@ -111,6 +111,8 @@ struct H2sLaunch {
     const uint16_t *c_params = nullptr;
     const SharedBlock *c_blocks = nullptr;
     const uint16_t *c_q_desc = nullptr, *c_l_desc = nullptr;
+    bool pair = false;      // ... two blocks of a group behind one quadratic-half image (score_shapes.hpp: h2q_*); `c_params` is then
+                            // readable one image past its end
     float band_hi = -__builtin_inff();
 };
 int launch_score_h2_shared(const H2sLaunch &a, int KQF, int KLF);

@@ -99,7 +99,7 @@ ScorePlan plan_score(const SRModelSet &set, int64_t n_rows, int n_utt, const Sco
         // 1200 frames (a third workgroup per CU: a second round) 0.141 against 0.111.
         const int64_t ms_wgs = n32 * (int64_t)set.h2s.blocks.size();
         const bool tiny = ms_wgs <= (int64_t)n_cu * (h2s_msplit_direct(set.h2s.klf) ? 2 : 1);
-        p.h2s_shape = opt.h2s_shape == 5 ? H2S_PIPELINED_SHAPE : opt.h2s_shape ? opt.h2s_shape - 1 : (tiny ? H2S_MSPLIT_SHAPE : wide ? H2S_PIPELINED_SHAPE : 0);
+        p.h2s_shape = (opt.h2s_shape == 5 || opt.h2s_shape == 6) ? H2S_PIPELINED_SHAPE : opt.h2s_shape ? opt.h2s_shape - 1 : (tiny ? H2S_MSPLIT_SHAPE : wide ? H2S_PIPELINED_SHAPE : 0);
         if (p.h2s_shape == H2S_PIPELINED_SHAPE && !h2p_fits(set.h2s.kqf, set.h2s.klf)) p.h2s_shape = H2S_WIDE_SHAPE;
     }
     // the generic split-fp16 engine as ONE wide workgroup per CU (gmm_score_splitp.hip) once the batch fills the chip: the 4-wave

@@ -23,7 +23,8 @@ struct ScoreOptions {
                                // workgroups per CU); 2 = 12 waves (one per CU, one copy of the stream in LDS); 3 = 12 waves with the
                                // image loop software-pipelined inside each wave (gmm_score_h2p_kernel; on the compact image where that
                                // form applies, score_shapes.hpp: h2c_built); 4 = 4 waves on one tile, the block's models split between
-                               // them; 5 = as 3, always on the flat image (A/B, and what 3 runs for the other sets)
+                               // them; 5 = as 3, always on the flat image (A/B, and what 3 runs for the other sets); 6 = as 3, the
+                               // quadratic half once per block of 15 models where 3 forms it once per two blocks (A/B)
     int split_shape = 0;       // workgroup shape of the generic split-fp16 engine: 0 = automatic; 1 = 4 waves (gmm_score_split_kernel);
                                // 16 / 12 / 8 = gmm_score_splitp_kernel with that many waves (one 32-frame tile each, log-sum-exp pipelined
                                // under the next chunk's MFMAs; 16 and 12: one workgroup per CU, 8: two)

@@ -131,6 +131,49 @@ SR_HD constexpr bool h2c_built(int dim, int klf) { return klf == H2C_KLF && h2c_
 SR_HD constexpr int h2c_lds_bytes(int h) { return (2 * 4 * h2c_map(h).nf + 12 * h2c_map(h).nb) * 1024; }
 static_assert(h2c_lds_bytes(H2C_H) <= 160 * 1024 && (4 * h2c_map(H2C_H).nf) % 12 == 0, "the compact ring fits a CU; a stage is a whole number of pieces per wave");
 
+// PAIRS of blocks in the compact pipelined kernel: the quadratic half Q is the same for every model of the set, so a workgroup runs
+// two consecutive blocks of its group behind ONE Q image -- per mixture tile [Q][L_0 .. L_(sb-1)][L'_0 .. L'_(m2-1)], the second
+// block's images taken from ITS stream from image 1 on (its own Q image is never read) -- in stages of g images.  `m1` / `m2` =
+// models of the first / second block; m2 = 0 is a lone block (the odd one at a group's end), which runs as it always did.  A pair
+// needs a full first block (m1 == sb): every block but a set's last one is.
+constexpr int H2Q_SB = 15, H2Q_G = 4;                        // SHARED_SB and the pipelined kernel's images per stage
+SR_HD constexpr bool h2q_pairs(int sb, int m1, int m2) { return m2 > 0 && m1 == sb; }
+// stages per mixture tile that hold a model (stages of phantom models only are skipped, counted over the pair)
+SR_HD constexpr int h2q_stages(int g, int m1, int m2) { return (1 + m1 + m2 + g - 1) / g; }
+// images executed per mixture tile: whole stages, but never the slot behind a full pair's last image (1 + 2 sb is one short of a stage)
+SR_HD constexpr int h2q_images(int sb, int g, int m1, int m2) {
+    return h2q_stages(g, m1, m2) * g < 1 + 2 * sb ? h2q_stages(g, m1, m2) * g : 1 + 2 * sb;
+}
+// the last executed image of a mixture tile (its epilogue rides on the next tile's Q image) and the accumulator it lies in
+SR_HD constexpr int h2q_last_image(int sb, int g, int m1, int m2) { return h2q_images(sb, g, m1, m2) - 1; }
+SR_HD constexpr int h2q_last_parity(int sb, int g, int m1, int m2) { return h2q_last_image(sb, g, m1, m2) & 1; }
+// ... as a model of the pair: 0 .. sb - 1 the first block's, sb .. 2 sb - 1 the second's (image i holds model i - 1)
+SR_HD constexpr int h2q_last_model(int sb, int g, int m1, int m2) { return h2q_last_image(sb, g, m1, m2) - 1; }
+// where stage s of a pair comes from: which block's stream (0 / 1), and the first of its g images within that block's mixture tile.
+// The second block's last stage ends one image behind its tile -- image 0 of the next tile, or, at the last tile of a set's last
+// block, one image past the end: the DEVICE buffer carries one image of padding (the image is loaded, never executed).
+SR_HD constexpr int h2q_stage_block(int sb, int g, int s) { return s * g < 1 + sb ? 0 : 1; }
+SR_HD constexpr int h2q_stage_image(int sb, int g, int s) { return s * g < 1 + sb ? s * g : s * g - sb; }
+static_assert((1 + H2Q_SB) % H2Q_G == 0 && h2q_stages(H2Q_G, H2Q_SB, H2Q_SB) == 8 && h2q_images(H2Q_SB, H2Q_G, H2Q_SB, H2Q_SB) == 31 &&
+              h2q_last_parity(H2Q_SB, H2Q_G, H2Q_SB, H2Q_SB) == 0 && h2q_last_parity(H2Q_SB, H2Q_G, H2Q_SB, 6) == 1 &&
+              h2q_stage_image(H2Q_SB, H2Q_G, 4) == 1 && h2q_stage_image(H2Q_SB, H2Q_G, 7) == 13, "a full pair: 31 images, the last an even one");
+// images executed per mixture tile over a group of `n_models` models in blocks of sb, paired (or block by block)
+SR_HD constexpr int h2q_group_images(int sb, int g, int n_models, bool paired) {
+    int n = 0, left = n_models;
+    while (left > 0) {
+        const int m1 = left < sb ? left : sb;
+        left -= m1;
+        int m2 = 0;
+        if (paired && left > 0 && m1 == sb) {
+            m2 = left < sb ? left : sb;
+            left -= m2;
+        }
+        n += h2q_images(sb, g, m1, m2);
+    }
+    return n;
+}
+static_assert(h2q_group_images(H2Q_SB, H2Q_G, 201, false) == 216 && h2q_group_images(H2Q_SB, H2Q_G, 201, true) == 210, "BASELINE configs[2]: 201 models");
+
 // workgroups resident per CU, and 32-frame tiles per workgroup, of shape `shape` (0: 4 waves; 1: 12 waves; 2: 12 waves, pipelined;
 // 3: 4 waves on one tile, the block's models split between them)
 constexpr int h2s_resident_per_cu(int kqf, int klf, int shape) { return (shape == 0 || shape == 3) ? h2s_waves_per_eu(kqf, klf, 1, 4, shape == 3) : 1; }
