@@ -12,6 +12,8 @@
 // N_k, sum g (x-mu_old), sum g (x-mu_old)^2 (centred on the current mean, so the variance
 // update does not cancel).  The M-step is O(K*D) and runs on the host in float64 with the
 // reference's formulas.
+#include "em_mstep.hpp"
+#include "em_plan.hpp"
 #include "score.hpp"
 #include "split_prologue.hpp"
 #include "split_schemes.hpp"
@@ -26,10 +28,10 @@
 #include <cstring>
 #include <future>
 #include <memory>
-#include <system_error>
-#include <thread>
 
 namespace sr {
+
+static_assert(EM_KB == KB && EM_CB == CB && EM_MAX_REG_DIM == MAX_REG_DIM, "em_shapes.hpp restates gmm_model.hpp's record shapes");
 
 constexpr float EM_MINLOG = -708.396418532264f;   // fastexp.cc:93,105: below this the reference's
                                                   // linear-domain sum is 0 -> MIN_PROB_SUM path
@@ -137,7 +139,6 @@ void em_stats_kernel(const float *__restrict__ X, int64_t n_frames, int dim,
 // its row from global memory, CB x KB running distances in registers across the slices -> 32 responsibilities per frame into LDS.
 // Phase B (thread = dimension d, 8 mixtures at a time): sweeps the tile's frames -- x[i][d] straight from global memory,
 // consecutive threads consecutive addresses -- in frame order, as em_stats_kernel does.  Same slabs, same reduction.
-constexpr int EMW_JB = 8;
 __global__ __launch_bounds__(256, 2)
 void em_stats_wide_kernel(const float *__restrict__ X, int64_t n_frames, int dim, int dp,
                           const float4 *__restrict__ params, const float *__restrict__ center, int n_records,
@@ -280,14 +281,7 @@ void em_stats_wide_kernel(const float *__restrict__ X, int64_t n_frames, int dim
 // phase down by about as much as it gains: A + B (11 k + 13 k cycles per 128 frames x 128 mixtures) is what both forms measure,
 // 23.6 k here, 29.8 k there.  What shortens this kernel is less arithmetic in phase A, not a different interleaving.
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-constexpr int EMM_WAVES = 4, EMM_MB = 16, EMM_WG_MIX = EMM_WAVES * EMM_MB;
-constexpr int EMM_F = 2;                       // frames per lane in the responsibility phase: a parameter read serves both
-constexpr int EMM_FT = 64 * EMM_F;             // frames per tile
-// Row strides = 2 mod 32.  The operand reads are ds_read_b32: two 32-lane groups, bank = dword address mod 32; a group holds
-// (mixture or column j = 0..15) x (frame fl = 0..1 or 2..3) at j * stride + fl + const, i.e. banks 2 j + fl: all different.
-// (Stride 4 mod 64 -- the ds_read_b64 / b128 bank map -- made j and j + 8 collide: SQ_LDS_BANK_CONFLICT 55 % of the LDS cycles.)
-constexpr int EMM_XS = EMM_FT + 2, EMM_GS = EMM_FT + 2;
-__host__ __device__ constexpr int emm_ncb(int dp) { return 2 * (dp / 16) + (2 * (dp % 16) + 1 + 15) / 16; }
+// (the shapes -- EMM_*, emm_ncb, the LDS of a workgroup: em_shapes.hpp)
 
 template <int DP>
 __global__ __launch_bounds__(EMM_WAVES * 64, 2)
@@ -446,12 +440,6 @@ void em_stats_mfma_kernel(const float *__restrict__ X, int64_t n_frames, int dim
             slab[(size_t)(wave * EMM_MB + fl + 4 * r) * (NCB * 16) + 16 * cb + j] = acc[cb][r];
 }
 
-// dynamic LDS of em_stats_mfma_kernel<DP>: 16 parameter records, one transposed tile of rows, four waves' responsibilities
-static size_t emm_lds_bytes(int DP) {
-    return (size_t)(EMM_WG_MIX / KB) * (2 * DP + 1) * sizeof(float4) + (size_t)DP * EMM_XS * sizeof(float) +
-           (size_t)EMM_WAVES * EMM_MB * EMM_GS * sizeof(float);
-}
-
 // ---- round 4: the responsibilities on the 16-bit matrix cores -------------------------------------------------------------------
 // em_stats_mfma_kernel's phase A is 2 D fused multiply-adds per (frame, mixture) on the vector ALU, and v_mfma_f64 shares that
 // ALU's rate (above): 11 k of the tile's 24 k cycles.  Here the log2 densities come from the scoring engine's own contraction
@@ -465,10 +453,7 @@ static size_t emm_lds_bytes(int DP) {
 //   phase B : as em_stats_mfma_kernel -- wave w owns mixtures 16 w .. 16 w + 15 over all 128 frames, fp64 MFMAs from fp32-exact
 //             operands into accumulators that live in registers until the chunk is done.
 // Same slabs, same reduction; the statistics themselves are float64 as before.
-constexpr int EMS_WAVES = 8, EMS_WG_MIX = EMS_WAVES * EMM_MB;       // 128 mixtures = 4 tiles of the split layout
-__host__ __device__ constexpr int ems_lds_bytes(int ks) {
-    return 4 * ks * 3 * 64 * 16 + 8 * ks * EMM_XS * 4 + EMS_WG_MIX * EMM_GS * 4;
-}
+// (EMS_WAVES = 8 waves, EMS_WG_MIX = 128 mixtures = 4 tiles of the split layout, ems_lds_bytes: em_shapes.hpp)
 
 template <int DP, int KS>
 __global__ __launch_bounds__(EMS_WAVES * 64, 2)
@@ -663,97 +648,10 @@ void em_reduce_kernel(const float *__restrict__ slabs, int n_slabs, int n_elem,
     out[e] = acc;
 }
 
-template <int DP>
-static void launch_stats(const float *X, int64_t n, int dim, const float4 *params, const float *center, int n_records,
-                         const float *mean_f32, const float *frame_ll, float *slabs, int n_tiles,
-                         int grid) {
-    const int gy = std::max(1, std::min(n_records, (4 * ctx().n_cu + grid - 1) / grid));
-    hipLaunchKernelGGL((em_stats_kernel<DP>), dim3(grid, gy), dim3(256), 0, ctx().stream, X, n, dim,
-                       params, center, n_records, mean_f32, frame_ll, slabs, n_tiles);
-}
-
-static void dispatch_stats(int DP, const float *X, int64_t n, int dim, const float4 *params, const float *center,
-                           int n_records, const float *mean_f32, const float *frame_ll,
-                           float *slabs, int n_tiles, int grid) {
-#define SR_CASE(V) case V: launch_stats<V>(X, n, dim, params, center, n_records, mean_f32, frame_ll, slabs, n_tiles, grid); break;
-    switch (DP) {
-        SR_CASE(8) SR_CASE(13) SR_CASE(16) SR_CASE(24) SR_CASE(26) SR_CASE(32) SR_CASE(34)
-        SR_CASE(39) SR_CASE(40) SR_CASE(48) SR_CASE(56) SR_CASE(64) SR_CASE(80) SR_CASE(96)
-        default: fail("no EM kernel for padded dim %d", DP);
-    }
-#undef SR_CASE
-}
-
-template <int DP>
-static void launch_stats_mfma(const float *X, int64_t n, int dim, const float4 *params, const float *center, int n_records,
-                              const float *frame_ll, double *slabs, int n_tiles64, int n_ranges, int n_chunks, int k_pad, double *out) {
-    static bool attr_set[MAX_DEVICES] = {};
-    if (!attr_set[ctx().device]) {
-        SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&em_stats_mfma_kernel<DP>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)emm_lds_bytes(DP)));
-        attr_set[ctx().device] = true;
-    }
-    hipLaunchKernelGGL((em_stats_mfma_kernel<DP>), dim3(n_ranges, n_chunks), dim3(EMM_WAVES * 64), emm_lds_bytes(DP), ctx().stream, X,
-                       n, dim, params, center, n_records, frame_ll, slabs, n_tiles64);
-    const int n_elem = k_pad * (2 * DP + 1);
-    hipLaunchKernelGGL((em_reduce64_kernel<DP>), dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0, ctx().stream, slabs, n_chunks,
-                       n_ranges, k_pad, out, EMM_WG_MIX);
-}
-
-template <int DP, int KS>
-static void launch_stats_split(const float *X, int64_t n, int dim, const uint4 *frags, int n_mix_tiles, const float *center,
-                               const float *frame_ll, double *slabs, int n_tiles128, int n_ranges, int n_chunks, int k_pad, double *out) {
-    static_assert(8 * KS >= DP, "the transposed tile has a row per slot feature");
-    static bool attr_set[MAX_DEVICES] = {};
-    if (!attr_set[ctx().device]) {
-        SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&em_stats_split_kernel<DP, KS>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, ems_lds_bytes(KS)));
-        attr_set[ctx().device] = true;
-    }
-    hipLaunchKernelGGL((em_stats_split_kernel<DP, KS>), dim3(n_ranges, n_chunks), dim3(EMS_WAVES * 64), ems_lds_bytes(KS), ctx().stream, X,
-                       n, dim, frags, n_mix_tiles, center, frame_ll, slabs, n_tiles128);
-    const int n_elem = k_pad * (2 * DP + 1);
-    hipLaunchKernelGGL((em_reduce64_kernel<DP>), dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0, ctx().stream, slabs, n_chunks,
-                       n_ranges, k_pad, out, EMS_WG_MIX);
-}
-
-// instantiated for the (padded dim, contraction steps) pairs whose LDS fits a CU (DP = 40 with dim = 40 has KS = 6: 164 KB)
-static bool stats_split_available(int DP, int dim) {
-    const int ks = (dim + 8) / 8;
-    return DP <= 40 && 8 * ks >= DP && ems_lds_bytes(ks) <= 160 * 1024;
-}
-static void dispatch_stats_split(int DP, int KS, const float *X, int64_t n, int dim, const uint4 *frags, int n_mix_tiles, const float *center,
-                                 const float *frame_ll, double *slabs, int n_tiles128, int n_ranges, int n_chunks, int k_pad, double *out) {
-#define SR_CASE(V, W) if (DP == V && KS == W) return launch_stats_split<V, W>(X, n, dim, frags, n_mix_tiles, center, frame_ll, slabs, n_tiles128, n_ranges, n_chunks, k_pad, out);
-    SR_CASE(8, 1) SR_CASE(8, 2) SR_CASE(13, 2) SR_CASE(16, 2) SR_CASE(16, 3) SR_CASE(24, 3) SR_CASE(24, 4) SR_CASE(26, 4)
-    SR_CASE(32, 4) SR_CASE(32, 5) SR_CASE(34, 5) SR_CASE(39, 5)         // (DP = 40 is dim = 40: six steps, 164 KB of LDS -- not available)
-#undef SR_CASE
-    fail("no split-responsibility EM kernel for padded dim %d with %d contraction steps", DP, KS);
-}
-
-// the fp64 matrix-core form is instantiated for padded dims <= 40 (its LDS -- 16 parameter records, a transposed 128-frame
-// tile, the responsibilities: 75 KiB at DP = 39 -- lets two workgroups share a CU); wider rows keep em_stats_kernel
-static bool stats_mfma_available(int DP) { return DP <= 40; }
-static size_t stats_mfma_slab_doubles(int DP, int n_ranges, int n_chunks, int wg_mix = EMM_WG_MIX) {
-    return (size_t)n_chunks * n_ranges * wg_mix * (size_t)(emm_ncb(DP) * 16);
-}
-static void dispatch_stats_mfma(int DP, const float *X, int64_t n, int dim, const float4 *params, const float *center, int n_records,
-                                const float *frame_ll, double *slabs, int n_tiles64, int n_ranges, int n_chunks, int k_pad, double *out) {
-#define SR_CASE(V) case V: launch_stats_mfma<V>(X, n, dim, params, center, n_records, frame_ll, slabs, n_tiles64, n_ranges, n_chunks, k_pad, out); break;
-    switch (DP) {
-        SR_CASE(8) SR_CASE(13) SR_CASE(16) SR_CASE(24) SR_CASE(26) SR_CASE(32) SR_CASE(34) SR_CASE(39) SR_CASE(40)
-        default: fail("no fp64 matrix-core EM kernel for padded dim %d", DP);
-    }
-#undef SR_CASE
-}
-
 // initialisation: kmeans_init.hip (the reference's own draws, decision for decision)
 void init_gmm_like_reference(GMM &g, const float *X, long n, int dim, const Parameter &param, long seed);
-// em_small.hip
-bool em_small_eligible(int K, int dim, long n, const Parameter &param);
+// em_small.hip, em_f64.hip: true = done; false = handed back (gmm untouched)
 bool train_em_small(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
-// em_f64.hip
-bool em_f64_eligible(int K, int dim, long n, const Parameter &param);
 bool train_em_f64(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
 void burn_reference_rand(int count);
 
@@ -779,7 +677,7 @@ static void pack_em_set(SRModelSet &set, const GMM &gmm) {
     }
 }
 
-// A fit's packed sets are RECYCLED (train_em): a re-packed set keeps its device buffers, so its layouts go up into the
+// A fit's packed sets are RECYCLED (EmSetPool): a re-packed set keeps its device buffers, so its layouts go up into the
 // allocations of the iteration before last -- upload_model_set + ensure_bx3_layout on a fresh SRModelSet were
 // six hipMalloc, two waits and, when the set of the previous iteration died, six hipFree (each one a device synchronisation) per
 // iteration: most of a 16-mixture speaker model's 0.16 ms per iteration.
@@ -805,11 +703,53 @@ static void upload_em_set(SRModelSet &s) {
     s.device = ctx().device;
 }
 
+// The fit's own packed sets: at most two are alive at a time -- the one an E-step reads and the one the total log-likelihood of
+// every second iteration is taken under (`carried`), which the next E-step then reads.  The UBM handle's set, which serves the
+// first E-step of every speaker enrolled from it, is not this fit's to recycle: it never comes in here.
+struct EmSetPool {
+    std::vector<std::shared_ptr<SRModelSet>> spare;
+    std::shared_ptr<SRModelSet> carried;
+    std::shared_ptr<SRModelSet> take() {
+        if (spare.empty()) return std::make_shared<SRModelSet>();
+        std::shared_ptr<SRModelSet> p = std::move(spare.back());
+        spare.pop_back();
+        return p;
+    }
+    void give(std::shared_ptr<SRModelSet> p) { spare.push_back(std::move(p)); }
+};
+
+// phase times of every iteration on stdout (verbosity >= 2): pack | upload | denominators | statistics | M-step
+struct EmPhaseTrace {
+    const bool on;
+    double t[5] = {};
+    int n_marks = 0;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void begin() { n_marks = 0; mark(false); }
+    void mark(bool device_phase) {          // a device phase ends when the stream has drained
+        if (!on) return;
+        if (device_phase) sync_stream();
+        t[n_marks++] = now();
+    }
+    void print(int it) const {
+        if (on)
+            printf("iter %d: pack %.2f ms, upload %.2f ms, posteriors' denominators %.2f ms, statistics %.2f ms, M-step %.2f ms\n", it,
+                   (t[1] - t[0]) * 1e3, (t[2] - t[1]) * 1e3, (t[3] - t[2]) * 1e3, (t[4] - t[3]) * 1e3, (now() - t[4]) * 1e3);
+    }
+};
+
 struct EmWorkspace {
     DevBuf<float> slabs, mean_f32;
     DevBuf<double> stats, slabs64;
     PinnedBuf<double> h_stats;        // where an iteration's sums land on the host
+    void ensure(const EmStatsPlan &p) {
+        stats.ensure(p.n_elem);
+        h_stats.ensure(p.n_elem);
+        if (p.slab_f64) slabs64.ensure(p.slab_elems);
+        else slabs.ensure(p.slab_elems);
+    }
 };
+static EmWorkspace &ews() { return per_device<EmWorkspace>(); }
+
 static int &em_stats_engine_option() {
     // 0 = automatic (a speaker-sized fit whole in one launch, em_small.hip; short data through em_f64.hip; else fp64 matrix cores where instantiated, responsibilities
     // on the 16-bit ones where the model allows), 1 = the vector-ALU form always, 2 = fp64 matrix cores with the responsibilities on the
@@ -832,11 +772,102 @@ static int &reference_side_effects_option() {
 }
 void set_reference_side_effects(int v) { reference_side_effects_option() = v; }
 int reference_side_effects() { return reference_side_effects_option(); }
-static EmWorkspace &ews() { return per_device<EmWorkspace>(); }
 
-int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param,
-             long seed) {
-    ensure_device();
+static void dump_intermediate_model(const GMM &gmm) {      // gmm.cc:624-630
+    const char *dump_file = "gmm-training-intermediate-dump.model";
+    printf("dumping model to %s ...\n", dump_file);
+    const std::string text = gmm_format_text(gmm);
+    if (FILE *f = fopen(dump_file, "w")) {
+        fwrite(text.data(), 1, text.size(), f);
+        fclose(f);
+    }
+    printf("model dumped to %s ...\n", dump_file);
+}
+
+// ---- the statistics launch of an iteration, as planned (em_plan.cpp) ----
+// (the matrix-core forms take more dynamic LDS than a launch gets unasked: once per instantiation and device)
+template <class Kernel>
+static void allow_lds(Kernel *kernel, bool (&done)[MAX_DEVICES], size_t bytes) {
+    if (done[ctx().device]) return;
+    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[ctx().device] = true;
+}
+
+template <int DP>
+static void launch_stats_mfma(const EmStatsPlan &p, const SRModelSet &set, const SRBatch &feat, const float *frame_ll, double *slabs) {
+    static bool attr_set[MAX_DEVICES] = {};
+    allow_lds(&em_stats_mfma_kernel<DP>, attr_set, p.lds_bytes);
+    hipLaunchKernelGGL((em_stats_mfma_kernel<DP>), dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds_bytes, ctx().stream, feat.data.p, feat.n_rows,
+                       feat.dim, reinterpret_cast<const float4 *>(set.d_params.p), set.d_center0.p, p.n_records, frame_ll, slabs, p.n_tiles);
+}
+
+template <int DP, int KS>
+static void launch_stats_split(const EmStatsPlan &p, const SRModelSet &set, const SRBatch &feat, const float *frame_ll, double *slabs) {
+    static bool attr_set[MAX_DEVICES] = {};
+    allow_lds(&em_stats_split_kernel<DP, KS>, attr_set, p.lds_bytes);
+    hipLaunchKernelGGL((em_stats_split_kernel<DP, KS>), dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds_bytes, ctx().stream, feat.data.p, feat.n_rows,
+                       feat.dim, reinterpret_cast<const uint4 *>(set.d_bx3_params.p), (int)set.bx3.chunks.size(), set.d_bx3_center.p, frame_ll,
+                       slabs, p.n_tiles);
+}
+
+template <int DP>
+static void launch_reduce64(const EmStatsPlan &p, const double *slabs, double *out) {
+    hipLaunchKernelGGL((em_reduce64_kernel<DP>), dim3((unsigned)p.reduce_grid), dim3(256), 0, ctx().stream, slabs, p.grid_y, p.grid_x, p.k_pad,
+                       out, p.wg_mix);
+}
+
+// One iteration's sums of `gmm`, packed as `set`, over the resident frames -> w.stats [k_pad][2 dp + 1].  A missing kernel is an error.
+static void launch_em_stats(const EmStatsPlan &p, SRModelSet &set, const SRBatch &feat, const float *frame_ll, const GMM &gmm, EmWorkspace &w) {
+    const int DP = p.dp;
+    if (p.slab_f64) {
+        // sums about the origin on the fp64 matrix cores; the host re-centres them (recentre_origin_sums)
+        if (p.engine == 3) ensure_bx3_layout(set);
+        ScopedKernelTimer t(T_ESTEP);
+        if (p.engine == 3) {
+#define SR_CASE(V, W) if (DP == V && p.ks == W) launch_stats_split<V, W>(p, set, feat, frame_ll, w.slabs64.p);
+            SR_EM_SPLIT_SHAPES(SR_CASE)
+#undef SR_CASE
+        } else {
+#define SR_CASE(V) if (DP == V) launch_stats_mfma<V>(p, set, feat, frame_ll, w.slabs64.p);
+            SR_EM_MFMA_DPS(SR_CASE)
+#undef SR_CASE
+        }
+#define SR_CASE(V) if (DP == V) launch_reduce64<V>(p, w.slabs64.p, w.stats.p);
+        SR_EM_MFMA_DPS(SR_CASE)
+#undef SR_CASE
+    } else {
+        if (p.engine != 1) fail("no EM kernel for padded dim %d", DP);
+        const int K = gmm.nr_mixtures, dim = gmm.dim;
+        std::vector<float> mean_f32((size_t)p.k_pad * DP, 0.f);
+        for (int k = 0; k < K; k++)
+            for (int d = 0; d < dim; d++) mean_f32[(size_t)k * DP + d] = (float)gmm.mean[(size_t)k * dim + d];
+        w.mean_f32.upload(mean_f32.data(), mean_f32.size());
+        SR_HIP(hipMemsetAsync(w.slabs.p, 0, p.slab_elems * sizeof(float), ctx().stream));
+        {
+            ScopedKernelTimer t(T_ESTEP);
+            const dim3 grid(p.grid_x, p.grid_y);
+            const float4 *params = reinterpret_cast<const float4 *>(set.d_params.p);
+            if (p.wide) {
+                hipLaunchKernelGGL(em_stats_wide_kernel, grid, dim3(p.block), 0, ctx().stream, feat.data.p, feat.n_rows, feat.dim, DP, params,
+                                   set.d_center0.p, p.n_records, w.mean_f32.p, frame_ll, w.slabs.p, p.n_tiles);
+            } else {
+#define SR_CASE(V)                                                                                                                     \
+    if (DP == V)                                                                                                                       \
+        hipLaunchKernelGGL((em_stats_kernel<V>), grid, dim3(p.block), 0, ctx().stream, feat.data.p, feat.n_rows, feat.dim, params,    \
+                           set.d_center0.p, p.n_records, w.mean_f32.p, frame_ll, w.slabs.p, p.n_tiles);
+                SR_EM_VECTOR_DPS(SR_CASE)
+#undef SR_CASE
+            }
+        }
+        SR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(em_reduce_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, ctx().stream, w.slabs.p, p.grid_x, (int)p.n_elem,
+                           w.stats.p);
+    }
+    SR_HIP(hipGetLastError());
+}
+
+// validation and the start: MAP from the UBM's parameters, a warm start from the handle's own, else the reference's initialisation
+static void start_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param, long seed) {
     if (n <= 0) fail("X.size() == 0");                       // gmm.cc:582-586
     if (dim <= 0) fail("bad dimension %d", dim);
     if (param.verbosity >= 1 && !reference_side_effects_option())       // (with the reference's own block on, this summary would be extra)
@@ -860,6 +891,24 @@ int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Pa
         if (n < 2) fail("need at least 2 frames to initialise the variances");
         init_gmm_like_reference(gmm, X, n, dim, param, seed);
     }
+}
+
+// Mixtures without fp32 support (rare: more mixtures than the data supports) get their three sums again on the host, in float64
+// (em_mstep.hpp): the reference's N_k is then tiny but not 0, and the mean jumps to the frames' weighted mean (gmm.cc:396-412)
+static void redo_unsupported(double *stats, int DP, const EmModelRef &model, const float *X, long n, const float *d_frame_ll) {
+    const std::vector<int> weak = weak_mixtures(stats, DP, model.K);
+    if (weak.empty()) return;
+    std::vector<float> ll((size_t)n);
+    SR_HIP(hipMemcpyAsync(ll.data(), d_frame_ll, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx().stream));
+    sync_stream();
+    redo_weak_mixtures(stats, DP, model, weak, X, n, ll.data());
+}
+
+// GMMTrainerBaseline::train (gmm.cc:581-653) / GMMUBMTrainerBaseline (gmmubm.cc:29-81), step for step
+int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param,
+             long seed) {
+    ensure_device();
+    start_em(gmm, ubm, X, n, dim, param, seed);
     const int K = gmm.nr_mixtures;
     const double relevance = 16.0;                           // gmm.hh:118-120
     const double min_sigma = std::sqrt(param.min_covar);
@@ -873,18 +922,16 @@ int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Pa
     feat.offsets = {0, (int64_t)n};
     feat.data.upload(X, (size_t)n * dim);
     feat.d_offsets.upload(feat.offsets.data(), feat.offsets.size());
-    // a speaker-sized fit: every iteration, the stop rule included, in ONE launch (em_small.hip; last_em_stats_engine() = 4).  Not with
-    // the reference's side effects on (a model file after every second iteration) nor with the per-phase trace (verbosity >= 2).
-    if (em_stats_engine_option() == 0 && !reference_side_effects_option() && em_small_eligible(K, dim, n, param)) {
-        int iterations = 0;
+    // the whole fit in one launch (last_em_stats_engine() = 4) or float64 iterations on the device (= 5) where the shape allows;
+    // what either hands back goes on below
+    int iterations = 0;
+    const int route = em_route(K, dim, n, param, em_stats_engine_option(), reference_side_effects_option() != 0, ctx().n_cu);
+    if (route == EM_ROUTE_WHOLE_FIT) {
         if (train_em_small(gmm, ubm, feat.data.p, n, dim, param, relevance, &iterations)) {
             g_last_stats_engine.store(4);
             return iterations;
         }
-    } else if (em_stats_engine_option() == 0 && !reference_side_effects_option() && em_f64_eligible(K, dim, n, param)) {
-        // short data, a model of any size (a speaker's MAP enrolment from a large UBM): float64 iterations on the device, nothing
-        // packed, nothing redone on the host (em_f64.hip; last_em_stats_engine() = 5)
-        int iterations = 0;
+    } else if (route == EM_ROUTE_F64) {
         if (train_em_f64(gmm, ubm, feat.data.p, n, dim, param, relevance, &iterations)) {
             g_last_stats_engine.store(5);
             return iterations;
@@ -892,259 +939,63 @@ int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Pa
     }
     sync_stream();
 
-    const int n_tiles = (int)((n + 255) / 256);
-    // (wide rows: a slab is K x (2 D + 1) floats per workgroup column -- one per CU, the records cut along gridDim.y instead)
-    const int grid = std::min(n_tiles, ctx().n_cu * (dim > MAX_REG_DIM ? 1 : 4));
-    auto &w = ews();
-
+    EmWorkspace &w = ews();
+    EmSetPool pool;
+    EmPhaseTrace trace{param.verbosity >= 2};
+    const EmModelRef model = {K, dim, gmm.weights.data(), gmm.mean.data(), gmm.sigma.data()};
     double last_ll = -std::numeric_limits<double>::max();
     int it = 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const bool trace = param.verbosity >= 2;                 // phase times of every iteration on stdout
-    std::shared_ptr<SRModelSet> carried;
-    // the fit's own packed sets, recycled (upload_em_set): at most two are alive at a time -- the one an E-step reads and the one the
-    // total log-likelihood of every second iteration is taken under, which the next E-step then reads
-    std::vector<std::shared_ptr<SRModelSet>> spare;
-    auto take_set = [&]() {
-        if (spare.empty()) return std::make_shared<SRModelSet>();
-        std::shared_ptr<SRModelSet> p = std::move(spare.back());
-        spare.pop_back();
-        return p;
-    };
     for (; it < param.nr_iteration; it++) {
-        // ---- E-step ----
-        const double t0 = now();
-        // (the model as the previous iteration left it is already packed and resident when that iteration computed its total
-        // log-likelihood: every second one, gmm.cc:622-623)
-        std::shared_ptr<SRModelSet> set_owner = std::move(carried);
-        carried.reset();
-        bool fresh = !set_owner;
-        bool own = true;                   // (the UBM handle's set is not this fit's to recycle)
-        if (fresh && ubm && it == 0) {
-            // MAP: the first E-step runs on the UBM's own parameters (gmm_replace_with, gmmubm.cc:29-38), the same for every
-            // speaker enrolled from it -- its handle's packed set serves them all (K = 2048: 1.5 ms of packing per speaker)
-            set_owner = single_model_set(ubm);
-            fresh = false;
-            own = false;
-        }
+        // ---- E-step: the model as a packed set.  The previous iteration left it packed and resident when it computed its total
+        // log-likelihood (every second one); MAP's first runs on the UBM's own parameters (gmm_replace_with, gmmubm.cc:29-38),
+        // the same for every speaker enrolled from it -- its handle's set serves them all (K = 2048: 1.5 ms of packing per speaker)
+        trace.begin();
+        std::shared_ptr<SRModelSet> set_owner = std::move(pool.carried);
+        pool.carried.reset();
+        const bool ubm_set = !set_owner && ubm && it == 0;
+        const bool fresh = !set_owner && !ubm_set;
+        if (ubm_set) set_owner = single_model_set(ubm);
         if (fresh) {
-            set_owner = take_set();
+            set_owner = pool.take();
             pack_em_set(*set_owner, gmm);
         }
         SRModelSet &set = *set_owner;
-        const double t1 = now();
+        trace.mark(false);
         if (fresh) upload_em_set(set);
-        if (trace) sync_stream();
-        const double t2 = now();
-        const int DP = set.host.dp;
-        const int n_records = (K + KB - 1) / KB;
-        const int K_pad = n_records * KB;
-        const int REC = 2 * DP + 1;
+        trace.mark(true);
+        // the posteriors' denominators, then the three sums per mixture on the engine the plan names
         const ScoreResult sres = score_device(set, feat, true, SCORE_PRECISE);
-        if (trace) sync_stream();
-        const double t3 = now();
-        const size_t n_elem = (size_t)K_pad * REC;
-        w.stats.ensure(n_elem);
-        const int stats_engine = em_stats_engine_option();
-        const bool use_mfma = stats_mfma_available(DP) && stats_engine != 1;
-        // round 4: responsibilities on the 16-bit matrix cores when the model is inside the split-bf16 layout's range -- the
-        // engine score_device has just taken for the denominators (em_stats_engine = 2 keeps them on the vector ALU)
-        const bool use_split = use_mfma && (stats_engine == 0 || stats_engine == 3) && split_bf16_in_range(set) && stats_split_available(DP, dim);
-        g_last_stats_engine.store(use_split ? 3 : use_mfma ? 2 : 1);
-        if (use_split) {
-            ensure_bx3_layout(set);
-            const int n_mix_tiles = (int)set.bx3.chunks.size();
-            const int n_ranges = (n_mix_tiles + 3) / 4;
-            const int n_tiles128 = (int)((n + EMM_FT - 1) / EMM_FT);
-            const int n_chunks = std::max(1, std::min(n_tiles128, (4 * ctx().n_cu + n_ranges - 1) / n_ranges));
-            w.slabs64.ensure(stats_mfma_slab_doubles(DP, n_ranges, n_chunks, EMS_WG_MIX));
-            ScopedKernelTimer t(T_ESTEP);
-            dispatch_stats_split(DP, set.bx3.ks, feat.data.p, n, dim, reinterpret_cast<const uint4 *>(set.d_bx3_params.p), n_mix_tiles,
-                                 set.d_bx3_center.p, sres.d_frame_ll, w.slabs64.p, n_tiles128, n_ranges, n_chunks, K_pad, w.stats.p);
-        } else if (use_mfma) {
-            // sums about the origin on the fp64 matrix cores (em_stats_mfma_kernel); re-centred below
-            const int n_ranges = (n_records + EMM_WG_MIX / KB - 1) / (EMM_WG_MIX / KB);
-            const int n_tiles64 = (int)((n + EMM_FT - 1) / EMM_FT);
-            const int n_chunks = std::max(1, std::min(n_tiles64, (4 * ctx().n_cu + n_ranges - 1) / n_ranges));
-            w.slabs64.ensure(stats_mfma_slab_doubles(DP, n_ranges, n_chunks));
-            ScopedKernelTimer t(T_ESTEP);
-            dispatch_stats_mfma(DP, feat.data.p, n, dim, reinterpret_cast<const float4 *>(set.d_params.p), set.d_center0.p, n_records,
-                                sres.d_frame_ll, w.slabs64.p, n_tiles64, n_ranges, n_chunks, K_pad, w.stats.p);
-        } else {
-            std::vector<float> mean_f32((size_t)K_pad * DP, 0.f);
-            for (int k = 0; k < K; k++)
-                for (int d = 0; d < dim; d++) mean_f32[(size_t)k * DP + d] = (float)gmm.mean[(size_t)k * dim + d];
-            w.mean_f32.upload(mean_f32.data(), mean_f32.size());
-            w.slabs.ensure((size_t)grid * n_elem);
-            SR_HIP(hipMemsetAsync(w.slabs.p, 0, (size_t)grid * n_elem * sizeof(float), ctx().stream));
-            {
-                ScopedKernelTimer t(T_ESTEP);
-                if (DP > MAX_REG_DIM) {
-                    const int gy = std::max(1, std::min((n_records + CB - 1) / CB, (4 * ctx().n_cu + grid - 1) / grid));
-                    hipLaunchKernelGGL(em_stats_wide_kernel, dim3(grid, gy), dim3(256), 0, ctx().stream, feat.data.p, (int64_t)n, dim, DP,
-                                       reinterpret_cast<const float4 *>(set.d_params.p), set.d_center0.p, n_records, w.mean_f32.p,
-                                       sres.d_frame_ll, w.slabs.p, n_tiles);
-                } else {
-                    dispatch_stats(DP, feat.data.p, n, dim, reinterpret_cast<const float4 *>(set.d_params.p), set.d_center0.p,
-                                   n_records, w.mean_f32.p, sres.d_frame_ll, w.slabs.p, n_tiles, grid);
-                }
-            }
-            SR_HIP(hipGetLastError());
-            hipLaunchKernelGGL(em_reduce_kernel, dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0,
-                               ctx().stream, w.slabs.p, grid, (int)n_elem, w.stats.p);
-        }
-        SR_HIP(hipGetLastError());
-        w.h_stats.ensure(n_elem);
+        trace.mark(true);
+        const EmStatsPlan plan = plan_em_stats(K, dim, set.host.dp, n, em_stats_engine_option(), split_bf16_in_range(set), set.bx3.ks,
+                                               (int)set.bx3.chunks.size(), ctx().n_cu);
+        g_last_stats_engine.store(plan.engine);
+        w.ensure(plan);
+        launch_em_stats(plan, set, feat, sres.d_frame_ll, gmm, w);
         double *const stats = w.h_stats.p;
-        w.stats.download(stats, n_elem);
+        w.stats.download(stats, plan.n_elem);
         sync_stream();
-        if (use_mfma) {
-            // T1 = sum g x, T2 = sum g x^2, N = sum g  ->  the centred sums the M-step below works on, about the fp32 mean
-            // the vector form centres on: sum g (x - m) = T1 - N m, sum g (x - m)^2 = T2 - 2 m T1 + N m^2 (float64)
-            for (int k = 0; k < K; k++) {
-                double *st = stats + (size_t)k * REC;
-                const double N = st[2 * DP];
-                for (int d = 0; d < dim; d++) {
-                    const double m = (double)(float)gmm.mean[(size_t)k * dim + d];
-                    const double t1 = st[d], t2 = st[DP + d];
-                    st[d] = t1 - N * m;
-                    st[DP + d] = t2 - 2.0 * m * t1 + N * m * m;
-                }
-            }
-        }
-        const double t4 = now();
-
-        // Mixtures without support: a responsibility below fp32's range (~1e-38) is 0 on the device, while the
-        // reference's float64 keeps it down to DBL_MIN -- its N_k is then tiny but not 0, and the mixture's mean
-        // jumps to the responsibility-weighted mean of the frames (gmm.cc:396-412) instead of staying put.  Such
-        // mixtures (rare: more mixtures than the data supports) get their three sums again on the host, in float64,
-        // with the reference's rules (terms below DBL_MIN are 0; frames whose likelihood underflowed carry none).
-        {
-            std::vector<int> weak;
-            for (int k = 0; k < K; k++)
-                if (stats[(size_t)k * REC + 2 * DP] < 1e-25) weak.push_back(k);
-            if (!weak.empty()) {
-                std::vector<float> ll((size_t)n);
-                SR_HIP(hipMemcpyAsync(ll.data(), sres.d_frame_ll, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx().stream));
-                sync_stream();
-                const double SQRT_2_PI = 2.5066282746310002, MINLOG = -708.396418532264;
-                const float *ll_p = ll.data();
-                auto redo = [&, ll_p](int k) {
-                    double *st = stats + (size_t)k * REC;
-                    for (int e = 0; e < REC; e++) st[e] = 0.0;
-                    const double *mu = gmm.mean.data() + (size_t)k * dim, *sg = gmm.sigma.data() + (size_t)k * dim;
-                    double c = gmm.weights[k] > 0 ? std::log(gmm.weights[k]) : -INFINITY;
-                    for (int d = 0; d < dim; d++) c -= std::log(SQRT_2_PI * sg[d]);
-                    for (long i = 0; i < n; i++) {
-                        if (!(ll_p[i] >= (float)MINLOG)) continue;
-                        const float *x = X + (size_t)i * dim;
-                        double lp = c;
-                        for (int d = 0; d < dim; d++) {
-                            const double v = ((double)x[d] - mu[d]) / sg[d];
-                            lp -= 0.5 * v * v;
-                        }
-                        if (!(lp >= MINLOG)) continue;
-                        const double gam = std::exp(lp - (double)ll_p[i]);
-                        for (int d = 0; d < dim; d++) {
-                            const double dv = (double)x[d] - (double)(float)mu[d];       // centred on the fp32 mean the device used
-                            st[d] += gam * dv;
-                            st[DP + d] += gam * dv * dv;
-                        }
-                        st[2 * DP] += gam;
-                    }
-                };
-                // A large UBM adapted on a short utterance leaves MANY mixtures without support (2048 mixtures, 3000 frames: this
-                // loop was 4.6 of an iteration's 6.5 ms -- one division per (mixture, frame, dimension) on one core).  The mixtures
-                // are independent -- each writes its own row of sums -- so they are dealt to a few host threads: same operations
-                // in the same order per mixture, same bits for any number of threads.
-                const size_t work = weak.size() * (size_t)n * (size_t)dim;
-                const int n_thr = work < ((size_t)1 << 20) ? 1 : (int)std::max<size_t>(1, std::min<size_t>({weak.size(), (size_t)std::thread::hardware_concurrency(), (size_t)16}));
-                if (n_thr <= 1) {
-                    for (int k : weak) redo(k);
-                } else {
-                    std::atomic<size_t> next{0};
-                    auto worker = [&]() {
-                        for (size_t j; (j = next.fetch_add(1)) < weak.size();) redo(weak[j]);
-                    };
-                    std::vector<std::future<void>> helpers;
-                    for (int t = 1; t < n_thr; t++) {
-                        try {
-                            helpers.push_back(std::async(std::launch::async, worker));
-                        } catch (const std::system_error &) {      // (no thread to be had: the others take its share)
-                            break;
-                        }
-                    }
-                    worker();
-                    for (auto &h : helpers) h.get();
-                }
-            }
-        }
+        if (plan.slab_f64) recentre_origin_sums(stats, plan.dp, model);
+        trace.mark(false);
+        redo_unsupported(stats, plan.dp, model, X, n, sres.d_frame_ll);
 
         // ---- M-step (float64, host; O(K*D)) ----
-        std::vector<double> Nk(K);
-        for (int k = 0; k < K; k++) {
-            double v = stats[(size_t)k * REC + 2 * DP];
-            if (v == 0) v = 1e-6;                            // min_n_k, gmm.cc:502-509
-            Nk[k] = v;
-        }
-        if (!ubm) {                                          // update_weights, gmm.cc:388-394
-            double wsum = 0;
-            for (int k = 0; k < K; k++) {
-                gmm.weights[k] = Nk[k] / (double)n;
-                wsum += gmm.weights[k];
-            }
-            for (int k = 0; k < K; k++) gmm.weights[k] /= wsum;
-        }
-        for (int k = 0; k < K; k++) {
-            for (int d = 0; d < dim; d++) {
-                const double sd = stats[(size_t)k * REC + d];
-                const double sdd = stats[(size_t)k * REC + DP + d];
-                const double mu_old = gmm.mean[(size_t)k * dim + d];
-                const double shift = sd / Nk[k];             // E_k[x] - mu_old
-                // no responsibility at all (raw N_k 0, the sums above exact zeros): the reference's E_k[x] = sum g x / 1e-6
-                // is 0, not the old mean (gmm.cc:396-412)
-                const double ex = stats[(size_t)k * REC + 2 * DP] == 0 ? 0.0 : mu_old + shift;
-                if (ubm) {                                   // update_means, gmmubm.cc:53-74
-                    const double alpha = Nk[k] / (Nk[k] + relevance);
-                    gmm.mean[(size_t)k * dim + d] = alpha * ex + (1 - alpha) * ubm->mean[(size_t)k * dim + d];
-                } else {                                     // gmm.cc:396-412, :415-437
-                    gmm.mean[(size_t)k * dim + d] = ex;
-                    // sum g (x - mu_new)^2 = sdd - 2 shift sd + shift^2 N = sdd - N shift^2
-                    double var = sdd / Nk[k] - shift * shift;
-                    if (var < 0) var = 0;
-                    gmm.sigma[(size_t)k * dim + d] = std::max(min_sigma, std::sqrt(var));
-                }
-            }
-        }
+        em_mstep(stats, plan.dp, model, n, ubm ? ubm->mean.data() : nullptr, relevance, min_sigma);
         gmm.drop_single();
-        if (own) spare.push_back(std::move(set_owner));       // (the E-step's kernels ended before the sums came back)
-        if (trace)
-            printf("iter %d: pack %.2f ms, upload %.2f ms, posteriors' denominators %.2f ms, statistics %.2f ms, M-step %.2f ms\n", it,
-                   (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (now() - t4) * 1e3);
+        if (!ubm_set) pool.give(std::move(set_owner));       // (the E-step's kernels ended before the sums came back)
+        trace.print(it);
 
         if (it % 2 == 0) continue;                           // gmm.cc:622-623
-        if (reference_side_effects_option()) {               // gmm.cc:624-630
-            const char *dump_file = "gmm-training-intermediate-dump.model";
-            printf("dumping model to %s ...\n", dump_file);
-            const std::string text = gmm_format_text(gmm);
-            if (FILE *f = fopen(dump_file, "w")) {
-                fwrite(text.data(), 1, text.size(), f);
-                fclose(f);
-            }
-            printf("model dumped to %s ...\n", dump_file);
-        }
+        if (reference_side_effects_option()) dump_intermediate_model(gmm);
         // total log-likelihood under the updated model (gmm.cc:631-641), reference clamp on
-        carried = take_set();
-        SRModelSet &set2 = *carried;
-        pack_em_set(set2, gmm);
-        upload_em_set(set2);
+        pool.carried = pool.take();
+        pack_em_set(*pool.carried, gmm);
+        upload_em_set(*pool.carried);
         double ll = 0.0;
-        score_batch_set(set2, feat, &ll, nullptr, nullptr, SR_CLAMP_COMPAT | SCORE_PRECISE);
+        score_batch_set(*pool.carried, feat, &ll, nullptr, nullptr, SR_CLAMP_COMPAT | SCORE_PRECISE);
         if (param.verbosity >= 1) printf("iter %d: ll %lf\n", it, ll);
-        const double ll_diff = ll - last_ll;
-        if (std::fabs(ll_diff) / std::fabs(ll) < param.threshold && ll_diff < param.threshold) {
+        if (em_converged(ll, last_ll, param.threshold)) {    // gmm.cc:643-650
             it++;
-            break;                                           // gmm.cc:643-650
+            break;
         }
         last_ll = ll;
     }

@@ -110,8 +110,6 @@ struct E64Workspace {
 
 }  // namespace
 
-bool em_f64_eligible(int K, int dim, long n, const Parameter &param) { return em_f64_shape_eligible(K, dim, n, param); }
-
 // The fit of `gmm` (its parameters are the start) on the n resident frames dX, an iteration = four launches.  true: done -- gmm holds
 // the result, *iterations the count train_em returns; false: a frame this path leaves to the other one (gmm untouched).
 bool train_em_f64(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations) {

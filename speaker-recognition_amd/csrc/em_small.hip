@@ -441,10 +441,6 @@ struct EmSmallWorkspace {
 
 void set_em_small_test_absent(int v) { em_small_test_absent().store(v); }
 
-bool em_small_eligible(int K, int dim, long n, const Parameter &param) {
-    return em_small_shape_eligible(K, dim, n, param, ctx().n_cu);
-}
-
 // The fit of `gmm` (its parameters are the start) on the n resident frames dX.  true: done -- gmm holds the result, *iterations the
 // count train_em returns; false: the kernel met what it leaves to the iteration-at-a-time path (gmm untouched).
 bool train_em_small(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations) {

@@ -4,7 +4,7 @@
 // frames fails alone), the cut of the batched speakers into groups whose float64 scratch fits the bound, and per group the tile
 // tables the kernels read -- as a pure function of the model's shape, the speakers' lengths, the training parameters, the bound
 // and the number of compute units.  The two eligibility rules of train_em's engine choice live here so that they can be
-// evaluated without a device: em_small.hip and em_f64.hip call them.
+// evaluated without a device: em_route (em_plan.cpp) calls them.
 // Host-only C++17, nothing of HIP: map_batch.hip consumes it, sr_map_fit_plan hands it to tests, tests/host/map_checks.cpp runs
 // it under the host sanitizers.
 #pragma once
