@@ -700,6 +700,70 @@ int sr_jfa_score_linear(int64_t T, int64_t J, int K, int D, int Ry, int Ru, cons
 int sr_jfa_score_plan(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, int64_t *out,
                       int n_out);
 
+/* ---- The JFA leg resident on the device (csrc/jfa_stats.hip): statistics that stay there from the Baum-Welch pass to the score
+ * matrix.  Nothing above changes; these are the same kernels reached without the statistics going home in between.
+ * SRStats: raw N [n][K] and F [n][K*D] (not centred, mixture-major, float64) of n sessions on one device.
+ * sr_bw_stats_resident: the passes of sr_bw_stats_batch -- same plan, same kernels, same launch order -- with the reduce writing
+ *   into buffers the handle owns; only ll and dropped come back.  sr_stats_get of the handle returns the bits sr_bw_stats_batch
+ *   returns.  The result is checked by a small device kernel (finite, N >= 0) when the handle is made.  At least one utterance.
+ * sr_stats_from_host: uploads host arrays once, validated first (finite values, N >= 0: the texts of sr_jfa_open).
+ * sr_stats_info: 4 fields (n_out >= 4): n, K, D, device; returns 4.  sr_stats_get: N and / or F back to the host.
+ * sr_stats_take: a new handle of the rows named, a device gather: any order, repeats allowed.
+ * sr_stats_close: NULL and a handle closed before are harmless; every other call refuses a closed handle by its text.
+ * sr_jfa_open_centred: the grouping and centring on the device into an ordinary SRJfa (sr_jfa_factors, sr_jfa_train, sr_jfa_close
+ *   work on it unchanged; it owns its arrays: the statistics handle may be closed while it lives).  ids [n]: 0-based labels below
+ *   n_labels; N_j (x) w: the row of K counts expanded over D.
+ *     mode 0, groups = the labels that occur, ascending:  N_g = sum_{j in g} N_j,
+ *             Fc_g = sum_{j in g} (F_j - N_j (x) (x_j u)) - N_g (x) (m + z_g .* d + y_g v)
+ *     mode 1, groups = sessions:  Fc_j = (F_j - N_j (x) (x_j u)) - N_j (x) (m + z_s .* d + y_s v),  s = ids[j]
+ *   A NULL pair (d and z [n_labels][K*D]; v [Ry][K*D] and y [n_labels][Ry]; u [Ru][K*D] and x [n][Ru]) is an absent term, not a
+ *   product with zeros.  y v and x u run on v_mfma_f64_16x16x4_f64 through the GEMM kernel of sr_jfa_factors, x u a chunk of
+ *   sessions at a time under "jfa_scratch_mib" (chunks are a function of n, K*D and the bound only); one streaming kernel reads F,
+ *   N and the product once and writes Fc once.  A group's sessions are added in ascending session order, N_g with plain adds; no
+ *   atomics: a group's row is the same bits alone (its sessions taken into a handle of their own), inside any batch, under any
+ *   bound, from run to run.
+ * sr_jfa_statistics: what a factor handle holds, N [G][K] and / or Fc [G][K*D].
+ * sr_jfa_centre_plan: what sr_jfa_open_centred decides (csrc/jfa_plan.cpp, host only; Ry / Ru 0: the term is absent), for tests.
+ *   Writes 16 fields (n_out >= 16) and returns 16, -1 on refusal: mode, sessions per chunk, chunks, bytes of a chunk's product,
+ *   bounds of the bytes of N, Fc, y v and z, doubles per lane of the centring kernel, the grids x y of a chunk's x u product, of
+ *   y v and of the centring kernel, the GEMM's row tile (chunks but the last are multiples of it).
+ * sr_jfa_zd: estimate_z_and_d.m on a handle's resident N_g, Fc_g and E (from sr_jfa_open_centred centred with y and x, or from
+ *   sr_jfa_open):  L = 1 + N_g (x) d^2 / E,  z = Fc_g .* d ./ (E .* L),  a = sum_g (1 / L + z^2) .* N_g,  b = sum_g z .* Fc_g,
+ *   d <- b / a, n_iter times in ONE launch (columns do not interact; the sums run in group order).  d in / out (n_iter = 0: one
+ *   evaluation, d untouched); z, a, b (each or NULL): of the last round, i.e. for the d that round started from.  A column no
+ *   group occupies with d = 0 gives 0 / 0 as the reference does.
+ * sr_jfa_score_integrated_stats / sr_jfa_score_linear_stats: the two scorers with a statistics handle in place of T, K, D, N, F:
+ *   the same launches on the handle's buffers; n_t and the empty-segment count come from a device kernel that adds a segment's K
+ *   counts in mixture order -- the scores are the same bits as the host-array entries give for the same numbers.
+ * Timer kinds (none is added): SR_T_JFA_GRAM the check, gather, group-count, centring, z / d and n_t kernels; SR_T_JFA_GEMM_C y v, x u.
+ * Refused, before the device is touched, with a message that names the argument and the remedy: a NULL or closed statistics
+ * handle, labels that are negative or >= n_labels, Ry / Ru outside 1 .. 512, a non-finite value in any host array, E <= 0, half
+ * of a pair, rows outside the handle, a bound below one chunk of 64 sessions, a handle on another device than the calling
+ * thread's; and in a process forked after the GPU runtime was initialised. */
+typedef struct SRStats SRStats;
+SRStats *sr_bw_stats_resident(SRModelSet *set, int model, SRBatch *feats, double *ll /*[U] or NULL*/, int64_t *dropped /*[U] or NULL*/);
+SRStats *sr_stats_from_host(int64_t n, int K, int D, const double *N /*[n][K]*/, const double *F /*[n][K*D]*/);
+int sr_stats_info(const SRStats *s, int64_t *out /*n, K, D, device*/, int n_out);
+int sr_stats_get(const SRStats *s, double *N /*or NULL*/, double *F /*or NULL*/);
+SRStats *sr_stats_take(const SRStats *s, const int64_t *rows, int64_t n_rows);
+void sr_stats_close(SRStats *s);
+SRJfa *sr_jfa_open_centred(const SRStats *s, const double *E /*[K*D]*/, const double *m /*[K*D]*/, int mode, const int64_t *ids /*[n]*/,
+                           int64_t n_labels, const double *d /*[K*D] or NULL*/, const double *z /*[n_labels][K*D] or NULL*/,
+                           const double *v /*[Ry][K*D] or NULL*/, int Ry, const double *y /*[n_labels][Ry] or NULL*/,
+                           const double *u /*[Ru][K*D] or NULL*/, int Ru, const double *x /*[n][Ru] or NULL*/);
+int sr_jfa_statistics(SRJfa *h, double *N /*[G][K] or NULL*/, double *Fc /*[G][K*D] or NULL*/);
+int sr_jfa_centre_plan(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int64_t *out, int n_out);
+int sr_jfa_zd(SRJfa *h, double *d /*[K*D] in/out*/, int n_iter, double *z /*[G][K*D] or NULL*/, double *a /*[K*D] or NULL*/,
+              double *b /*[K*D] or NULL*/);
+int sr_jfa_score_integrated_stats(const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d /*or NULL*/,
+                                  const double *v, const double *u, const double *z /*or NULL*/, const double *y,
+                                  const unsigned char *mask /*or NULL*/, int64_t mask_rows, int64_t mask_cols, double *out /*[J][T]*/,
+                                  int64_t *empty_segments /*or NULL*/, int64_t *bad_segments /*or NULL*/);
+int sr_jfa_score_linear_stats(const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d /*or NULL*/,
+                              const double *v, const double *u, const double *z /*or NULL*/, const double *y, const double *x /*[T][Ru]*/,
+                              const unsigned char *mask /*or NULL*/, int64_t mask_rows, int64_t mask_cols, double *out /*[J][T]*/,
+                              int64_t *empty_segments /*or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

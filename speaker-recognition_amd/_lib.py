@@ -44,6 +44,8 @@ EXT_SYMBOLS = [
     "sr_bw_stats_batch", "sr_bw_plan",
     "sr_jfa_open", "sr_jfa_factors", "sr_jfa_update", "sr_jfa_train", "sr_jfa_close", "sr_jfa_plan",
     "sr_jfa_score_integrated", "sr_jfa_score_linear", "sr_jfa_score_plan",
+    "sr_bw_stats_resident", "sr_stats_from_host", "sr_stats_info", "sr_stats_get", "sr_stats_take", "sr_stats_close",
+    "sr_jfa_open_centred", "sr_jfa_statistics", "sr_jfa_centre_plan", "sr_jfa_zd", "sr_jfa_score_integrated_stats", "sr_jfa_score_linear_stats",
     "sr_multi_slot_pieces", "sr_multi_plan",
     "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
 ]
@@ -224,6 +226,19 @@ def lib():
         "sr_jfa_score_linear": (i32, [i64, i64, i32, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint8), i64, i64, dp,
                                       C.POINTER(i64)]),
         "sr_jfa_score_plan": (i32, [i64, i64, i32, i32, i32, i32, i32, i64, i32, i32, C.POINTER(i64), i32]),
+        "sr_bw_stats_resident": (vp, [vp, i32, vp, dp, C.POINTER(i64)]),
+        "sr_stats_from_host": (vp, [i64, i32, i32, dp, dp]),
+        "sr_stats_info": (i32, [vp, C.POINTER(i64), i32]),
+        "sr_stats_get": (i32, [vp, dp, dp]),
+        "sr_stats_take": (vp, [vp, C.POINTER(i64), i64]),
+        "sr_stats_close": (None, [vp]),
+        "sr_jfa_open_centred": (vp, [vp, dp, dp, i32, C.POINTER(i64), i64, dp, dp, dp, i32, dp, dp, i32, dp]),
+        "sr_jfa_statistics": (i32, [vp, dp, dp]),
+        "sr_jfa_centre_plan": (i32, [i64, i64, i32, i32, i32, i32, i32, i64, C.POINTER(i64), i32]),
+        "sr_jfa_zd": (i32, [vp, dp, i32, dp, dp, dp]),
+        "sr_jfa_score_integrated_stats": (i32, [vp, i64, i32, i32, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint8), i64, i64, dp,
+                                                C.POINTER(i64), C.POINTER(i64)]),
+        "sr_jfa_score_linear_stats": (i32, [vp, i64, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint8), i64, i64, dp, C.POINTER(i64)]),
         "sr_multi_slot_pieces": (i32, [vp, i32]),
         "sr_multi_plan": (i32, [C.POINTER(i64), i32, C.POINTER(i32), i32, i32, C.POINTER(i32)] + [C.POINTER(i32)] * 4),
         "sr_map_fit_batch": (i32, [C.POINTER(vp), i32, vp, fp, C.POINTER(i64), i32, C.POINTER(Parameter), C.c_long, C.POINTER(i32),
@@ -503,6 +518,18 @@ JFA_SCORE_PLAN_FIELDS = ("mode", "chunk", "n_chunks", "seg_bytes", "bytes_scratc
                          "cross_grid_y", "cross_grid_z", "gemm_L_x", "gemm_L_y", "gemm_a_x", "gemm_a_y", "gemm_lin_x", "gemm_lin_y", "gemm_quad_x",
                          "gemm_quad_y", "gemm_h_x", "gemm_h_y", "kscore_grid", "gemm_xu_x", "gemm_xu_y", "comp_grid", "gemm_out_x", "gemm_out_y",
                          "gram_lds", "gemm_lds", "cross_lds", "kscore_lds", "kscore_rounds", "max_R", "max_lds_rows", "max_J")
+
+
+def jfa_centre_plan(n: int, n_labels: int, K: int, D: int, Ry: int = 0, Ru: int = 0, groups: str = "speakers", scratch_bytes: int = 1 << 30) -> dict:
+    """What ``sr_jfa_open_centred`` decides for n sessions with labels below n_labels, a K x D model and y v / x u terms of Ry / Ru
+    factors (0: absent) under a scratch bound (csrc/jfa_plan.cpp; host only): the refusals, sessions per chunk of the x u product,
+    chunks, bytes, doubles per lane and the grids."""
+    v = (C.c_int64 * 16)()
+    check(lib().sr_jfa_centre_plan(int(n), int(n_labels), int(K), int(D), int(Ry), int(Ru), {"speakers": 0, "sessions": 1}.get(groups, -1),
+                                   int(scratch_bytes), v, 16), "sr_jfa_centre_plan")
+    keys = ("mode", "chunk", "n_chunks", "bytes_scratch", "bytes_N", "bytes_Fc", "bytes_yv", "bytes_z", "vec", "gemm_xu_x", "gemm_xu_y",
+            "gemm_yv_x", "gemm_yv_y", "centre_x", "centre_y", "row_tile")
+    return dict(zip(keys, (int(x) for x in v)))
 
 
 def jfa_score_plan(T: int, J: int, K: int, D: int, Ry: int, Ru: int, mode: str = "integrated", scratch_bytes: int = 1 << 30, lds_rows: int = 0,

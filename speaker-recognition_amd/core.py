@@ -206,16 +206,24 @@ class ModelSet:
                                             _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_score_batch_set_topc")
         return (sums, arg) + ((fll,) if frame_ll else ()) + ((sel,) if selection else ())
 
-    def bw_stats(self, feats: Batch, model: int = 0, ll: bool = False):
+    def bw_stats(self, feats: Batch, model: int = 0, ll: bool = False, resident: bool = False):
         """Baum-Welch statistics of every utterance of a feature batch against model ``model`` of the set, the UBM
         (sr_bw_stats_batch): -> (N[U, K], F[U, K * D][, ll[U], dropped[U]]), float64 (dropped: int64).  N[u, k] = sum_t gamma_k(t),
         F[u, k * D + d] = sum_t gamma_k(t) x_t[d] (mixture-major, the supervector order), ll[u] the utterance's log-likelihood;
         a frame whose log-sum-exp is not finite (a NaN row, values beyond every density's range) contributes nothing and is
         counted in ``dropped``.  A PCM batch, a model index out of range, rows wider than 40 dimensions or a dimension mismatch
-        raise ``SRError`` before the device is touched."""
+        raise ``SRError`` before the device is touched.  ``resident``: N and F stay on the device in a ``jfa.Stats`` (the same
+        passes, the same bits; sr_bw_stats_resident) -> stats, or (stats, ll, dropped)."""
         model = int(model)
         K = self._keep[model].get_nr_mixtures() if 0 <= model < len(self._keep) else 0
         U, D = feats.n_utt, self.dim
+        if resident:
+            from .jfa import Stats
+            lls = np.zeros(U, dtype=np.float64)
+            dropped = np.zeros(U, dtype=np.int64)
+            h = check(lib().sr_bw_stats_resident(self._h, model, feats._h, _lib.as_dp(lls), _lib.as_i64p(dropped)), "sr_bw_stats_resident")
+            stats = Stats(h)
+            return (stats, lls, dropped) if ll else stats
         N = np.zeros((U, K), dtype=np.float64)
         F = np.zeros((U, K * D), dtype=np.float64)
         lls = np.zeros(U, dtype=np.float64)

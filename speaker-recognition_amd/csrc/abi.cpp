@@ -904,6 +904,47 @@ int sr_bw_stats_batch(SRModelSet *set, int model, SRBatch *feats, double *N, dou
     SR_CATCH(-1)
 }
 
+SRStats *sr_bw_stats_resident(SRModelSet *set, int model, SRBatch *feats, double *ll, int64_t *dropped) {
+    SR_TRY
+    if (!set || !feats) fail("sr_bw_stats_resident: null argument");
+    return bw_stats_resident(*set, model, *feats, ll, dropped);
+    SR_CATCH(nullptr)
+}
+
+// ---- statistics handles (jfa_stats.hip) ----
+
+SRStats *sr_stats_from_host(int64_t n, int K, int D, const double *N, const double *F) {
+    SR_TRY
+    return stats_from_host(n, K, D, N, F);
+    SR_CATCH(nullptr)
+}
+
+int sr_stats_info(const SRStats *s, int64_t *out, int n_out) {
+    SR_TRY
+    stats_info(s, out, n_out);
+    return 4;
+    SR_CATCH(-1)
+}
+
+int sr_stats_get(const SRStats *s, double *N, double *F) {
+    SR_TRY
+    stats_get(s, N, F);
+    return 0;
+    SR_CATCH(-1)
+}
+
+SRStats *sr_stats_take(const SRStats *s, const int64_t *rows, int64_t n_rows) {
+    SR_TRY
+    return stats_take(s, rows, n_rows);
+    SR_CATCH(nullptr)
+}
+
+void sr_stats_close(SRStats *s) {
+    SR_TRY
+    stats_close(s);
+    SR_CATCH_VOID
+}
+
 int sr_bw_plan(int S, int model, int K, int D, int batch_is_features, int feat_dim, const int64_t *lengths, int64_t n_utt,
                int64_t range_frames, int64_t scratch_bytes, int n_cu, int64_t *ranges_out, int64_t range_cap, int64_t *out, int n_out) {
     SR_TRY
@@ -1075,7 +1116,64 @@ int sr_jfa_plan(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_r
     SR_CATCH(-1)
 }
 
+// ---- grouping and centring on the device, the z / d iteration (jfa_stats.hip) ----
+
+SRJfa *sr_jfa_open_centred(const SRStats *s, const double *E, const double *m, int mode, const int64_t *ids, int64_t n_labels, const double *d,
+                           const double *z, const double *v, int Ry, const double *y, const double *u, int Ru, const double *x) {
+    SR_TRY
+    return jfa_open_centred(s, E, m, mode, ids, n_labels, d, z, v, Ry, y, u, Ru, x);
+    SR_CATCH(nullptr)
+}
+
+int sr_jfa_statistics(SRJfa *h, double *N, double *Fc) {
+    SR_TRY
+    if (!h) fail("sr_jfa_statistics: null argument");
+    jfa_statistics(*h, N, Fc);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_zd(SRJfa *h, double *d, int n_iter, double *z, double *a, double *b) {
+    SR_TRY
+    if (!h) fail("sr_jfa_zd: null argument");
+    jfa_zd(*h, d, n_iter, z, a, b);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_centre_plan(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 16) fail("sr_jfa_centre_plan writes 16 fields");
+    std::string why;
+    JfaCentrePlan p;
+    if (!plan_jfa_centre(n, n_labels, K, D, Ry, Ru, mode, scratch_bytes, p, why)) fail("%s", why.c_str());
+    const int64_t v[16] = {p.mode, p.chunk, p.n_chunks, p.bytes_scratch, p.bytes_N, p.bytes_Fc, p.bytes_yv, p.bytes_z, p.vec, p.gemm_xu.x,
+                           p.gemm_xu.y, p.gemm_yv.x, p.gemm_yv.y, p.centre.x, p.centre.y, JFA_TILE};
+    std::memcpy(out, v, sizeof v);
+    return 16;
+    SR_CATCH(-1)
+}
+
 // ---- JFA trial scoring (jfa_score.hip) ----
+
+int sr_jfa_score_integrated_stats(const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d, const double *v,
+                                  const double *u, const double *z, const double *y, const unsigned char *mask, int64_t mask_rows, int64_t mask_cols,
+                                  double *out, int64_t *empty_segments, int64_t *bad_segments) {
+    SR_TRY
+    jfa_score_stats(JFA_SCORE_INTEGRATED, tst, J, Ry, Ru, m, E, d, v, u, z, y, nullptr, mask, mask_rows, mask_cols, out, empty_segments, bad_segments);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_jfa_score_linear_stats(const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d, const double *v,
+                              const double *u, const double *z, const double *y, const double *x, const unsigned char *mask, int64_t mask_rows,
+                              int64_t mask_cols, double *out, int64_t *empty_segments) {
+    SR_TRY
+    jfa_score_stats(JFA_SCORE_LINEAR, tst, J, Ry, Ru, m, E, d, v, u, z, y, x, mask, mask_rows, mask_cols, out, empty_segments, nullptr);
+    return 0;
+    SR_CATCH(-1)
+}
 
 int sr_jfa_score_integrated(int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
                             const double *d, const double *v, const double *u, const double *z, const double *y, const unsigned char *mask,

@@ -24,9 +24,12 @@
 // Deterministic: no atomics; an utterance's cut into ranges depends on its own length and the option bw_range_frames only, its
 // slabs are added in range order whatever group they were computed in -- N, F and ll of an utterance are the same bits alone, in
 // any batch and under any scratch bound.
+// Two entry points share one body (bw_stats_run): sr_bw_stats_batch reduces into the per-device scratch and copies N and F home;
+// sr_bw_stats_resident reduces into the buffers of a statistics handle (jfa_dev.hpp, jfa_stats.hip) and leaves them there.
 #include "batch.hpp"
 #include "bw_plan.hpp"
 #include "gmm_model.hpp"
+#include "jfa_dev.hpp"
 #include "score.hpp"
 #include "wave_ops.hpp"
 
@@ -348,7 +351,16 @@ static void launch_bw_stats(dim3 grid, hipStream_t st, const float *X, int dim, 
 
 #define SR_BW_DIMS(CASE) CASE(8) CASE(13) CASE(16) CASE(24) CASE(26) CASE(32) CASE(34) CASE(39) CASE(40)
 
-void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, double *F_out, double *ll_out, int64_t *dropped_out) {
+// The passes of one call, N and F into device memory the caller names: the per-device scratch (sr_bw_stats_batch, which then
+// copies them home) or a statistics handle's own buffers (sr_bw_stats_resident).  `out(U, K, D)` is asked for the two pointers
+// once every refusal is past and the device is bound; ll and dropped come back through the pinned staging buffers.
+struct BwOut {
+    double *N = nullptr, *F = nullptr;
+};
+
+template <typename OutFn>
+static void bw_stats_run(const char *what, SRModelSet &set, int model, SRBatch &feat, OutFn &&out, double *N_out, double *F_out, double *ll_out,
+                         int64_t *dropped_out) {
     // every refusal before the device is touched
     const int S = set.host.n_models, D = set.host.dim;
     const int K = (model >= 0 && model < (int)set.host.model_mixtures.size()) ? set.host.model_mixtures[model] : 0;
@@ -356,8 +368,7 @@ void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, do
     if (!bw_check(feat.kind == SRBatch::FEATURES, S, model, K, D, feat.dim, why)) fail("%s", why.c_str());
     const int U = feat.n_utt;
     const int64_t n = feat.n_rows;
-    if (U > 0 && (!N_out || !F_out)) fail("sr_bw_stats_batch: null output (N and F are both required)");
-    if (gpu_runtime_lost()) fail_gpu_runtime_lost("sr_bw_stats_batch");
+    if (gpu_runtime_lost()) fail_gpu_runtime_lost(what);
     ensure_device();
     feat.bind_device();
     if (set.device != ctx().device) fail("model set lives on device %d, the calling thread is on device %d", set.device, ctx().device);
@@ -366,6 +377,7 @@ void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, do
     BwPlan pl;
     if (!plan_bw(K, D, lengths.data(), U, bw_range_frames(), (int64_t)bw_scratch_mib() << 20, ctx().n_cu, pl, why)) fail("%s", why.c_str());
     if (pl.dp != set.host.dp) fail("Baum-Welch statistics: the set is packed at %d padded dimensions, the plan expects %d", set.host.dp, pl.dp);
+    const BwOut dst = out(U, K, D);
     if (U == 0) return;
     const int n_records = (K + KB - 1) / KB;
     const float4 *params = reinterpret_cast<const float4 *>(set.d_params.p) + set.host.chunks[set.host.model_chunk_begin[model]].offset_f4;
@@ -373,12 +385,10 @@ void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, do
     hipStream_t st = ctx().stream;
     auto &w = per_device<BwScratch>();
     const size_t nN = (size_t)U * K, nF = nN * D;
-    w.N.ensure(nN);
-    w.F.ensure(nF);
     w.ll.ensure((size_t)U);
     w.dropped.ensure((size_t)U);
-    SR_HIP(hipMemsetAsync(w.N.p, 0, nN * sizeof(double), st));
-    SR_HIP(hipMemsetAsync(w.F.p, 0, nF * sizeof(double), st));
+    SR_HIP(hipMemsetAsync(dst.N, 0, nN * sizeof(double), st));
+    SR_HIP(hipMemsetAsync(dst.F, 0, nF * sizeof(double), st));
     if (n > 0) {
         w.lse.ensure((size_t)n);
         ScopedKernelTimer t(T_BW_LSE);
@@ -433,13 +443,13 @@ void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, do
             {
                 ScopedKernelTimer t(T_BW_REDUCE);
                 hipLaunchKernelGGL(bw_reduce_kernel, dim3((unsigned)(n_segs * pl.reduce_blocks)), dim3(BW_WG), 0, st, w.slabs.p,
-                                   w.segs.p + seg_begin[gi], (int)pl.reduce_blocks, K, D, pl.dp, pl.n_mix_blocks, nc, w.N.p, w.F.p);
+                                   w.segs.p + seg_begin[gi], (int)pl.reduce_blocks, K, D, pl.dp, pl.n_mix_blocks, nc, dst.N, dst.F);
                 SR_HIP(hipGetLastError());
             }
         }
     }
-    SR_HIP(hipMemcpyAsync(N_out, w.N.p, nN * sizeof(double), hipMemcpyDeviceToHost, st));
-    SR_HIP(hipMemcpyAsync(F_out, w.F.p, nF * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (N_out) SR_HIP(hipMemcpyAsync(N_out, dst.N, nN * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (F_out) SR_HIP(hipMemcpyAsync(F_out, dst.F, nF * sizeof(double), hipMemcpyDeviceToHost, st));
     w.h_ll.ensure((size_t)U);
     w.h_dropped.ensure((size_t)U);
     SR_HIP(hipMemcpyAsync(w.h_ll.p, w.ll.p, (size_t)U * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -448,6 +458,43 @@ void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, do
     if (ll_out) std::memcpy(ll_out, w.h_ll.p, (size_t)U * sizeof(double));
     if (dropped_out)
         for (int u = 0; u < U; u++) dropped_out[u] = (int64_t)w.h_dropped.p[u];
+}
+
+void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, double *F_out, double *ll_out, int64_t *dropped_out) {
+    if (feat.n_utt > 0 && (!N_out || !F_out)) {
+        // (the shape's refusals come first, as they always did)
+        std::string why;
+        const int K = (model >= 0 && model < (int)set.host.model_mixtures.size()) ? set.host.model_mixtures[model] : 0;
+        if (!bw_check(feat.kind == SRBatch::FEATURES, set.host.n_models, model, K, set.host.dim, feat.dim, why)) fail("%s", why.c_str());
+        fail("sr_bw_stats_batch: null output (N and F are both required)");
+    }
+    bw_stats_run("sr_bw_stats_batch", set, model, feat, [](int U, int K, int D) {
+        auto &w = per_device<BwScratch>();
+        w.N.ensure((size_t)U * K);
+        w.F.ensure((size_t)U * K * D);
+        return BwOut{w.N.p, w.F.p};
+    }, N_out, F_out, ll_out, dropped_out);
+}
+
+SRStats *bw_stats_resident(SRModelSet &set, int model, SRBatch &feat, double *ll_out, int64_t *dropped_out) {
+    if (feat.n_utt < 1) {
+        std::string why;
+        const int K = (model >= 0 && model < (int)set.host.model_mixtures.size()) ? set.host.model_mixtures[model] : 0;
+        if (!bw_check(feat.kind == SRBatch::FEATURES, set.host.n_models, model, K, set.host.dim, feat.dim, why)) fail("%s", why.c_str());
+        fail("sr_bw_stats_resident: the batch holds no utterance; a statistics handle needs at least one session");
+    }
+    SRStats *h = nullptr;
+    try {
+        bw_stats_run("sr_bw_stats_resident", set, model, feat, [&h](int U, int K, int D) {
+            h = stats_new(U, K, D);
+            return BwOut{h->N.p, h->F.p};
+        }, nullptr, nullptr, ll_out, dropped_out);
+        stats_check_device(*h);
+    } catch (...) {
+        stats_close(h);
+        throw;
+    }
+    return h;
 }
 
 }  // namespace sr

@@ -32,15 +32,6 @@
 #include <cmath>
 #include <vector>
 
-struct SRJfa {
-    int64_t G = 0;
-    int K = 0, D = 0, device = 0;
-    sr::DevBuf<double> N, Fc, E, iE;                    // resident for the handle's life
-    sr::DevBuf<double> W, WE, P, A, C, Y, B, L;         // per call, grown on demand
-    sr::DevBuf<int> flags;
-    std::vector<int> h_flags;
-};
-
 namespace sr {
 
 typedef double jfa_f64x4 __attribute__((ext_vector_type(4)));
@@ -367,7 +358,7 @@ static int64_t jfa_count_flags(DevBuf<int> &flags, std::vector<int> &host, int64
     return c;
 }
 
-static void jfa_check_handle(SRJfa &h, const char *what) {
+void jfa_check_handle(SRJfa &h, const char *what) {
     if (gpu_runtime_lost()) fail_gpu_runtime_lost(what);
     ensure_device();
     if (h.device != ctx().device) fail("%s: the handle lives on device %d, the calling thread is on device %d", what, h.device, ctx().device);

@@ -37,13 +37,36 @@ bool jfa_check_rank(int R, std::string &why) {
     return true;
 }
 
+std::string jfa_text_non_finite(const char *what, int64_t element) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "JFA factors: %s holds a non-finite value at element %lld; drop that row or repair the statistics", what,
+             (long long)element);
+    return buf;
+}
+
+std::string jfa_text_negative(int64_t element, int K) {
+    return fmt("JFA factors: N holds a negative occupancy at group %lld, mixture %lld; occupancies are sums of posteriors", element / K, element % K);
+}
+
 bool jfa_check_finite(const double *v, int64_t n, const char *what, std::string &why) {
     for (int64_t i = 0; i < n; i++)
         if (!std::isfinite(v[i])) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "JFA factors: %s holds a non-finite value at element %lld; drop that row or repair the statistics",
-                     what, (long long)i);
-            why = buf;
+            why = jfa_text_non_finite(what, i);
+            return false;
+        }
+    return true;
+}
+
+bool jfa_check_raw_stats(int64_t n, int K, int D, const double *N, const double *F, std::string &why) {
+    if (!jfa_check_shape(n, K, D, why)) return false;
+    if (!N || !F) {
+        why = "JFA statistics: null argument (N and F are both required)";
+        return false;
+    }
+    if (!jfa_check_finite(N, n * K, "N", why) || !jfa_check_finite(F, n * (int64_t)K * D, "F", why)) return false;
+    for (int64_t i = 0; i < n * K; i++)
+        if (N[i] < 0.0) {
+            why = jfa_text_negative(i, K);
             return false;
         }
     return true;
@@ -59,7 +82,7 @@ bool jfa_check_stats(int64_t G, int K, int D, const double *N, const double *Fc,
     if (!jfa_check_finite(N, G * K, "N", why) || !jfa_check_finite(Fc, G * kd, "Fc", why) || !jfa_check_finite(E, kd, "E", why)) return false;
     for (int64_t i = 0; i < G * K; i++)
         if (N[i] < 0.0) {
-            why = fmt("JFA factors: N holds a negative occupancy at group %lld, mixture %lld; occupancies are sums of posteriors", i / K, i % K);
+            why = jfa_text_negative(i, K);
             return false;
         }
     for (int64_t i = 0; i < kd; i++)
@@ -128,6 +151,88 @@ bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_row
     return true;
 }
 
+// ---- resident statistics: grouping and centring ----
+
+bool jfa_centre_check_shape(int64_t n, int K, int D, int mode, int64_t n_labels, int Ry, int Ru, bool has_v, bool has_u, std::string &why) {
+    if (mode != JFA_CENTRE_GROUPS && mode != JFA_CENTRE_SESSIONS) {
+        why = "JFA centring: the mode is 0 (groups are speakers) or 1 (groups are sessions)";
+        return false;
+    }
+    if (!jfa_check_shape(n, K, D, why)) return false;
+    if (n_labels < 1 || n_labels > ((int64_t)1 << 31) - 1) {
+        why = fmt("JFA centring: n_labels is %lld; pass the number of labels, 1 .. 2^31 - 1 (the largest label + 1)", n_labels);
+        return false;
+    }
+    if (has_v && (Ry < 1 || Ry > JFA_MAX_R)) {
+        why = fmt("JFA centring is built for 1 .. %lld factors, Ry is %lld; pass v [Ry][K D] with its y, or neither", JFA_MAX_R, Ry);
+        return false;
+    }
+    if (has_u && (Ru < 1 || Ru > JFA_MAX_R)) {
+        why = fmt("JFA centring is built for 1 .. %lld factors, Ru is %lld; pass u [Ru][K D] with its x, or neither", JFA_MAX_R, Ru);
+        return false;
+    }
+    const int64_t kd = (int64_t)K * D, cap = (int64_t)1 << 36;
+    if (n > cap / kd) {          // (a label without sessions takes no row: at most n rows are ever held)
+        why = "JFA centring: statistics of more than 2^36 values; split the corpus";
+        return false;
+    }
+    return true;
+}
+
+bool jfa_centre_check_labels(const int64_t *ids, int64_t n, int64_t n_labels, std::string &why) {
+    if (!ids) {
+        why = "JFA centring: null argument (ids: one 0-based label per session)";
+        return false;
+    }
+    for (int64_t j = 0; j < n; j++)
+        if (ids[j] < 0 || ids[j] >= n_labels) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "JFA centring: ids[%lld] is %lld, outside 0 .. n_labels - 1 = %lld; labels are 0-based, pass n_labels = the largest + 1",
+                     (long long)j, (long long)ids[j], (long long)(n_labels - 1));
+            why = buf;
+            return false;
+        }
+    return true;
+}
+
+bool plan_jfa_centre(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, JfaCentrePlan &p, std::string &why) {
+    p = JfaCentrePlan();
+    if (!jfa_centre_check_shape(n, K, D, mode, n_labels, Ry, Ru, Ry != 0, Ru != 0, why)) return false;
+    const int64_t kd = (int64_t)K * D, row = kd * (int64_t)sizeof(double);
+    p.mode = mode;
+    p.vec = kd % JFA_CENTRE_VEC == 0 ? JFA_CENTRE_VEC : 1;
+    if (Ru > 0) {
+        // a function of n, K D and the bound only: whole GEMM row tiles, so that a chunk's product is full tiles but the last
+        const int64_t fit = scratch_bytes / row;
+        p.chunk = fit >= n ? n : fit / JFA_TILE * JFA_TILE;
+        p.chunk = std::min<int64_t>(p.chunk, (int64_t)65535 * JFA_TILE);
+        if (p.chunk < 1) {
+            why = fmt("JFA centring: the scratch bound of %lld bytes is below one chunk of %lld bytes (64 sessions' rows of the x u product); "
+                      "raise the option jfa_scratch_mib", scratch_bytes, std::min<int64_t>(n, JFA_TILE) * row);
+            return false;
+        }
+        p.bytes_scratch = p.chunk * row;
+    } else {
+        p.chunk = n;
+    }
+    p.n_chunks = (n + p.chunk - 1) / p.chunk;
+    const int64_t rows = mode == JFA_CENTRE_SESSIONS ? n : std::min(n, n_labels), labels = std::min(n, n_labels);
+    p.bytes_N = rows * K * 8;
+    p.bytes_Fc = rows * row;
+    p.bytes_yv = Ry > 0 ? labels * row : 0;
+    p.bytes_z = labels * row;
+    const int64_t col_blocks = (kd / p.vec + JFA_WG - 1) / JFA_WG;
+    if (col_blocks > 65535) {
+        why = "JFA centring: more than 2^24 supervector columns; split the model";
+        return false;
+    }
+    if (Ru > 0) p.gemm_xu = gemm_grid(p.chunk, kd);
+    if (Ry > 0) p.gemm_yv = gemm_grid(labels, kd);
+    p.centre = JfaGrid{std::min(rows, mode == JFA_CENTRE_SESSIONS ? p.chunk : rows), col_blocks};
+    p.counts = JfaGrid{rows, (K + JFA_WG - 1) / JFA_WG};
+    return true;
+}
+
 // ---- trial scoring ----
 
 bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, std::string &why) {
@@ -153,11 +258,11 @@ bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, i
     return true;
 }
 
-bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F, const double *m,
-                            const double *E, const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
-                            const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why) {
+static bool score_check_inputs(bool resident, int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F,
+                               const double *m, const double *E, const double *d, const double *v, const double *u, const double *z, const double *y,
+                               const double *x, const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why) {
     if (!jfa_score_check_shape(T, J, K, D, Ry, Ru, mode, why)) return false;
-    if (!N || !F || !m || !E || !v || !u || !y) {
+    if ((!resident && (!N || !F)) || !m || !E || !v || !u || !y) {
         why = "JFA scoring: null argument (N, F, m, E, v, u and y are all required; d, z, x and the mask may be absent)";
         return false;
     }
@@ -173,12 +278,12 @@ bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, 
         return false;
     }
     const int64_t kd = (int64_t)K * D;
-    if (!jfa_check_finite(N, T * K, "N", why) || !jfa_check_finite(F, T * kd, "F", why) || !jfa_check_finite(m, kd, "m", why) ||
+    if ((!resident && (!jfa_check_finite(N, T * K, "N", why) || !jfa_check_finite(F, T * kd, "F", why))) || !jfa_check_finite(m, kd, "m", why) ||
         !jfa_check_finite(E, kd, "E", why) || (d && !jfa_check_finite(d, kd, "d", why)) || !jfa_check_finite(v, Ry * kd, "v", why) ||
         !jfa_check_finite(u, Ru * kd, "u", why) || (z && !jfa_check_finite(z, J * kd, "z", why)) || !jfa_check_finite(y, J * Ry, "y", why) ||
         (x && !jfa_check_finite(x, T * Ru, "x", why)))
         return false;
-    for (int64_t i = 0; i < T * K; i++)
+    for (int64_t i = 0; !resident && i < T * K; i++)
         if (N[i] < 0.0) {
             why = fmt("JFA scoring: N holds a negative occupancy at segment %lld, mixture %lld; occupancies are sums of posteriors", i / K, i % K);
             return false;
@@ -189,6 +294,18 @@ bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, 
             return false;
         }
     return true;
+}
+
+bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F, const double *m,
+                            const double *E, const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
+                            const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why) {
+    return score_check_inputs(false, T, J, K, D, Ry, Ru, mode, N, F, m, E, d, v, u, z, y, x, mask, mask_rows, mask_cols, why);
+}
+
+bool jfa_score_check_inputs_resident(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *m, const double *E, const double *d,
+                                     const double *v, const double *u, const double *z, const double *y, const double *x, const unsigned char *mask,
+                                     int64_t mask_rows, int64_t mask_cols, std::string &why) {
+    return score_check_inputs(true, T, J, K, D, Ry, Ru, mode, nullptr, nullptr, m, E, d, v, u, z, y, x, mask, mask_rows, mask_cols, why);
 }
 
 static JfaGrid flat_grid(int64_t n) { return JfaGrid{(n + JFA_WG - 1) / JFA_WG, 1}; }

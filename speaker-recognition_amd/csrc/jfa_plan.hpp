@@ -54,6 +54,36 @@ int jfa_factor_lds_bytes(int R, int path);
 // Fills `p` and returns true, or false with the reason.  lds_rows: the option jfa_lds_rows; n_cu: compute units (>= 1).
 bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, JfaPlan &p, std::string &why);
 
+// ---- resident statistics, grouping and centring (jfa_stats.hip): raw statistics N [n][K], F [n][K D] stay on the device from the
+// Baum-Welch pass on; the centred, group-summed rows of a factor handle are formed there.  With labels ids [n] in [0, n_labels):
+//   mode 0 (groups = the labels that occur, ascending)   N_g = sum_{j in g} N_j
+//          Fc_g = sum_{j in g} (F_j - N_j (x) (x_j u)) - N_g (x) (m + z_g .* d + y_g v)
+//   mode 1 (groups = sessions)                            Fc_j = (F_j - N_j (x) (x_j u)) - N_j (x) (m + z_s .* d + y_s v),  s = ids[j]
+// The session-sized product x u is formed a chunk of sessions at a time under the bound; chunk boundaries depend on n, K D and
+// the bound only.  A group's sessions are added in ascending session order, a later chunk continuing from what the row holds.
+constexpr int JFA_CENTRE_GROUPS = 0, JFA_CENTRE_SESSIONS = 1;
+constexpr int JFA_CENTRE_VEC = 2;           // doubles per lane of the centring kernel where K D is even: 16-byte accesses
+
+struct JfaCentrePlan {
+    int mode = 0;
+    int64_t chunk = 0, n_chunks = 0;        // sessions per chunk (without the x u term: all n in one)
+    int64_t bytes_scratch = 0;              // chunk x K D x 8: the x u product, what the bound bounds (0 without the term)
+    int64_t bytes_N = 0, bytes_Fc = 0;      // of the handle that results: G rows (G = n in mode 1, <= min(n, n_labels) in mode 0: the bound here)
+    int64_t bytes_yv = 0, bytes_z = 0;      // per call, outside the bound: one row per label that can occur
+    int vec = 1;                            // doubles per lane
+    JfaGrid gemm_xu, gemm_yv, centre, counts;      // grids of a full chunk (centre: x = groups at most, y = column blocks)
+};
+
+// The refusals of the shapes and of the labels (null, negative, >= n_labels); true, or false with the text (it names the remedy).
+bool jfa_centre_check_shape(int64_t n, int K, int D, int mode, int64_t n_labels, int Ry, int Ru, bool has_v, bool has_u, std::string &why);
+bool jfa_centre_check_labels(const int64_t *ids, int64_t n, int64_t n_labels, std::string &why);
+bool plan_jfa_centre(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, JfaCentrePlan &p, std::string &why);
+// Raw statistics as a handle takes them: a non-finite value in N or F, a negative N (the texts of jfa_check_stats).
+bool jfa_check_raw_stats(int64_t n, int K, int D, const double *N, const double *F, std::string &why);
+// The two texts alone, for the device-side check of a resident pass's result.
+std::string jfa_text_non_finite(const char *what, int64_t element);
+std::string jfa_text_negative(int64_t element, int K);
+
 // ---- trial scoring (jfa_score.hip): the score matrix [J][T] of J models against T test segments, with the channel factors
 // integrated out (the reference's kscore_famous_19.m) or by the linear approximation (linear_scoring.m).  With M_0 = m,
 // M_j = m + z_j .* d + y_j v, J1 = J + 1:
@@ -86,6 +116,10 @@ bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, i
 bool jfa_score_check_inputs(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *N, const double *F, const double *m,
                             const double *E, const double *d, const double *v, const double *u, const double *z, const double *y, const double *x,
                             const unsigned char *mask, int64_t mask_rows, int64_t mask_cols, std::string &why);
+// The same with the segments' statistics in a resident handle (validated when it was made): N and F are not read.
+bool jfa_score_check_inputs_resident(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, const double *m, const double *E, const double *d,
+                                     const double *v, const double *u, const double *z, const double *y, const double *x, const unsigned char *mask,
+                                     int64_t mask_rows, int64_t mask_cols, std::string &why);
 bool plan_jfa_score(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, JfaScorePlan &p,
                     std::string &why);
 

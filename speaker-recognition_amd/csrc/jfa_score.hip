@@ -182,9 +182,8 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
     ensure_device();
     if (!plan_jfa_score(T, J, K, D, Ry, Ru, mode, (int64_t)jfa_scratch_mib() << 20, (int)jfa_lds_rows(), std::max(1, ctx().n_cu), pl, why))
         fail("%s", why.c_str());
-    const int64_t kd = (int64_t)K * D, rr = (int64_t)Ru * Ru, J1 = J + 1;
-    std::vector<double> ie((size_t)kd), nt((size_t)T);
-    for (int64_t i = 0; i < kd; i++) ie[(size_t)i] = 1.0 / E[i];
+    const int64_t kd = (int64_t)K * D;
+    std::vector<double> nt((size_t)T);
     int64_t empty = 0;
     for (int64_t t = 0; t < T; t++) {          // in mixture order: a segment's n_t does not depend on the batch
         double s = 0.0;
@@ -192,13 +191,28 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
         nt[(size_t)t] = s;
         empty += !(s > 0.0);
     }
+    auto &w = per_device<JfaScoreScratch>();
+    w.N.upload(N, (size_t)(T * K));
+    w.F.upload(F, (size_t)(T * kd));
+    w.nt.upload(nt.data(), (size_t)T);
+    jfa_score_device(pl, T, J, K, D, Ry, Ru, w.N.p, w.F.p, w.nt.p, m, E, d, v, u, z, y, x, mask, out, bad_segments);
+    if (empty_segments) *empty_segments = empty;
+}
+
+// The launches, on statistics and totals that are on the device already: the host-array entry above has just uploaded them, the
+// entries on a statistics handle (jfa_stats.hip) pass the handle's own buffers.  Synchronises before it returns.
+void jfa_score_device(const JfaScorePlan &pl, int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *dN, const double *dF,
+                      const double *d_nt, const double *m, const double *E, const double *d, const double *v, const double *u, const double *z,
+                      const double *y, const double *x, const unsigned char *mask, double *out, int64_t *bad_segments) {
+    const int mode = pl.mode;
+    const int64_t kd = (int64_t)K * D, rr = (int64_t)Ru * Ru, J1 = J + 1;
+    std::vector<double> ie((size_t)kd);
+    for (int64_t i = 0; i < kd; i++) ie[(size_t)i] = 1.0 / E[i];
     hipStream_t st = ctx().stream;
     auto &w = per_device<JfaScoreScratch>();
     const bool integrated = mode == JFA_SCORE_INTEGRATED;
     const int ubm_row = integrated ? 1 : 0;
     const int64_t rows = J + ubm_row;
-    w.N.upload(N, (size_t)(T * K));
-    w.F.upload(F, (size_t)(T * kd));
     w.m.upload(m, (size_t)kd);
     w.iE.upload(ie.data(), (size_t)kd);
     if (d) w.d.upload(d, (size_t)kd);
@@ -206,7 +220,6 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
     w.u.upload(u, (size_t)(Ru * kd));
     if (z) w.z.upload(z, (size_t)(J * kd));
     w.y.upload(y, (size_t)(J * Ry));
-    w.nt.upload(nt.data(), (size_t)T);
     w.M.ensure((size_t)(rows * kd));
     w.ME.ensure((size_t)(rows * kd));
     w.out.ensure((size_t)(J * T));
@@ -241,13 +254,13 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
         }
         for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
             const int64_t t0 = ci * pl.chunk, n = std::min(pl.chunk, T - t0);
-            const double *Nc = w.N.p + t0 * K, *Fc = w.F.p + t0 * kd;
+            const double *Nc = dN + t0 * K, *Fc = dF + t0 * kd;
             launch_gemm(T_JFA_GEMM_L, st, Nc, K, 1, w.P.p, rr, 1, w.L.p, rr, n, rr, K, false, Ru + 1);                        // L = I + N P
             launch_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.uE.p, 1, kd, w.a.p + t0 * Ru, Ru, n, Ru, kd, false, 0);                // a = F (u ./ E)^T
             launch_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.ME.p, 1, kd, w.lin.p + t0 * J1, J1, n, J1, kd, false, 0);              // lin = F (M ./ E)^T
             launch_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.q.p, 1, K, w.quad.p + t0 * J1, J1, n, J1, K, false, 0);                 // quad = N q^T
             launch_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.G.p, Ru * J1, 1, w.h.p, Ru * J1, n, Ru * J1, K, false, 0);              // h = N G
-            launch_kscore(st, pl, n, w.L.p, Ru, w.a.p, w.h.p, w.lin.p, w.quad.p, w.nt.p, J1, T, t0, w.out.p, w.flags.p);
+            launch_kscore(st, pl, n, w.L.p, Ru, w.a.p, w.h.p, w.lin.p, w.quad.p, d_nt, J1, T, t0, w.out.p, w.flags.p);
         }
         std::vector<int> host((size_t)T);
         SR_HIP(hipMemcpyAsync(host.data(), w.flags.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -260,8 +273,8 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
         launch_gemm(T_JFA_GEMM_C, st, w.x.p, Ru, 1, w.u.p, kd, 1, w.h.p, kd, T, kd, Ru, false, 0);                            // x u
         {
             ScopedKernelTimer tm(T_JFA_GRAM);
-            hipLaunchKernelGGL(jfa_compensate_kernel, dim3((unsigned)((T * kd + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, w.F.p, w.N.p, w.m.p, w.h.p,
-                               w.nt.p, T * kd, K, D);
+            hipLaunchKernelGGL(jfa_compensate_kernel, dim3((unsigned)((T * kd + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, dF, dN, w.m.p, w.h.p,
+                               d_nt, T * kd, K, D);
             SR_HIP(hipGetLastError());
         }
         launch_gemm(T_JFA_GEMM_B, st, w.ME.p, kd, 1, w.h.p, 1, kd, w.out.p, T, J, T, kd, false, 0);                           // out = (M ./ E) Fc^T
@@ -271,7 +284,6 @@ void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, con
     if (mask)
         for (int64_t i = 0; i < J * T; i++)
             if (!mask[i]) out[i] = 0.0;
-    if (empty_segments) *empty_segments = empty;
     if (bad_segments) *bad_segments = bad;
 }
 

@@ -247,7 +247,25 @@ void set_bw_range_frames(long v);
 long bw_range_frames();
 }  // namespace sr
 struct SRJfa;
+struct SRStats;
 namespace sr {
+// bw_stats.hip / jfa_stats.hip: the same passes with N and F left on the device in a statistics handle (jfa_dev.hpp); the handle's
+// life.  Every refusal comes before any device work.
+SRStats *bw_stats_resident(SRModelSet &set, int model, SRBatch &feat, double *ll_out, int64_t *dropped_out);
+SRStats *stats_from_host(int64_t n, int K, int D, const double *N, const double *F);
+void stats_info(const SRStats *s, int64_t *out, int n_out);
+void stats_get(const SRStats *s, double *N, double *F);
+SRStats *stats_take(const SRStats *s, const int64_t *rows, int64_t n_rows);
+void stats_close(SRStats *s);
+// jfa_stats.hip: grouping and centring on the device into a factor handle, what it holds, the z / d iteration on it, and the two
+// scorers on a statistics handle (jfa_plan.hpp has the formulas).
+SRJfa *jfa_open_centred(const SRStats *s, const double *E, const double *m, int mode, const int64_t *ids, int64_t n_labels, const double *d,
+                        const double *z, const double *v, int Ry, const double *y, const double *u, int Ru, const double *x);
+void jfa_statistics(SRJfa &h, double *N, double *Fc);
+void jfa_zd(SRJfa &h, double *d, int n_iter, double *z, double *a, double *b);
+void jfa_score_stats(int mode, const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d, const double *v,
+                     const double *u, const double *z, const double *y, const double *x, const unsigned char *mask, int64_t mask_rows,
+                     int64_t mask_cols, double *out, int64_t *empty_segments, int64_t *bad_segments);
 // jfa.hip: JFA factor estimation on resident statistics (eigenvoices, eigenchannels; jfa_plan.hpp has the formulas).  Every
 // refusal (jfa_plan.cpp) comes before any device work.  Host pointers throughout; W [R][K D] in / out where it says so.
 SRJfa *jfa_open(int64_t G, int K, int D, const double *N, const double *Fc, const double *E);

@@ -20,7 +20,13 @@ reference's: rows of ``F`` and ``N`` are segments, supervector columns are mixtu
 ``0`` for ``d``, ``u``, ``z``, ``y`` or ``x`` broadcasts as it does in MATLAB.  One stated difference: ``spk_ids`` are 0-BASED
 integer labels -- row i of ``y`` and ``z`` belongs to label i, rows of labels that do not occur stay zero.  Where the reference's
 ``inv`` of an unoccupied mixture's accumulator gives Inf, the update here keeps that mixture's old columns (zeros in the
-two-argument form, which has no old matrix)."""
+two-argument form, which has no old matrix).
+
+The resident route (csrc/jfa_stats.hip): ``compute_suf_stats(..., resident=True)`` returns a ``Stats`` -- N and F stay on the
+device -- and wherever a function here takes the pair ``F, N`` (or an ``(F, N)`` pair / mapping for ``trn`` / ``tst``) a ``Stats``
+in place of ``F`` with ``N=None`` keeps every [sessions, K D] array there: grouping and centring run on the device
+(``centred``), the z / d iteration too (``FactorEstimator.z_and_d``), the scorers read the handle.  Same outputs, same shapes, same
+label rules; only factors and loading matrices cross the bus.  With host arrays nothing of this is reached."""
 from __future__ import annotations
 
 import ctypes as C
@@ -44,12 +50,81 @@ def as_ubm(ubm) -> GMM:
     return GMM.from_arrays(w.reshape(-1), m, np.sqrt(v))
 
 
-def compute_suf_stats(sessions, ubm):
+def compute_suf_stats(sessions, ubm, resident=False):
     """``sessions``: a list of [T_s, D] feature matrices (or a feature ``Batch`` already on the device); ``ubm``: see ``as_ubm``.
-    -> ``N`` [n_sessions, K], ``F`` [n_sessions, K * D]: the two arrays sc_compute_suf_stats.m saves, from one device pass."""
+    -> ``N`` [n_sessions, K], ``F`` [n_sessions, K * D]: the two arrays sc_compute_suf_stats.m saves, from one device pass.
+    ``resident``: -> a ``Stats`` that holds the two on the device instead."""
     g = as_ubm(ubm)
     feats = sessions if isinstance(sessions, Batch) else Batch.from_features([np.asarray(s) for s in sessions])
+    if resident:
+        return ModelSet([g]).bw_stats(feats, 0, resident=True)
     return ModelSet([g]).bw_stats(feats, 0)
+
+
+class Stats:
+    """Raw statistics ``N`` [n, K], ``F`` [n, K * D] of n sessions on the device (sr_stats_*): from ``compute_suf_stats(...,
+    resident=True)`` / ``ModelSet.bw_stats(..., resident=True)`` or ``Stats.from_arrays``.  A context manager."""
+
+    def __init__(self, handle):
+        from . import _lib
+        self._h = handle
+        info = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().sr_stats_info(self._h, info, 4), "sr_stats_info")
+        self.n, self.K, self.D, self.device = (int(v) for v in info)
+
+    @classmethod
+    def from_arrays(cls, N, F):
+        from . import _lib
+        N = _f64(np.atleast_2d(N))
+        F = _f64(np.atleast_2d(F))
+        n, K = N.shape
+        if K < 1 or F.shape[0] != n or F.shape[1] % K:
+            raise ValueError("expected N [n, K] and F [n, K * D]; got %r and %r" % (N.shape, F.shape))
+        return cls(_lib.check(_lib.lib().sr_stats_from_host(n, K, F.shape[1] // K, _lib.as_dp(N), _lib.as_dp(F)), "sr_stats_from_host"))
+
+    def _handle(self):
+        from . import _lib
+        if self._h is None:
+            raise _lib.SRError("the statistics are closed")
+        return self._h
+
+    def get(self):
+        """-> ``(N, F)`` as host arrays."""
+        from . import _lib
+        N, F = np.zeros((self.n, self.K)), np.zeros((self.n, self.K * self.D))
+        _lib.check(_lib.lib().sr_stats_get(self._handle(), _lib.as_dp(N), _lib.as_dp(F)), "sr_stats_get")
+        return N, F
+
+    def take(self, rows):
+        """A new ``Stats`` of the rows named (any order, repeats allowed; a boolean mask of n values selects), gathered on the device."""
+        from . import _lib
+        rows = np.asarray(rows)
+        if rows.dtype == bool:
+            rows = np.flatnonzero(rows)
+        rows = np.arange(self.n)[rows] if rows.size else rows          # negative indices and slices' results as numpy reads them
+        rows = np.ascontiguousarray(rows.reshape(-1), dtype=np.int64)
+        return Stats(_lib.check(_lib.lib().sr_stats_take(self._handle(), _lib.as_i64p(rows), rows.size), "sr_stats_take"))
+
+    def close(self):
+        if self._h is not None:
+            from . import _lib
+            _lib.lib().sr_stats_close(self._h)
+            self._h = None
+
+    def __len__(self):
+        return self.n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def collect_suf_stats(data, m, v, w):
@@ -111,6 +186,40 @@ class FactorEstimator:
         self.bad_groups = self.skipped = 0
         self._h = None
         self._h = _lib.check(_lib.lib().sr_jfa_open(G, K, self.D, _lib.as_dp(N), _lib.as_dp(Fc), _lib.as_dp(E)), "sr_jfa_open")
+
+    @classmethod
+    def _adopt(cls, handle, G, K, D, present=None):
+        """An estimator around a handle the library made (``centred``)."""
+        est = cls.__new__(cls)
+        est.G, est.K, est.D = int(G), int(K), int(D)
+        est.bad_groups = est.skipped = 0
+        est.present = present
+        est._h = handle
+        return est
+
+    def statistics(self):
+        """-> ``(N [G, K], Fc [G, K * D])``: what the handle holds."""
+        from . import _lib
+        if self._h is None:
+            raise _lib.SRError("the estimator is closed")
+        N, Fc = np.zeros((self.G, self.K)), np.zeros((self.G, self.K * self.D))
+        _lib.check(_lib.lib().sr_jfa_statistics(self._h, _lib.as_dp(N), _lib.as_dp(Fc)), "sr_jfa_statistics")
+        return N, Fc
+
+    def z_and_d(self, d, n_iter=1, want_z=False):
+        """estimate_z_and_d.m on the handle's groups, ``n_iter`` rounds of ``d <- b / a`` in one device call (0: one evaluation,
+        ``d`` comes back as it went in).  -> ``(d, a, b)`` or, with ``want_z``, ``(z [G, K * D], d, a, b)``; z, a and b are the
+        last round's, for the d that round started from."""
+        from . import _lib
+        if self._h is None:
+            raise _lib.SRError("the estimator is closed")
+        kd = self.K * self.D
+        d = np.array(np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (kd,)), dtype=np.float64, order="C")
+        a, b = np.zeros(kd), np.zeros(kd)
+        z = np.zeros((self.G, kd)) if want_z else None
+        _lib.check(_lib.lib().sr_jfa_zd(self._h, _lib.as_dp(d), int(n_iter), _lib.as_dp(z) if want_z else None, _lib.as_dp(a), _lib.as_dp(b)),
+                   "sr_jfa_zd")
+        return (z, d, a, b) if want_z else (d, a, b)
 
     def _loadings(self, W):
         W = np.array(np.atleast_2d(W), dtype=np.float64, order="C")
@@ -234,10 +343,107 @@ def _finish(est, W, nargout):
     return f, A, Cm
 
 
+# ---- the resident route: grouping and centring on the device (csrc/jfa_stats.hip) ----
+
+def _absent(a):
+    return a is None or (np.ndim(a) == 0 and a == 0)
+
+
+def _term(f, W, n, kd, names):
+    """A (factor, loading) pair for the device, or (None, None) where the term is absent: either side the scalar 0, or factors
+    that are all zero (the sc_* scripts' columns of zeros)."""
+    if _absent(W) or _absent(f):
+        return None, None
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim < 2:
+        raise ValueError("%s: the resident route takes a loading matrix [R, %d] or the scalar 0" % (names[1], kd))
+    W = _f64(W)
+    if W.shape[1] != kd:
+        raise ValueError("expected %s [R, %d], got %r" % (names[1], kd, W.shape))
+    f = _f64(_rows(f, n, W.shape[0]))
+    if f.shape != (n, W.shape[0]):
+        raise ValueError("expected %s [%d, %d], got %r" % (names[0], n, W.shape[0], f.shape))
+    return (f, W) if f.any() else (None, None)
+
+
+def centred(stats, m, E, spk_ids, groups="speakers", d=0, v=0, u=0, z=0, y=0, x=0):
+    """The grouping and centring of ``estimate_*`` / ``train_*`` on the device (sr_jfa_open_centred) -> ``FactorEstimator``.
+    ``groups`` "speakers": a row per label that occurs, ascending (``.present``), ``Fc_g = sum_j (F_j - N_j (x_j u)) -
+    N_g (m + z_g d + y_g v)``; "sessions": a row per session, ``Fc_j = F_j - N_j (m + z_s d + y_s v + x_j u)``.  A term whose factor
+    or loading is the scalar 0 is absent."""
+    from . import _lib
+    if groups not in ("speakers", "sessions"):
+        raise ValueError("groups is 'speakers' or 'sessions', got %r" % (groups,))
+    if not isinstance(stats, Stats):
+        raise TypeError("centred takes a Stats (compute_suf_stats(..., resident=True) or Stats.from_arrays)")
+    n, kd = stats.n, stats.K * stats.D
+    m, E = _f64(np.reshape(m, -1), (kd,), "m"), _f64(np.reshape(E, -1), (kd,), "E")
+    ids = np.ascontiguousarray(_labels(spk_ids, n))
+    n_labels = int(ids.max()) + 1
+    y, v = _term(y, v, n_labels, kd, ("y", "v"))
+    x, u = _term(x, u, n, kd, ("x", "u"))
+    if _absent(d) or _absent(z):
+        z = d = None
+    else:
+        d = _f64(np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (kd,)))
+        z = _f64(_rows(z, n_labels, kd))
+        if not (z.any() and d.any()):
+            z = d = None
+    opt = lambda a: _lib.as_dp(a) if a is not None else None                        # noqa: E731
+    h = _lib.check(_lib.lib().sr_jfa_open_centred(stats._handle(), _lib.as_dp(E), _lib.as_dp(m), 0 if groups == "speakers" else 1, _lib.as_i64p(ids),
+                                                  n_labels, opt(d), opt(z), opt(v), v.shape[0] if v is not None else 0, opt(y), opt(u),
+                                                  u.shape[0] if u is not None else 0, opt(x)), "sr_jfa_open_centred")
+    present = np.unique(ids)
+    return FactorEstimator._adopt(h, present.size if groups == "speakers" else n, stats.K, stats.D, present)
+
+
+def _resident_y_and_v(stats, m, E, d, v, u, z, x, spk_ids, nargout):
+    W = _f64(np.atleast_2d(v))
+    with centred(stats, m, E, spk_ids, "speakers", d=d, u=u, z=z, x=x) as est:
+        f, A, Cm = _finish(est, W, nargout)
+        out = np.zeros((int(est.present.max()) + 1, W.shape[0]))
+        out[est.present] = f
+    if nargout == 1:
+        return out
+    return (out, A, Cm) if nargout == 3 else (out, update_loadings(A, Cm, W))
+
+
+def _resident_x_and_u(stats, m, E, d, v, u, z, y, spk_ids, nargout):
+    W = _f64(np.atleast_2d(u))
+    with centred(stats, m, E, spk_ids, "sessions", d=d, v=v, z=z, y=y) as est:
+        f, A, Cm = _finish(est, W, nargout)
+    if nargout == 1:
+        return f
+    return (f, A, Cm) if nargout == 3 else (f, update_loadings(A, Cm, W))
+
+
+def _resident_z_and_d(stats, m, E, d, v, u, y, x, spk_ids, nargout):
+    with centred(stats, m, E, spk_ids, "speakers", v=v, u=u, y=y, x=x) as est:
+        zg, d_new, a, b = est.z_and_d(d, n_iter=0 if nargout != 2 else 1, want_z=True)
+        zz = np.zeros((int(est.present.max()) + 1, stats.K * stats.D))
+        zz[est.present] = zg
+    if nargout == 1:
+        return zz
+    return (zz, a, b) if nargout == 3 else (zz, d_new)
+
+
+def _pair(t):
+    """``trn`` / ``tst`` as (F, N): an (F, N) pair, a mapping with those keys, or a ``Stats`` (-> (stats, None))."""
+    if isinstance(t, Stats):
+        return t, None
+    return (t["F"], t["N"]) if hasattr(t, "keys") else t
+
+
+def _n_rows(F, N):
+    return F.n if isinstance(F, Stats) else np.atleast_2d(N).shape[0]
+
+
 def estimate_y_and_v(F, N, S=None, m=None, E=None, d=0, v=None, u=0, z=0, y=0, x=0, spk_ids=None, nargout=1):
     """estimate_y_and_v.m: speaker factors ``y`` [max label + 1, R] (``nargout`` 1), ``(y, v)`` with the updated eigenvoices (2) or
     ``(y, A, C)`` with the accumulators (3); ``estimate_y_and_v(A, C)`` updates from accumulators.  Groups are speakers; the
     centring ``Fs = sum_sessions F - (m + z d) Ns - sum_j (x_j u) N_j`` is done here in float64, the rest on the device."""
+    if isinstance(F, Stats):
+        return _resident_y_and_v(F, m, E, d, v, u, z, x, spk_ids, nargout)
     if m is None:
         return update_loadings(F, N, 0.0)
     F, N, Nx, m, E = _stats(F, N, m, E)
@@ -260,6 +466,8 @@ def estimate_y_and_v(F, N, S=None, m=None, E=None, d=0, v=None, u=0, z=0, y=0, x
 def estimate_x_and_u(F, N, S=None, m=None, E=None, d=0, v=0, u=None, z=0, y=0, x=0, spk_ids=None, nargout=1):
     """estimate_x_and_u.m: channel factors ``x`` [n_sessions, R], ``(x, u)`` or ``(x, A, C)``; ``estimate_x_and_u(A, C)`` updates
     from accumulators.  Every session is its own group, ``Fh = F_j - N_j (m + y v + z d)`` with its speaker's y and z."""
+    if isinstance(F, Stats):
+        return _resident_x_and_u(F, m, E, d, v, u, z, y, spk_ids, nargout)
     if m is None:
         return update_loadings(F, N, 0.0)
     F, N, Nx, m, E = _stats(F, N, m, E)
@@ -279,6 +487,8 @@ def estimate_x_and_u(F, N, S=None, m=None, E=None, d=0, v=0, u=None, z=0, y=0, x
 def estimate_z_and_d(F, N, S=None, m=None, E=None, d=0, v=0, u=0, z=0, y=0, x=0, spk_ids=None, nargout=1):
     """estimate_z_and_d.m on the host in float64: ``z`` [max label + 1, K * D], ``(z, d)`` or ``(z, a, b)``;
     ``estimate_z_and_d(a, b)`` gives ``d = b / a``."""
+    if isinstance(F, Stats):
+        return _resident_z_and_d(F, m, E, d, v, u, y, x, spk_ids, nargout)
     if m is None:
         return np.asarray(N, dtype=np.float64) / np.asarray(F, dtype=np.float64)
     F, N, Nx, m, E = _stats(F, N, m, E)
@@ -303,6 +513,8 @@ def estimate_z_and_d(F, N, S=None, m=None, E=None, d=0, v=0, u=0, z=0, y=0, x=0,
 def linear_scoring(F, N, S=None, m=None, E=None, d=0, v=0, u=0, z=0, y=0, x=0, scores=None):
     """linear_scoring.m on the host in float64: -> [n_models, n_segments], the models ``z d + y v`` divided by E against the
     channel-compensated, count-normalised first-order statistics of the segments."""
+    if isinstance(F, Stats):
+        return score_trials(F, None, m, E, d, v, u, z, y, _f64(_rows(x, F.n, np.atleast_2d(u).shape[0])), mode="linear")
     F, N, Nx, m, E = _stats(F, N, m, E)
     n, kd = F.shape
     y = np.atleast_2d(np.asarray(y, dtype=np.float64))
@@ -335,6 +547,10 @@ def random_loadings(n_rows, E, seed=0):
 def train_v(F, N, spk_ids, ubm, ny=300, niter=10, v0=None, seed=0):
     """sc_train_v_from_files.m: ``niter`` rounds of ``[y, v] = estimate_y_and_v(F, N, S, m, E, 0, v, 0, 0, 0, 0, spk_ids)`` from the
     random start (or ``v0``), as ONE device call.  -> v [ny, K * D]."""
+    if isinstance(F, Stats):
+        m, E = _ubm_m_E(ubm)
+        with centred(F, m, E, spk_ids, "speakers") as est:
+            return est.train(random_loadings(ny, E, seed) if v0 is None else v0, niter)[0]
     m, E = _ubm_m_E(ubm)
     F, N, Nx, m, E = _stats(F, N, m, E)
     ids = _labels(spk_ids, F.shape[0])
@@ -350,6 +566,11 @@ def train_v(F, N, spk_ids, ubm, ny=300, niter=10, v0=None, seed=0):
 def train_u(F, N, spk_ids, ubm, v, nx=300, niter=10, u0=None, seed=0):
     """sc_train_u_from_files.m: y once from ``v``, then ``niter`` rounds of ``[x, u] = estimate_x_and_u(...)`` with that y fixed, as
     one device call.  -> u [nx, K * D]."""
+    if isinstance(F, Stats):
+        m, E = _ubm_m_E(ubm)
+        y = estimate_y_and_v(F, None, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
+        with centred(F, m, E, spk_ids, "sessions", v=v, y=y) as est:
+            return est.train(random_loadings(nx, E, seed) if u0 is None else u0, niter)[0]
     m, E = _ubm_m_E(ubm)
     y = estimate_y_and_v(F, N, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
     F, N, Nx, m, E = _stats(F, N, m, E)
@@ -362,6 +583,13 @@ def train_u(F, N, spk_ids, ubm, v, nx=300, niter=10, u0=None, seed=0):
 
 def train_d(F, N, spk_ids, ubm, v, u, niter=10, d0=None, seed=0):
     """sc_train_d_from_files.m: y and x once, then ``niter`` rounds of ``[z, d] = estimate_z_and_d(...)`` (host).  -> d [K * D]."""
+    if isinstance(F, Stats):
+        m, E = _ubm_m_E(ubm)
+        y = estimate_y_and_v(F, None, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
+        x = estimate_x_and_u(F, None, None, m, E, 0, v, u, 0, y, 0, spk_ids)
+        d = random_loadings(1, E, seed)[0] if d0 is None else np.asarray(d0, dtype=np.float64).reshape(-1)
+        with centred(F, m, E, spk_ids, "speakers", v=v, u=u, y=y, x=x) as est:       # Fc_g does not depend on d: centred once
+            return est.z_and_d(d, n_iter=int(niter))[0]
     m, E = _ubm_m_E(ubm)
     y = estimate_y_and_v(F, N, None, m, E, 0, v, 0, 0, 0, 0, spk_ids)
     x = estimate_x_and_u(F, N, None, m, E, 0, v, u, 0, y, 0, spk_ids)
@@ -376,14 +604,14 @@ def score_dot_product(trn, tst, ubm, v, u, d):
     segments' channel factors against the UBM, then ``linear_scoring``.  ``trn`` / ``tst``: ``(F, N)`` pairs or mappings with
     those keys.  -> scores [n_enrolment, n_test]."""
     m, E = _ubm_m_E(ubm)
-    tF, tN = (trn["F"], trn["N"]) if hasattr(trn, "keys") else trn
-    sF, sN = (tst["F"], tst["N"]) if hasattr(tst, "keys") else tst
+    tF, tN = _pair(trn)
+    sF, sN = _pair(tst)
     v = _f64(np.atleast_2d(v))
     u = _f64(np.atleast_2d(u))
     ny = v.shape[0]
     vu = np.vstack([v, u])
-    trn_ids = np.arange(np.atleast_2d(tN).shape[0])
-    tst_ids = np.arange(np.atleast_2d(sN).shape[0])
+    trn_ids = np.arange(_n_rows(tF, tN))
+    tst_ids = np.arange(_n_rows(sF, sN))
     yx = estimate_y_and_v(tF, tN, None, m, E, d, vu, 0, 0, 0, 0, trn_ids)
     trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
     tst_x = estimate_x_and_u(sF, sN, None, m, E, d, v, u, 0, 0, 0, tst_ids)
@@ -402,12 +630,16 @@ def score_trials(F, N, m, E, d, v, u, z, y, x=None, mode="integrated", mask=None
     from . import _lib
     if mode not in ("integrated", "linear"):
         raise ValueError("mode is 'integrated' or 'linear', got %r" % (mode,))
-    F = _f64(np.atleast_2d(F))
-    N = _f64(np.atleast_2d(N))
-    T, K = N.shape
-    if K < 1 or F.shape[0] != T or F.shape[1] % K:
-        raise ValueError("expected N [T, K] and F [T, K * D]; got %r and %r" % (N.shape, F.shape))
-    kd = F.shape[1]
+    stats = F if isinstance(F, Stats) else None
+    if stats is not None:
+        T, K, kd = stats.n, stats.K, stats.K * stats.D
+    else:
+        F = _f64(np.atleast_2d(F))
+        N = _f64(np.atleast_2d(N))
+        T, K = N.shape
+        if K < 1 or F.shape[0] != T or F.shape[1] % K:
+            raise ValueError("expected N [T, K] and F [T, K * D]; got %r and %r" % (N.shape, F.shape))
+        kd = F.shape[1]
     m, E = _f64(np.reshape(m, -1), (kd,), "m"), _f64(np.reshape(E, -1), (kd,), "E")
     v = _f64(np.atleast_2d(v))
     u = _f64(np.atleast_2d(u))
@@ -433,6 +665,14 @@ def score_trials(F, N, m, E, d, v, u, z, y, x=None, mode="integrated", mask=None
     empty, bad = C.c_int64(0), C.c_int64(0)
     opt = lambda a: _lib.as_dp(a) if a is not None else None                        # noqa: E731
     mk = (mask.ctypes.data_as(C.POINTER(C.c_uint8)), J, T) if mask is not None else (None, 0, 0)
+    if stats is not None:
+        head = (stats._handle(), J, v.shape[0], u.shape[0], _lib.as_dp(m), _lib.as_dp(E), opt(d), _lib.as_dp(v), _lib.as_dp(u), opt(z), _lib.as_dp(y))
+        if mode == "integrated":
+            _lib.check(_lib.lib().sr_jfa_score_integrated_stats(*head, *mk, _lib.as_dp(out), C.byref(empty), C.byref(bad)),
+                       "sr_jfa_score_integrated_stats")
+        else:
+            _lib.check(_lib.lib().sr_jfa_score_linear_stats(*head, opt(x), *mk, _lib.as_dp(out), C.byref(empty)), "sr_jfa_score_linear_stats")
+        return (out, {"empty_segments": int(empty.value), "bad_segments": int(bad.value)}) if return_counts else out
     head = (T, J, K, kd // K, v.shape[0], u.shape[0], _lib.as_dp(N), _lib.as_dp(F), _lib.as_dp(m), _lib.as_dp(E), opt(d), _lib.as_dp(v),
             _lib.as_dp(u), opt(z), _lib.as_dp(y))
     if mode == "integrated":
@@ -453,6 +693,9 @@ def kscore_famous_19(F, N, S=None, m=None, E=None, d=0, v=None, u=None, z=0, y=N
     zt = None if (np.ndim(z) == 0 and z == 0) else np.reshape(np.asarray(z, dtype=np.float64), (-1, J)).T
     dv = None if (np.ndim(d) == 0 and d == 0) else np.reshape(d, -1)
     mask = None if scores is None else np.asarray(scores) == 1
+    if isinstance(F, Stats):                                                         # (a handle has one orientation: rows are segments)
+        return score_trials(F, None, np.reshape(m, -1), np.reshape(E, -1), dv, np.atleast_2d(np.asarray(v, dtype=np.float64)).T,
+                            np.atleast_2d(np.asarray(u, dtype=np.float64)).T, zt, y.T, mode="integrated", mask=mask)
     return score_trials(np.atleast_2d(np.asarray(F, dtype=np.float64)).T, np.atleast_2d(np.asarray(N, dtype=np.float64)).T, np.reshape(m, -1),
                         np.reshape(E, -1), dv, np.atleast_2d(np.asarray(v, dtype=np.float64)).T, np.atleast_2d(np.asarray(u, dtype=np.float64)).T,
                         zt, y.T, mode="integrated", mask=mask)
@@ -463,13 +706,13 @@ def score_integrated(trn, tst, ubm, v, u, d):
     on the stacked [v; u], then z), scored against the test segments' raw statistics by the integrated scorer -- no point estimate
     of the test segments' channel factors.  -> scores [n_enrolment, n_test]."""
     m, E = _ubm_m_E(ubm)
-    tF, tN = (trn["F"], trn["N"]) if hasattr(trn, "keys") else trn
-    sF, sN = (tst["F"], tst["N"]) if hasattr(tst, "keys") else tst
+    tF, tN = _pair(trn)
+    sF, sN = _pair(tst)
     v = _f64(np.atleast_2d(v))
     u = _f64(np.atleast_2d(u))
     ny = v.shape[0]
     vu = np.vstack([v, u])
-    trn_ids = np.arange(np.atleast_2d(tN).shape[0])
+    trn_ids = np.arange(_n_rows(tF, tN))
     yx = estimate_y_and_v(tF, tN, None, m, E, d, vu, 0, 0, 0, 0, trn_ids)
     trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
     return score_trials(sF, sN, m, E, d, v, u, trn_z, yx[:, :ny], mode="integrated")
