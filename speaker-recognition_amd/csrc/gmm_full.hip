@@ -211,6 +211,7 @@ void fullcov_finalize_kernel(const float *__restrict__ fll, long n, const int64_
 // ---------------------------------------------------------------- training (float64)
 constexpr int FE_FB = 32;          // frames of a density workgroup
 constexpr int FE_PQ = 9;           // covariance pairs per thread: 9 x 256 >= 64 x 65 / 2
+static_assert(FE_PQ * 256 >= FULL_MAX_D * (FULL_MAX_D + 1) / 2, "fe_cov: 256 threads x FE_PQ slots must hold the upper triangle at FULL_MAX_D");
 constexpr int FE_CB = 32;          // frames staged per covariance step
 
 struct FeArgs {
