@@ -396,6 +396,8 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    up to whole tiles of 128)).  Results depend on it in their last bits only.
  *   "jfa_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the R x R float64 blocks sr_jfa_factors / _train keep at a time:
  *                    the groups run in chunks that fit.  Results do not depend on it, bit for bit.
+ *   "norm_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the scratch of sr_score_norm's as2 mode (the selections, the shifted
+ *                    copies and the four products): the test segments run in chunks that fit.  Results do not depend on it, bit for bit.
  *   "jfa_lds_rows"   largest R whose blocks the JFA factorisation copies into LDS (1 .. 112; 0 = automatic: 112); above it the
  *                    block is factored in place in global memory with panels in LDS.  1 forces that path at any R > 1.
  * The rest select kernel variants for A/B runs and tests. */
@@ -763,6 +765,57 @@ int sr_jfa_score_linear_stats(const SRStats *tst, int64_t J, int Ry, int Ru, con
                               const double *v, const double *u, const double *z /*or NULL*/, const double *y, const double *x /*[T][Ru]*/,
                               const unsigned char *mask /*or NULL*/, int64_t mask_rows, int64_t mask_cols, double *out /*[J][T]*/,
                               int64_t *empty_segments /*or NULL*/);
+
+/* ---- Score normalisation (csrc/score_norm.hip, csrc/norm_plan.cpp): a score matrix S [J][T] (models x test segments) normalised
+ * against impostor cohorts on the device, float64 throughout, row-major.  Ez [J][Cz]: the models against the Z-cohort (impostor
+ * segments); Tt [Ct][T]: the T-cohort models against the test segments; Zt [Ct][Cz]: the T-cohort models against the Z-cohort.  A
+ * matrix the mode does not read is NULL (its cohort size is ignored).  mu / sigma: the mean and the population standard deviation
+ * (ddof = 0); "top-N of a row": the N largest values, ties to the lower index, -0.0 taken as +0.0.  mode:
+ *   0 z    (S - mu(Ez[j,:])) / sigma(Ez[j,:])                 1 t    (S - mu(Tt[:,t])) / sigma(Tt[:,t])
+ *   2 zt   S' = z-norm of S by Ez; Tt' = z-norm of Tt by Zt, row c of Tt by row c of Zt; out = t-norm of S' by Tt'
+ *   3 s    (z + t) / 2                                        4 as1  as s, the moments over the top-N of Ez[j,:] and of Tt[:,t]
+ *   5 as2  Cz = Ct = C, cohort member c both a segment and a model; I_t = the top-N of Tt[:,t], I_j = the top-N of Ez[j,:]:
+ *          ((S - mu(Ez[j,I_t])) / sigma(Ez[j,I_t]) + (S - mu(Tt[I_j,t])) / sigma(Tt[I_j,t])) / 2
+ * top_n >= 2 in the adaptive modes (ignored in the others); top_n >= C selects everything.
+ * THE BUILT LIMIT: a cohort of at most 16384 members (Cz, Ct, C <= 16384): norm_select_moments_kernel keeps a cohort row in LDS as 64-bit
+ * keys next to its 256-bin histogram, 128 KiB + 1 KiB + 96 B of a gfx950 compute unit's 160 KiB.  At most 65535 * 64 models or test
+ * segments and 2^36 trials a call.
+ * One workgroup per cohort row finds the N-th largest value by radix select on the order-preserving 64-bit key of the double (eight
+ * 8-bit passes over an LDS histogram, no sort), resolves ties at the threshold by a prefix count in index order, and sums the moments
+ * of the selected values in an order that depends on the selected set only; a column of Tt is read with stride T.  as2's sums over
+ * the other side's selection are four products on v_mfma_f64_16x16x4_f64 through the GEMM kernel of sr_jfa_factors:
+ * Es SelT^T, (Es .* Es) SelT^T, SelE Ts, SelE (Ts .* Ts), with SelT [T][C] / SelE [J][C] the 0/1 selections and Es = Ez - mu(Ez[j,:]),
+ * Ts = Tt - mu(Tt[:,t]) shifted by the full row's / column's mean.  A pair whose variance the products cannot tell from 0 (not above
+ * 2^-30 of the mean square about the shift: a selected set that is constant, or nearly, in a row that is not) takes its moments from
+ * the selected values themselves, relative to the first of them, so that a constant set is degenerate exactly.  That scratch lives under "norm_scratch_mib": the test segments run
+ * in chunks that fit.  No atomics on global memory and no float atomics: a score is the same bits under any bound and from run to run;
+ * a row's selection and moments are the same bits alone and in any batch.
+ * Degenerate pairs: a moment pair whose variance is not > 0 or not finite (a constant cohort row; a cohort of one).  Every trial that
+ * needs it gets 0.0 exactly; no NaN is ever written.  degenerate (or NULL) [2]: the pairs of the enrolment side (Ez) and of the test
+ * side (Tt; in zt the columns of Tt' plus the rows of Zt, whose rows of Tt' are zeros) -- rows / columns in modes 0 .. 4, (model,
+ * segment) pairs in as2.
+ * sr_score_norm_select: the selection stage alone on X [rows][C]: idx [rows][min(top_n, C)] the selected indices of each row,
+ * ascending, mu / sigma [rows] the moments of the selected values (sigma 0.0: degenerate).  Each output may be NULL.
+ * sr_score_norm_plan: what a call decides (csrc/norm_plan.cpp; host only when n_cu > 0), for tests.  Writes 40 fields (n_out >= 40)
+ * and returns 40, -1 on refusal: mode, values per moment pair on the enrolment and on the test side, test segments per chunk, chunks;
+ * as2's bytes inside the bound: once per call (3 J C doubles), per test segment (3 C + 4 J doubles), of a full chunk with the fixed
+ * part; bytes of S, Ez, Tt, Zt, out, the moments with their flags, zt's Tt', as2's counters; workgroups of the selection over Ez, over
+ * a chunk of Tt, over Zt; its LDS bytes on either side; the grids of the two shifted copies, of the products Es SelT^T (x, y) and
+ * SelE Ts (x, y), the GEMM's LDS bytes, the apply kernel's grid (x = models, y = blocks of 256 segments); rounds of the largest
+ * selection launch over the chip; the built limits of C and of J / T; lanes per workgroup; six zeros.
+ * Refused, before the device is touched, with a message that names the argument and the remedy: a mode outside 0 .. 5, J or T < 1 or
+ * above the limits, a cohort of no members or above the built limit, top_n < 2 in an adaptive mode, as2 with Cz != Ct, a matrix the
+ * mode needs missing, a non-finite value anywhere, a bound below one chunk.  Refused in a process forked after the GPU runtime was
+ * initialised.
+ * Timer kinds (none is added): SR_T_JFA_FACTOR the selection kernel; SR_T_JFA_GRAM the shifted copies; SR_T_JFA_GEMM_A the two products
+ * with SelT; SR_T_JFA_GEMM_B the two with SelE; SR_T_JFA_UPDATE the apply kernel. */
+int sr_score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, const double *S /*[J][T]*/, const double *Ez /*[J][Cz] or NULL*/,
+                  const double *Tt /*[Ct][T] or NULL*/, const double *Zt /*[Ct][Cz] or NULL*/, double *out /*[J][T]*/,
+                  int64_t *degenerate /*[2] or NULL*/);
+int sr_score_norm_select(int64_t rows, int64_t C, int top_n, const double *X /*[rows][C]*/, int64_t *idx /*[rows][min(top_n,C)] or NULL*/,
+                         double *mu /*[rows] or NULL*/, double *sigma /*[rows] or NULL*/);
+int sr_score_norm_plan(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, int64_t scratch_bytes, int n_cu, int64_t *out,
+                       int n_out);
 
 #ifdef __cplusplus
 }

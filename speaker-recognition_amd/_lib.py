@@ -48,6 +48,7 @@ EXT_SYMBOLS = [
     "sr_jfa_open_centred", "sr_jfa_statistics", "sr_jfa_centre_plan", "sr_jfa_zd", "sr_jfa_score_integrated_stats", "sr_jfa_score_linear_stats",
     "sr_multi_slot_pieces", "sr_multi_plan",
     "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
+    "sr_score_norm", "sr_score_norm_select", "sr_score_norm_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -248,6 +249,9 @@ def lib():
         "sr_map_fit_batch_bytes": (C.c_long, []),
         "sr_map_fit_plan": (i32, [i32, i32, C.POINTER(i64), i32, C.POINTER(Parameter), i64, i32, C.POINTER(i64), C.POINTER(i64), i64,
                                   C.POINTER(i64), i64, C.POINTER(i64), i64, C.POINTER(i64), i32]),
+        "sr_score_norm": (i32, [i32, i64, i64, i64, i64, i32, dp, dp, dp, dp, dp, C.POINTER(i64)]),
+        "sr_score_norm_select": (i32, [i64, i64, i32, dp, C.POINTER(i64), dp, dp]),
+        "sr_score_norm_plan": (i32, [i32, i64, i64, i64, i64, i32, i64, i32, C.POINTER(i64), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -544,6 +548,25 @@ def jfa_score_plan(T: int, J: int, K: int, D: int, Ry: int, Ru: int, mode: str =
     d = dict(zip(JFA_SCORE_PLAN_FIELDS, (int(x) for x in v)))
     d["path"] = ("lds", "global")[d["path"]]
     d["mode"] = ("integrated", "linear")[d["mode"]]
+    return d
+
+
+NORM_MODES = ("z", "t", "zt", "s", "as1", "as2")
+NORM_PLAN_FIELDS = ("mode", "n_sel", "n_sel_test", "chunk", "n_chunks", "fixed_bytes", "seg_bytes", "bytes_scratch", "bytes_S", "bytes_Ez",
+                    "bytes_Tt", "bytes_Zt", "bytes_out", "bytes_moments", "bytes_tnorm", "bytes_counts", "select_enrol_grid", "select_test_grid",
+                    "select_zt_grid", "select_lds_enrol", "select_lds_test", "shift_enrol_grid", "shift_test_grid", "gemm_enrol_x", "gemm_enrol_y",
+                    "gemm_test_x", "gemm_test_y", "gemm_lds", "apply_x", "apply_y", "select_rounds", "max_C", "max_rows", "workgroup")
+
+
+def score_norm_plan(mode: str, J: int, T: int, Cz: int, Ct: int, top_n: int = 0, scratch_bytes: int = 1 << 30, n_cu: int = 256) -> dict:
+    """What ``sr_score_norm`` decides for a J x T score matrix, cohorts of Cz and Ct members and a scratch bound (csrc/norm_plan.cpp;
+    no GPU needed when n_cu > 0): the refusals, the values per moment pair, test segments per chunk and chunks (as2), the bytes of
+    every array inside and outside the bound, the grid of every launch, the selection kernel's LDS bytes and the built limits."""
+    v = (C.c_int64 * 40)()
+    m = NORM_MODES.index(mode) if mode in NORM_MODES else -1
+    check(lib().sr_score_norm_plan(m, int(J), int(T), int(Cz), int(Ct), int(top_n), int(scratch_bytes), int(n_cu), v, 40), "sr_score_norm_plan")
+    d = dict(zip(NORM_PLAN_FIELDS, (int(x) for x in v)))
+    d["mode"] = NORM_MODES[d["mode"]]
     return d
 
 

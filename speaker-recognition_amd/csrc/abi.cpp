@@ -15,6 +15,7 @@
 #include "topc_plan.hpp"
 #include "bw_plan.hpp"
 #include "jfa_plan.hpp"
+#include "norm_plan.hpp"
 #include "map_plan.hpp"
 
 #include <algorithm>
@@ -40,6 +41,12 @@ int map_fit_batch(GMM *const *models, int S, const GMM *ubm, const float *X, con
 void map_fit_batch_stats(long *calls, long *speakers_batched, long *speakers_single, long *speakers_handed_over, long *passes);
 void set_map_fit_batch_bytes(long v);
 long map_fit_batch_bytes();
+// score_norm.hip
+void score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, const double *S, const double *Ez, const double *Tt,
+                const double *Zt, double *out, int64_t *degenerate);
+void score_norm_select(int64_t rows, int64_t C, int top_n, const double *X, int64_t *idx, double *mu, double *sigma);
+void set_norm_scratch_mib(long v);
+long norm_scratch_mib();
 // silence.hip
 void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
 void set_silence_block(long v);
@@ -1218,6 +1225,47 @@ int sr_jfa_score_plan(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mo
     SR_CATCH(-1)
 }
 
+// ---- score normalisation (score_norm.hip).  Every refusal comes before the device is touched. ----
+
+int sr_score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, const double *S, const double *Ez, const double *Tt,
+                  const double *Zt, double *out, int64_t *degenerate) {
+    SR_TRY
+    score_norm(mode, J, T, Cz, Ct, top_n, S, Ez, Tt, Zt, out, degenerate);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_score_norm_select(int64_t rows, int64_t C, int top_n, const double *X, int64_t *idx, double *mu, double *sigma) {
+    SR_TRY
+    score_norm_select(rows, C, top_n, X, idx, mu, sigma);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_score_norm_plan(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, int64_t scratch_bytes, int n_cu, int64_t *out,
+                       int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 40) fail("sr_score_norm_plan writes 40 fields");
+    std::string why;
+    NormPlan p;
+    if (n_cu > 0) {
+        if (!plan_score_norm(mode, J, T, Cz, Ct, top_n, scratch_bytes, n_cu, p, why)) fail("%s", why.c_str());
+    } else {
+        if (!plan_score_norm(mode, J, T, Cz, Ct, top_n, scratch_bytes, 1, p, why)) fail("%s", why.c_str());      // the refusals first
+        ensure_device();
+        if (!plan_score_norm(mode, J, T, Cz, Ct, top_n, scratch_bytes, ctx().n_cu, p, why)) fail("%s", why.c_str());
+    }
+    const int64_t v[40] = {p.mode, p.n_sel, p.n_sel_test, p.chunk, p.n_chunks, p.fixed_bytes, p.seg_bytes, p.bytes_scratch, p.bytes_S, p.bytes_Ez,
+                           p.bytes_Tt, p.bytes_Zt, p.bytes_out, p.bytes_moments, p.bytes_tnorm, p.bytes_counts, p.select_enrol.x, p.select_test.x,
+                           p.select_zt.x, p.select_lds_enrol, p.select_lds_test, p.shift_enrol.x, p.shift_test.x, p.gemm_enrol.x, p.gemm_enrol.y,
+                           p.gemm_test.x, p.gemm_test.y, p.gemm_lds, p.apply.x, p.apply.y, p.select_rounds, NORM_MAX_C, NORM_MAX_ROWS, NORM_WG,
+                           0, 0, 0, 0, 0, 0};
+    std::memcpy(out, v, sizeof v);
+    return 40;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY
@@ -1389,6 +1437,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "jfa_scratch_mib") {
         if (value < 1 || value > (1L << 20)) fail("jfa_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(JFA_DEFAULT_SCRATCH >> 20));
         set_jfa_scratch_mib(value);
+    } else if (k == "norm_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("norm_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(NORM_DEFAULT_SCRATCH >> 20));
+        set_norm_scratch_mib(value);
     } else if (k == "jfa_lds_rows") {
         if (value < 0 || value > JFA_LDS_MAX_R) fail("jfa_lds_rows must be 0 (automatic) or 1 .. %d rows", JFA_LDS_MAX_R);
         set_jfa_lds_rows(value);

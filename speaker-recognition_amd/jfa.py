@@ -716,3 +716,22 @@ def score_integrated(trn, tst, ubm, v, u, d):
     yx = estimate_y_and_v(tF, tN, None, m, E, d, vu, 0, 0, 0, 0, trn_ids)
     trn_z = estimate_z_and_d(tF, tN, None, m, E, d, vu, 0, 0, yx, 0, trn_ids)
     return score_trials(sF, sN, m, E, d, v, u, trn_z, yx[:, :ny], mode="integrated")
+
+
+def score_normalised(trn, tst, cohort, ubm, v, u, d, norm="as2", top_n=200, scorer="integrated", return_counts=False):
+    """A verification run's normalised score matrix [n_enrolment, n_test]: the ``cohort`` segments (impostors; an ``(F, N)`` pair, a
+    mapping or a ``Stats`` as ``trn`` and ``tst``) are enrolled as models AND used as segments, the matrices the mode needs -- (trn,
+    tst), (trn, cohort), (cohort, tst) and, for "zt", (cohort, cohort) -- come from ``score_integrated`` (``scorer`` "integrated") or
+    ``score_dot_product`` ("dot_product"), and ``scorenorm.normalise`` is applied to them.  ``norm``: "z", "t", "zt", "s", "as1" or
+    "as2"; ``top_n``: the adaptive modes' N."""
+    from . import scorenorm
+    if scorer not in ("integrated", "dot_product"):
+        raise ValueError("scorer is 'integrated' or 'dot_product', got %r" % (scorer,))
+    if norm not in scorenorm.MODES:
+        raise ValueError("norm is one of %s, got %r" % (", ".join(repr(m) for m in scorenorm.MODES), norm))
+    score = score_integrated if scorer == "integrated" else score_dot_product
+    S = score(trn, tst, ubm, v, u, d)
+    Ez = score(trn, cohort, ubm, v, u, d) if norm != "t" else None
+    Tt = score(cohort, tst, ubm, v, u, d) if norm != "z" else None
+    Zt = score(cohort, cohort, ubm, v, u, d) if norm == "zt" else None
+    return scorenorm.normalise(S, norm, Ez, Tt, Zt, top_n=top_n if norm in ("as1", "as2") else None, return_counts=return_counts)
