@@ -481,6 +481,17 @@ const char *sr_fullgmm_fit_batch_error(int s);
 void sr_full_fit_batch_stats(long *calls, long *speakers, long *iterations);
 /* The current value of the option "full_fit_batch_bytes". */
 long sr_full_fit_batch_bytes(void);
+/* What a fit of S speakers of `lengths` frames decides before it touches the device (csrc/full_plan.cpp; no device is touched),
+ * for tests.  init_given / max_iter: [S], or NULL (the k-means start / 100).  bound_bytes: 0 means the current
+ * "full_fit_batch_bytes".  out [7]: groups, the lengths of the three work lists (density blocks of 32 frames, 256-frame blocks,
+ * covariance chunks) over all groups, the LDS bytes of the density kernel, the largest group's workspace bytes, the workspace bytes
+ * of a lone speaker of lengths[0] frames.  speakers_out [S][8] (may be NULL): frames, first row in its group, covariance chunks,
+ * frames per chunk, offset of its slice of `partial` (doubles), its bytes alone, group, slot.  groups_out [group_cap][28] (may be
+ * NULL): first speaker, speakers, rows, where its ranges of the three lists start, max_iter, any k-means start, any given start,
+ * bytes, then the element counts of X, w, logw, mu, prec, logdet, cov, lp, lpn, nk, partial, head, the speaker table, the records,
+ * the three lists and the labels.  Returns 7, or -1 with the reason. */
+int sr_full_fit_plan(int K, int D, const int64_t *lengths, const int *init_given, const int *max_iter, int S, int64_t bound_bytes,
+                     int64_t *speakers_out, int64_t *groups_out, int64_t group_cap, int64_t *out, int n_out);
 /* K and D of a handle; 1 when it has parameters, 0 when not, -1 on error.  Either pointer may be NULL. */
 int sr_fullgmm_info(SRFullGMM *g, int *K, int *D);
 /* Copies the parameters out; any pointer may be NULL.  covariances: the last M-step's (zeros for a model built from arrays). */

@@ -37,6 +37,7 @@ EXT_SYMBOLS = [
     "sr_fullset_score_batch", "sr_fullset_free", "sr_fullset_predict_pcm_batch", "sr_stream_create_full", "sr_multi_create_full",
     "sr_stream_create_vad", "sr_stream_collect_vad",
     "sr_fullgmm_fit_batch", "sr_fullgmm_fit_batch_error", "sr_full_fit_batch_stats", "sr_full_fit_batch_bytes",
+    "sr_full_fit_plan",
     "sr_open_set_decide", "sr_score_batch_set_open", "sr_predict_pcm_batch_open", "sr_stream_set_open", "sr_stream_collect_open",
     "sr_multi_predict_pcm_open",
     "sr_batch_download_pcm16", "sr_silence_remove_batch", "sr_silence_plan",
@@ -193,6 +194,8 @@ def lib():
         "sr_fullgmm_fit_batch_error": (C.c_char_p, [i32]),
         "sr_full_fit_batch_stats": (None, [C.POINTER(C.c_long)] * 3),
         "sr_full_fit_batch_bytes": (C.c_long, []),
+        "sr_full_fit_plan": (i32, [i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), i32, i64, C.POINTER(i64), C.POINTER(i64), i64,
+                                   C.POINTER(i64), i32]),
         "sr_fullgmm_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "sr_fullgmm_get": (i32, [vp, dp, dp, dp, dp]),
         "sr_fullgmm_free": (None, [vp]),
@@ -382,6 +385,29 @@ def full_fit_batch_stats():
 def full_fit_batch_bytes() -> int:
     """The current value of the option ``full_fit_batch_bytes``."""
     return int(lib().sr_full_fit_batch_bytes())
+
+
+def full_fit_plan(K: int, D: int, lengths, init_given=None, max_iter=None, bound_bytes: int = 0) -> dict:
+    """What a full-covariance fit of speakers of ``lengths`` frames decides before it touches the device (csrc/full_plan.cpp; no GPU
+    needed): ``n_groups``, the lengths of the three work lists ``n_lp`` / ``n_lse`` / ``n_cov``, ``lds_logprob``, ``max_group_bytes``,
+    ``lone_bytes`` (a speaker of ``lengths[0]`` frames alone); ``speakers`` [S, 8] = (frames, first row in its group, covariance
+    chunks, frames per chunk, offset into ``partial``, bytes alone, group, slot); ``groups`` [G, 28] = (first speaker, speakers, rows,
+    the three list ranges' starts, max_iter, any k-means start, any given start, bytes, then the 18 buffers' element counts).
+    ``bound_bytes`` 0: the current ``full_fit_batch_bytes``."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    S = len(lengths)
+    given = None if init_given is None else np.ascontiguousarray(init_given, dtype=np.int32)
+    iters = None if max_iter is None else np.ascontiguousarray(max_iter, dtype=np.int32)
+    as_ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    v = (C.c_int64 * 7)()
+    spk = np.zeros((max(S, 1), 8), dtype=np.int64)
+    args = (int(K), int(D), as_i64p(lengths), as_ip(given), as_ip(iters), S, int(bound_bytes))
+    check(lib().sr_full_fit_plan(*args, as_i64p(spk), None, 0, v, 7), "sr_full_fit_plan")
+    d = dict(zip(("n_groups", "n_lp", "n_lse", "n_cov", "lds_logprob", "max_group_bytes", "lone_bytes"), (int(x) for x in v)))
+    groups = np.zeros((max(d["n_groups"], 1), 28), dtype=np.int64)
+    check(lib().sr_full_fit_plan(*args, None, as_i64p(groups), d["n_groups"], v, 7), "sr_full_fit_plan")
+    d.update(speakers=spk[:S], groups=groups[:d["n_groups"]])
+    return d
 
 
 def map_fit_batch_stats():

@@ -1563,6 +1563,41 @@ void sr_full_fit_batch_stats(long *calls, long *speakers, long *iterations) { fu
 
 long sr_full_fit_batch_bytes(void) { return full_fit_batch_bytes(); }
 
+int sr_full_fit_plan(int K, int D, const int64_t *lengths, const int *init_given, const int *max_iter, int S, int64_t bound_bytes,
+                     int64_t *speakers_out, int64_t *groups_out, int64_t group_cap, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out || !lengths) fail("null argument");
+    if (n_out < 7) fail("sr_full_fit_plan writes 7 fields");
+    if (S < 1) fail("a plan needs at least one speaker (S = %d)", S);
+    std::vector<int> given((size_t)S, 0), iters((size_t)S, 100);
+    if (init_given) given.assign(init_given, init_given + S);
+    if (max_iter) iters.assign(max_iter, max_iter + S);
+    FullFitPlan p;
+    std::string why;
+    if (!plan_full_fit(K, D, lengths, given.data(), iters.data(), S, bound_bytes == 0 ? (int64_t)full_fit_batch_bytes() : bound_bytes, p, why))
+        fail("%s", why.c_str());
+    const int64_t v[7] = {(int64_t)p.groups.size(), (int64_t)p.wl_lp.size(), (int64_t)p.wl_lse.size(), (int64_t)p.wl_cov.size(),
+                          (int64_t)p.lds_logprob, p.max_group_bytes, full_speaker_bytes(K, D, lengths[0])};
+    std::memcpy(out, v, sizeof v);
+    if (speakers_out)
+        for (int s = 0; s < S; s++) {
+            const FullSpeakerPlan &sp = p.speakers[(size_t)s];
+            const int64_t r[8] = {sp.n, sp.row0, sp.n_chunks, sp.chunk, sp.o_partial, sp.bytes, sp.group, sp.slot};
+            std::memcpy(speakers_out + 8 * (size_t)s, r, sizeof r);
+        }
+    if (groups_out)
+        for (int64_t g = 0; g < std::min<int64_t>((int64_t)p.groups.size(), group_cap); g++) {
+            const FullGroupPlan &gp = p.groups[(size_t)g];
+            const FullCounts &c = gp.counts;
+            const int64_t r[28] = {gp.first, gp.count, gp.rows, gp.lp0, gp.lse0, gp.cov0, gp.max_iter, gp.any_kmeans, gp.any_given, gp.bytes,
+                                   c.X, c.w, c.logw, c.mu, c.prec, c.logdet, c.cov, c.lp, c.lpn, c.nk, c.partial, c.head,
+                                   c.spk, c.rec, c.wl_lp, c.wl_lse, c.wl_cov, c.label};
+            std::memcpy(groups_out + 28 * g, r, sizeof r);
+        }
+    return 7;
+    SR_CATCH(-1)
+}
+
 int sr_fullgmm_info(SRFullGMM *g, int *K, int *D) {
     SR_TRY
     if (!g) fail("null handle");

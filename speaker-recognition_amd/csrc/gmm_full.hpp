@@ -1,9 +1,11 @@
 // gmm_full.hpp -- full-covariance GMMs (C ABI handles `SRFullGMM *` / `SRFullSet *`): scikit-learn's GaussianMixture layout,
-// float64 EM on the device, fp32 matrix-core scoring of a packed set of speakers (csrc/gmm_full.hip).
+// float64 EM on the device (csrc/gmm_full_fit.hip, planned by csrc/full_plan.cpp), fp32 matrix-core scoring of a packed set of
+// speakers (csrc/gmm_full.hip).
 #pragma once
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "full_plan.hpp"
 #include "mfcc.hpp"
 
 #include "../../include/pygmm_hip.h"
@@ -35,8 +37,8 @@ struct SRFullSet {
 };
 
 namespace sr {
-constexpr int FULL_MAX_D = 64;
-// Both fits run gmm_full.hip's one EM driver, in which a speaker's bits do not depend on the speakers fitted with it.
+constexpr double FC_LN_2PI = 1.8378770664093453;
+// (FULL_MAX_D: full_plan.hpp.)  Both fits run gmm_full_fit.hip's one EM driver, in which a speaker's bits do not depend on the speakers fitted with it.
 // One model, a group of one: a failed fit throws and leaves the handle untouched; it moves none of full_fit_batch_stats' counters
 // and full_fit_batch_bytes does not bear on it.
 void fullgmm_fit(SRFullGMM &g, const double *X, long n, int D, const SRFullFitParams &p, SRFullFitStats &out);

@@ -2,8 +2,8 @@
 ``ModelInterface`` uses (interface.py:24: scikit-learn's ``GaussianMixture(32)``, full covariance).
 
 ``GMM`` is the subset of ``sklearn.mixture.GaussianMixture`` the reference and its users touch, computed by this library: EM in
-float64 on the device (csrc/gmm_full.hip) exactly as ``GaussianMixture.fit`` runs it with ``covariance_type='full'`` and
-``n_init=1``, and scoring on the fp32 matrix cores.  Parameters use scikit-learn's layout, so they convert 1:1.
+float64 on the device (csrc/gmm_full_fit.hip) exactly as ``GaussianMixture.fit`` runs it with ``covariance_type='full'`` and
+``n_init=1``, and scoring on the fp32 matrix cores (csrc/gmm_full.hip).  Parameters use scikit-learn's layout, so they convert 1:1.
 
 Differences from scikit-learn, all deliberate:
   * ``init_params='kmeans'`` takes its labels from this library's seeded k-means (k-means|| + Lloyd, csrc/kmeans_init.hip), not

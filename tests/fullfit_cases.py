@@ -1,4 +1,4 @@
-"""Cases and data for the float64 full-covariance EM kernels (csrc/gmm_full.hip: the fe_* kernels behind fe_fit_group), shared by
+"""Cases and data for the float64 full-covariance EM kernels (csrc/gmm_full_fit.hip: the fe_* kernels behind fe_fit_group), shared by
 tests/test_fullfit_cases_cpu.py, tests/test_gpu_fullfit_cases.py and the recorder tests/golden/make_fullfit_edge_golden.py.
 Plain module (as tests/mfcc_cases.py, tests/em_parent_cases.py).  Every row is the smallest shape that reaches the edge it names:
 
@@ -35,7 +35,7 @@ def _c(name, K, D, n, seed, edge, reg=1e-6, tol=0.0, max_iter=3, kind="plain", c
 
 
 def slots(D):
-    """covariance pair slots a width uses: pairs D (D + 1) / 2 over 256 threads (gmm_full.hip: 9 x 256 >= 64 x 65 / 2)"""
+    """covariance pair slots a width uses: pairs D (D + 1) / 2 over 256 threads (full_plan.hpp: 9 x 256 >= 64 x 65 / 2)"""
     return (D * (D + 1) // 2 + 255) // 256
 
 

@@ -147,8 +147,8 @@ def test_interface_and_cli_take_the_covariance_option():
 
 def test_gmm_full_kernels_do_not_spill(built_lib):
     import test_abi_cpu
-    res = test_abi_cpu._kernel_resources("gmm_full")
+    res = dict(test_abi_cpu._kernel_resources("gmm_full"), **test_abi_cpu._kernel_resources("gmm_full_fit"))
     names = [n for n in res if "fullcov_score_kernel" in n or "fe_" in n]
-    assert len([n for n in names if "fullcov_score_kernel" in n]) == 2
+    assert len([n for n in names if "fullcov_score_kernel" in n]) == 2 and len([n for n in names if "fe_" in n]) == 10
     for name, r in res.items():
         assert r["scratch"] == 0, (name, r)

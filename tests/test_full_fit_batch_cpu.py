@@ -1,4 +1,4 @@
-"""Batched full-covariance fits without a GPU (sr_fullgmm_fit_batch, skgmm.fit_many; csrc/gmm_full.hip): the symbol and its
+"""Batched full-covariance fits without a GPU (sr_fullgmm_fit_batch, skgmm.fit_many; csrc/gmm_full_fit.hip): the symbol and its
 binding, every argument check (all made before the device is touched, so they answer here), the loud failure without a device,
 the host-side checks of skgmm.fit_many, and the batched kernels' scratch."""
 import ctypes as C
@@ -201,7 +201,7 @@ def _kernel_resources(name):
 
 
 def test_batched_kernels_have_no_scratch_and_no_single_model_kernel_is_left(built_lib):
-    res = _kernel_resources("gmm_full")
+    res = _kernel_resources("gmm_full_fit")
     for stem, parent in PARENT_SCRATCH.items():
         batch = [n for n in res if stem + "_batch_kernel" in n]
         assert len(batch) == 1, (stem, sorted(res))
