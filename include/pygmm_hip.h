@@ -428,7 +428,7 @@ const char *sr_last_score_kernel(void);
 int sr_last_em_stats_engine(void);
 /* The first `count` values of the random stream train_model / load draw from when no seed is given: glibc's rand()
  * from its default seed, restated inside the library (the reference draws its initialisation from libc rand():
- * src/gmm/src/random.hh:22-25, gmm.hh:44, kmeansII.cc:94,133; csrc/kmeans_init.hip).  For checks. */
+ * src/gmm/src/random.hh:22-25, gmm.hh:44, kmeansII.cc:94,133; csrc/ref_rand.cpp).  For checks. */
 int sr_reference_rand_sample(int *out, int count);
 
 /* ---- Full-covariance GMMs (csrc/gmm_full.hip): scikit-learn's GaussianMixture(covariance_type='full') ----

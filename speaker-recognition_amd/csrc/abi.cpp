@@ -8,6 +8,7 @@
 #include "fork_proxy.hpp"
 #include "gmm_full.hpp"
 #include "gmm_model.hpp"
+#include "kmeans_init.hpp"
 #include "mfcc.hpp"
 #include "mfcc_plan.hpp"
 #include "score.hpp"
@@ -17,6 +18,7 @@
 #include "jfa_plan.hpp"
 #include "norm_plan.hpp"
 #include "map_plan.hpp"
+#include "ref_rand.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -26,15 +28,12 @@
 #include <sstream>
 
 namespace sr {
-void burn_reference_rand(int count);     // kmeans_init.hip
-void reference_rand_sample(int *out, int count);
 int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param,
              long seed);
 void set_em_stats_engine(int v);
 void set_em_small_test_absent(int v);   // em_small.hip
 int last_em_stats_engine();
 void set_reference_side_effects(int v);
-void set_kmeans_assign_engine(int v);
 // map_batch.hip
 int map_fit_batch(GMM *const *models, int S, const GMM *ubm, const float *X, const int64_t *row_offsets, int dim, const Parameter &param,
                   long seed, int *iterations_out, int *status, std::vector<std::string> &messages);
@@ -55,7 +54,6 @@ long silence_block();
 std::atomic<int> &stream_debug_capture_delay_ms();      // stream.cpp
 std::atomic<int> &multi_merge_option();
 namespace sr {
-void kmeans_fast_stats(long *passes, long *rechecked);
 int reference_side_effects();
 }  // namespace sr
 

@@ -1,5 +1,6 @@
 // common.cpp -- error parking, lazy device context, HIP-event kernel timers.
 #include "common.hpp"
+#include "ref_rand.hpp"
 
 #include <climits>
 #include <mutex>
@@ -67,7 +68,6 @@ static bool g_ready[MAX_DEVICES];
 static std::mutex g_mu;
 static std::mutex g_slot_mu;
 
-void reference_rand_fork_child();       // kmeans_init.hip
 
 // ---- fork (common.hpp) ----
 static std::atomic<long> g_runtime_pid{0};       // the process that made the first HIP call (0: none yet)

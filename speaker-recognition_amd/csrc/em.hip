@@ -14,6 +14,8 @@
 // reference's formulas.
 #include "em_mstep.hpp"
 #include "em_plan.hpp"
+#include "kmeans_init.hpp"
+#include "ref_rand.hpp"
 #include "score.hpp"
 #include "split_prologue.hpp"
 #include "split_schemes.hpp"
@@ -648,12 +650,9 @@ void em_reduce_kernel(const float *__restrict__ slabs, int n_slabs, int n_elem,
     out[e] = acc;
 }
 
-// initialisation: kmeans_init.hip (the reference's own draws, decision for decision)
-void init_gmm_like_reference(GMM &g, const float *X, long n, int dim, const Parameter &param, long seed);
 // em_small.hip, em_f64.hip: true = done; false = handed back (gmm untouched)
 bool train_em_small(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
 bool train_em_f64(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
-void burn_reference_rand(int count);
 
 // The model of one EM / MAP iteration as a set: the vector-ALU layout (the statistics kernels' records) and -- round 4 -- the
 // split-bf16 one, so that the posteriors' denominators and the total log-likelihood of every second iteration run on the matrix

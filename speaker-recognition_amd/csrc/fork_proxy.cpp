@@ -18,7 +18,7 @@
 // What crosses: requests carry the model(s) as float64 parameter arrays (once per model and helper: the helper keeps what it has
 // seen, keyed by the caller's handle and a hash of the contents), the frames as the contiguous fp32 matrix the entry point has
 // built anyway, the caller's Parameter block, the options set through sr_set_option so far (replayed at start-up, forwarded
-// afterwards), the current device index and the state of the restated libc rand() (kmeans_init.hip), which comes back with
+// afterwards), the current device index and the state of the restated libc rand() (ref_rand.cpp), which comes back with
 // the reply: training from scratch in a forked child draws what the reference's forked child would draw.  Replies carry a
 // status + message (an sr::Error in the helper becomes an sr::Error here), sums / per-frame values, or the trained parameters.
 //
@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "fork_proxy.hpp"
 #include "gmm_model.hpp"
+#include "ref_rand.hpp"
 
 #include <atomic>
 #include <cerrno>
@@ -50,7 +51,6 @@ extern char **environ;
 namespace sr {
 
 int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param, long seed);   // em.hip
-void reference_rand_state(int32_t *words36, bool set);                                                           // kmeans_init.hip
 void score_one_local(GMM *g, const float *X, long n, int dim, float *ll_out, double *sum_out, int flags);       // abi.cpp
 void score_models_local(GMM *const *models, int n_models, const float *X, long n, int dim, double *sums_out, int flags);   // abi.cpp
 

@@ -64,5 +64,4 @@ void masked_finalize(const float *fll, long n, const int64_t *d_off, const int *
 void fullset_reserve(SRFullSet &set, int64_t n_rows, int n_utt);
 // MFCC (+ LPC columns or deltas) -> scoring -> finalize -> one copy back (sr_fullset_predict_pcm_batch)
 void fullset_predict_pcm(SRMfcc &m, SRFullSet &set, SRBatch &pcm, int nd, double *sums, int *argmax);
-std::vector<int> kmeans_labels(const float *X, long n, int dim, int K, long seed);     // kmeans_init.hip
 }  // namespace sr

@@ -15,6 +15,7 @@
 // fullgmm_fit_batch its whole call, and fe_fit_group runs one group of a plan as four steps: fill the workspace, start, loop,
 // hand back.
 #include "gmm_full.hpp"
+#include "kmeans_init.hpp"
 
 #include <algorithm>
 #include <atomic>

@@ -1,17 +1,5 @@
-// kmeans_init.hip -- the reference's initialisation of a GMM before EM, decision for decision:
-// GMMTrainerBaseline::init_gaussians (src/gmm/src/gmm.cc:306-361): data variance, then either K random
-// frames (init_with_kmeans = 0, the reference's default) or k-means|| (KMeansIISolver::cluster,
-// kmeansII.cc:82-171: oversampling rounds -> weighted k-means++ on the candidates, kmeans++.cc:161-212 ->
-// weighted Lloyd, kmeans.cc:249-342 -> Lloyd on the full data, kmeans.cc:150-246).
-//
-// What makes the reference reproducible is its random numbers: every draw comes from libc rand() or
-// from a std::default_random_engine seeded by rand() (random.hh:17-56), and rand() starts from its default
-// seed in a fresh process.  The same draws are made here, in the same order, from the same generators
-// (libstdc++'s engine and distribution; glibc's rand() -- restated below, because the process-wide one
-// cannot be used: the HIP runtime draws from it while it initialises, scripts/debug/randcheck.py), so a
-// model trained from scratch through the legacy train_model symbol comes out as the reference's does in a
-// process where it is the only user of rand() (tests/golden/make_init_golden.py).  A caller who passes
-// a seed (sr_train_f32) gets the same algorithm on a stream of its own.
+// kmeans_init.hip -- the device back end of the start in front of EM (kmeans_host.cpp has the stages and the drivers, decision for
+// decision the reference's; kmeans_plan.cpp what is decided before a launch).
 //
 // Arithmetic: the reference works in float64 and sums in a fixed order (per worker block of
 // ceil(n / concurrency) points, then over the blocks); sums that feed a decision are formed in that
@@ -19,96 +7,26 @@
 // the device in float64, dimension by dimension with separate multiply and add as the reference's SSE2
 // build does (no FMA).  The per-cluster sums of a Lloyd step on the full data are formed on the device too
 // (round 3), in the reference's order: a stable radix sort of the points by (worker block, cluster) puts every
-// (block, cluster)'s members side by side in point order; one thread per (cluster, dimension) then adds each
 // (block, cluster)'s members side by side in point order; one thread per (block, cluster, dimension) adds them one
 // after the other, one per (cluster, dimension) the blocks' sums in block order -- the additions calc_belonging and
 // Lloyds_iteration make (kmeans.cc:72-107, :189-212), bit for bit, at device bandwidth instead of 9 s of host
 // loops in front of a 2048-mixture UBM.
-// The full data keeps every coordinate (gmm.cc:288-294 dense2sparse; only the CANDIDATE centres of the weighted
-// k-means++ / weighted Lloyd stages go through Vector2Instance, which drops |x| < 1e-15, kmeans++.cc:42-51), so
-// the distance here is the dense one.
+#include "kmeans_init.hpp"
+
+#include "kmeans_host.hpp"
 #include "score.hpp"
 
 #include "../../include/pygmm_hip.h"
 
-#include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>     // the device radix sort of the Lloyd step (rocPRIM: the native library; hipCUB wraps it in CUB's API)
 
 #include <algorithm>
 #include <atomic>
-#include <cfloat>
-#include <chrono>
-#include <climits>
-#include <cmath>
-#include <cstdlib>
-#include <limits>
-#include <mutex>
-#include <new>
-#include <random>
-#include <thread>
 
 namespace sr {
 
 namespace {
 
-// random.hh:17-56
-struct RefRandom {
-    std::default_random_engine generator;
-    std::uniform_real_distribution<double> real_distribution;     // [0, 1)
-    explicit RefRandom(long long seed) { generator.seed(seed); }
-    double rand_real() { return real_distribution(generator); }
-    int rand_int(int max_val = std::numeric_limits<int>::max()) { return (int)(rand_real() * max_val); }
-};
-
-// glibc's rand() (random_r.c, TYPE_3: the additive feedback generator x^31 + x^3 + 1 over 31-bit outputs,
-// state filled from the seed by the Lehmer generator 16807 mod 2^31 - 1, first 310 outputs discarded).
-// tests/test_abi_cpu.py checks it against the C library's own rand().
-struct GlibcRand {
-    int32_t r[34];
-    int f = 3, b = 0;           // front / rear indices into r[3..33]
-    explicit GlibcRand(unsigned seed = 1) {
-        int32_t *state = r + 3;     // 31 words (r[0..2] unused; keeps the textbook indices readable)
-        if (seed == 0) seed = 1;
-        state[0] = (int32_t)seed;
-        for (int i = 1; i < 31; i++) {
-            const long hi = state[i - 1] / 127773, lo = state[i - 1] % 127773;
-            long word = 16807 * lo - 2836 * hi;
-            if (word < 0) word += 2147483647;
-            state[i] = (int32_t)word;
-        }
-        f = 3;
-        b = 0;
-        for (int i = 0; i < 310; i++) (void)next();
-    }
-    int next() {
-        int32_t *state = r + 3;
-        const uint32_t val = (uint32_t)state[f] + (uint32_t)state[b];
-        state[f] = (int32_t)val;
-        const int result = (int)(val >> 1);
-        if (++f >= 31) f = 0;
-        if (++b >= 31) b = 0;
-        return result;
-    }
-};
-std::mutex g_rand_mutex;
-GlibcRand g_reference_rand;       // what rand() would return in a process where the reference library is its only user
-
-// The stream the reference draws from -- the restated libc one (library-wide, as the reference's is process-wide) --
-// or, when the caller seeds, a generator of the caller's own.
-struct RandStream {
-    bool shared;
-    GlibcRand own;
-    explicit RandStream(long seed) : shared(seed < 0), own(seed < 0 ? 1u : (unsigned)seed + 1u) {}
-    int operator()() {
-        if (!shared) return own.next();
-        std::lock_guard<std::mutex> lock(g_rand_mutex);
-        return g_reference_rand.next();
-    }
-};
-
-constexpr int KM_CH = 16;          // centres per LDS chunk
-constexpr int KM_PP = 2;           // points per lane: a centre coordinate read from LDS serves both
-constexpr int KM_MAX_ITER = 200;   // kmeans.cc:172, :272
 typedef double km_d2 __attribute__((ext_vector_type(2)));
 
 // Nearest centre among centres [c_begin, c_end): dist[i] / belong[i] are updated when a centre is STRICTLY
@@ -214,9 +132,6 @@ void kmeans_assign_kernel(const float *__restrict__ X, long n, int dim, const do
 // reference's way (subtract, multiply, add, dimension by dimension) for that one centre.  The others (exact ties between
 // duplicate centres, the odd near-tie) go on a list and through the exact pass: same belong[] and dist[], bit for bit
 // (test_kmeans_fast_assign_equals_the_exact_pass), 4 ms instead of 10.
-// chunk records for the fast search: 16 centres per record, [d][16] doubles of -2 c, then the 16 ||c||^2; padded to whole KiB so
-// that a record goes into LDS as 1 KiB LDS-DMA pieces
-__host__ __device__ constexpr int km_rec_doubles(int dim_max) { return (dim_max * KM_CH + KM_CH + 127) / 128 * 128; }
 
 __global__ __launch_bounds__(256)
 void kmeans_centre_prep_kernel(const double *__restrict__ C, int K, int dim, int dim_max, double *__restrict__ rec,
@@ -443,7 +358,6 @@ void lloyd_centroid_kernel(int dim, int K, int n_blocks, const unsigned *__restr
 // the sum of a worker block's distances in point order (calc_belonging's distsqr_sum, kmeans.cc:85-106): a workgroup per
 // block stages the distances through LDS with coalesced loads, one thread adds them one after the other (a lone thread
 // walking global memory pays a cache-miss latency per addend: 8 ms per Lloyd step at 4 k points per block)
-constexpr int KM_BS_CHUNK = 4096;
 __global__ __launch_bounds__(256)
 void lloyd_block_sum_kernel(const double *__restrict__ dist, long n, long block, int n_blocks, double *__restrict__ bsum) {
     __shared__ double stage[KM_BS_CHUNK];
@@ -461,322 +375,120 @@ void lloyd_block_sum_kernel(const double *__restrict__ dist, long n, long block,
     if (threadIdx.x == 0) bsum[b] = s;
 }
 
-void device_assign(long n, int dim, const std::vector<double> &C, int c_begin, int c_end,
-                   std::vector<double> &dist, std::vector<int> &belong, bool reset, bool download = true) {
-    auto &w = kws();
-    w.C.upload(C.data(), (size_t)c_end * dim);
-    if (reset) {
-        w.dist.ensure((size_t)n);
-        w.belong.ensure((size_t)n);
-    } else {
-        w.dist.upload(dist.data(), (size_t)n);
-        w.belong.upload(belong.data(), (size_t)n);
-    }
-    const unsigned grid = (unsigned)((n + 256 * KM_PP - 1) / (256 * KM_PP));
-    const bool fast = reset && c_begin == 0 && dim <= 40 && kmeans_assign_engine_option() == 0 && n < ((long)1 << 31);
-    if (fast) {
-        // one fused multiply-add per point, centre and dimension decides wherever it can; the rest goes through the exact pass
-        const int K = c_end;
-        const int dim_max = dim <= 16 ? 16 : 40;
-        const int n_chunks = (K + KM_CH - 1) / KM_CH;
-        w.m2c.ensure((size_t)n_chunks * km_rec_doubles(dim_max));
-        w.cn_max.ensure(1);
-        w.list.ensure((size_t)n);
-        w.n_list.ensure(1);
-        SR_HIP(hipMemsetAsync(w.cn_max.p, 0, sizeof(double), ctx().stream));
-        SR_HIP(hipMemsetAsync(w.n_list.p, 0, sizeof(int), ctx().stream));
-        hipLaunchKernelGGL(kmeans_centre_prep_kernel, dim3((unsigned)((n_chunks * KM_CH + 255) / 256)), dim3(256), 0, ctx().stream, w.C.p, K, dim,
-                           dim_max, w.m2c.p, w.cn_max.p);
-        if (dim <= 16)
-            hipLaunchKernelGGL(kmeans_assign_fast_kernel<16>, dim3(grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, w.m2c.p,
-                               w.cn_max.p, K, w.dist.p, w.belong.p, w.list.p, w.n_list.p);
-        else
-            hipLaunchKernelGGL(kmeans_assign_fast_kernel<40>, dim3(grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, w.m2c.p,
-                               w.cn_max.p, K, w.dist.p, w.belong.p, w.list.p, w.n_list.p);
-    }
-    const int *list = fast ? w.list.p : nullptr;
-    const int *n_list = fast ? w.n_list.p : nullptr;
-#define SR_KM_LAUNCH(DM)                                                                                                    \
-    hipLaunchKernelGGL(kmeans_assign_kernel<DM>, dim3(grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, c_begin, c_end, \
+
+// The two operations of the start's back end (kmeans_host.hpp: KmBackend) on the current device, each following its plan.  The
+// data go up with the first pass and stay (kws().X); dist / belong stay for lloyd_sums.
+struct DeviceBackend {
+    const float *X;
+    long n;
+    int dim;
+    bool resident = false;
+    KmAssignPlan last;                      // of the latest pass: was it a fast one?
+    long sort_n = -1;                       // what sort_tmp was last sized for
+    int sort_bits = -1;
+
+    void assign(const std::vector<double> &C, int c_begin, int c_end, std::vector<double> &dist, std::vector<int> &belong, bool reset, bool download) {
+        const KmAssignPlan p = plan_kmeans_assign(n, dim, c_begin, c_end, reset, kmeans_assign_engine_option());
+        if (!p.refusal.empty()) fail("%s", p.refusal.c_str());
+        auto &w = kws();
+        if (!resident) {
+            ensure_device();
+            w.X.upload(X, (size_t)n * dim);
+            resident = true;
+        }
+        w.C.upload(C.data(), p.C);
+        if (reset) {
+            w.dist.ensure(p.dist);
+            w.belong.ensure(p.belong);
+        } else {
+            w.dist.upload(dist.data(), p.dist);
+            w.belong.upload(belong.data(), p.belong);
+        }
+        if (p.fast) {
+            // one fused multiply-add per point, centre and dimension decides wherever it can; the rest goes through the exact pass
+            const int K = c_end;
+            w.m2c.ensure(p.m2c);
+            w.cn_max.ensure(p.cn_max);
+            w.list.ensure(p.list);
+            w.n_list.ensure(p.n_list);
+            SR_HIP(hipMemsetAsync(w.cn_max.p, 0, sizeof(double), ctx().stream));
+            SR_HIP(hipMemsetAsync(w.n_list.p, 0, sizeof(int), ctx().stream));
+            hipLaunchKernelGGL(kmeans_centre_prep_kernel, dim3(p.prep_grid), dim3(256), 0, ctx().stream, w.C.p, K, dim, p.fast_dim_max, w.m2c.p,
+                               w.cn_max.p);
+            if (p.fast_dim_max == 16)
+                hipLaunchKernelGGL(kmeans_assign_fast_kernel<16>, dim3(p.grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, w.m2c.p,
+                                   w.cn_max.p, K, w.dist.p, w.belong.p, w.list.p, w.n_list.p);
+            else
+                hipLaunchKernelGGL(kmeans_assign_fast_kernel<40>, dim3(p.grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, w.m2c.p,
+                                   w.cn_max.p, K, w.dist.p, w.belong.p, w.list.p, w.n_list.p);
+        }
+        const int *list = p.fast ? w.list.p : nullptr;
+        const int *n_list = p.fast ? w.n_list.p : nullptr;
+#define SR_KM_LAUNCH(DM)                                                                                                      \
+    hipLaunchKernelGGL(kmeans_assign_kernel<DM>, dim3(p.grid), dim3(256), 0, ctx().stream, w.X.p, n, dim, w.C.p, c_begin, c_end, \
                        w.dist.p, w.belong.p, reset ? 1 : 0, list, n_list)
-    if (dim <= 16) SR_KM_LAUNCH(16);
-    else if (dim <= 40) SR_KM_LAUNCH(40);
-    else if (dim <= 64) SR_KM_LAUNCH(64);
-    else SR_KM_LAUNCH(128);
+        if (p.exact_dim_max == 16) SR_KM_LAUNCH(16);
+        else if (p.exact_dim_max == 40) SR_KM_LAUNCH(40);
+        else if (p.exact_dim_max == 64) SR_KM_LAUNCH(64);
+        else SR_KM_LAUNCH(128);
 #undef SR_KM_LAUNCH
-    SR_HIP(hipGetLastError());
-    if (!download) return;                    // (Lloyd on the full data goes on with them on the device)
-    w.dist.download(dist.data(), (size_t)n);
-    w.belong.download(belong.data(), (size_t)n);
-    sync_stream();
-}
-
-// sum of v[0..n) as the reference's workers form it: sequentially inside blocks of ceil(n / concurrency),
-// then over the blocks (kmeansII.cc:103-129, kmeans.cc:166-187)
-double blocked_sum(const std::vector<double> &v, long n, int concurrency) {
-    const long block = (long)std::ceil((double)n / concurrency);
-    double total = 0;
-    for (long b = 0; b < n; b += block) {
-        double s = 0;
-        const long e = std::min(n, b + block);
-        for (long i = b; i < e; i++) s += v[i];
-        total += s;
+        SR_HIP(hipGetLastError());
+        last = p;
+        if (!download) return;                    // (Lloyd on the full data goes on with them on the device)
+        w.dist.download(dist.data(), p.dist);
+        w.belong.download(belong.data(), p.belong);
+        sync_stream();
     }
-    return total;
-}
 
-// Lloyd on the full data (kmeans.cc:150-246).  centroids: [K][dim] in/out.
-void lloyd_full(const float *X, long n, int dim, int K, int concurrency, std::vector<double> &centroids, int verbosity) {
-    (void)X;                                   // (resident on the device: kws().X)
-    auto &w = kws();
-    std::vector<double> best_centroids, dummy_d;
-    std::vector<int> dummy_i;
-    double best = std::numeric_limits<double>::max(), last = std::numeric_limits<double>::max();
-    const long block = (long)std::ceil((double)n / concurrency);
-    const int n_blocks = (int)((n + block - 1) / block);
-    if ((double)n_blocks * K >= 4.0e9 || n >= ((long)1 << 32)) fail("k-means: %d worker blocks x %d clusters x %ld points do not fit 32-bit sort keys", n_blocks, K, n);
-    const unsigned n_keys = (unsigned)n_blocks * (unsigned)K;
-    int end_bit = 1;
-    while (end_bit < 32 && (1ull << end_bit) <= (unsigned long long)n_keys) end_bit++;      // keys 0 .. n_keys inclusive
-    w.key_in.ensure((size_t)n);
-    w.key_out.ensure((size_t)n);
-    w.idx_in.ensure((size_t)n);
-    w.idx_out.ensure((size_t)n);
-    w.seg.ensure((size_t)n_keys + 2);
-    w.csum.ensure((size_t)K * dim);
-    w.csize.ensure((size_t)K);
-    w.bsum.ensure((size_t)n_blocks);
-    w.segsum.ensure((size_t)n_keys * dim);
-    size_t tmp_bytes = 0;
-    SR_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, w.key_in.p, w.key_out.p, w.idx_in.p, w.idx_out.p, (size_t)n, 0u, (unsigned)end_bit, ctx().stream));
-    w.sort_tmp.ensure(tmp_bytes);
-    std::vector<double> csum((size_t)K * dim), bsum((size_t)n_blocks);
-    std::vector<int> csize((size_t)K);
-    for (int iter = 0; iter < KM_MAX_ITER; iter++) {
-        device_assign(n, dim, centroids, 0, K, dummy_d, dummy_i, true, false);
-        const unsigned g256 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(lloyd_block_sum_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ctx().stream, w.dist.p, n, block, n_blocks,
-                           w.bsum.p);
-        hipLaunchKernelGGL(lloyd_keys_kernel, dim3(g256), dim3(256), 0, ctx().stream, w.belong.p, n, block, K, n_keys, w.key_in.p, w.idx_in.p);
+    long lloyd_sums(const KmLloydPlan &p, std::vector<double> &bsum, std::vector<double> &csum, std::vector<int> &csize) {
+        auto &w = kws();
+        w.key_in.ensure(p.key);
+        w.key_out.ensure(p.key);
+        w.idx_in.ensure(p.key);
+        w.idx_out.ensure(p.key);
+        w.seg.ensure(p.seg);
+        w.csum.ensure(p.csum);
+        w.csize.ensure(p.csize);
+        w.bsum.ensure(p.bsum);
+        w.segsum.ensure(p.segsum);
+        if (sort_n != p.n || sort_bits != p.end_bit) {
+            size_t tmp_bytes = 0;
+            SR_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, w.key_in.p, w.key_out.p, w.idx_in.p, w.idx_out.p, (size_t)p.n, 0u, (unsigned)p.end_bit, ctx().stream));
+            w.sort_tmp.ensure(tmp_bytes);
+            sort_n = p.n;
+            sort_bits = p.end_bit;
+        }
+        bsum.resize(p.bsum);
+        csum.resize(p.csum);
+        csize.resize(p.csize);
+        hipLaunchKernelGGL(lloyd_block_sum_kernel, dim3(p.grid_block_sum), dim3(256), 0, ctx().stream, w.dist.p, p.n, p.block, p.n_blocks, w.bsum.p);
+        hipLaunchKernelGGL(lloyd_keys_kernel, dim3(p.grid_keys), dim3(256), 0, ctx().stream, w.belong.p, p.n, p.block, p.K, p.n_keys, w.key_in.p, w.idx_in.p);
         size_t tb = w.sort_tmp.n;
-        SR_HIP(rocprim::radix_sort_pairs(w.sort_tmp.p, tb, w.key_in.p, w.key_out.p, w.idx_in.p, w.idx_out.p, (size_t)n, 0u, (unsigned)end_bit,
+        SR_HIP(rocprim::radix_sort_pairs(w.sort_tmp.p, tb, w.key_in.p, w.key_out.p, w.idx_in.p, w.idx_out.p, (size_t)p.n, 0u, (unsigned)p.end_bit,
                                          ctx().stream));                                     // stable: point order inside a key
-        hipLaunchKernelGGL(lloyd_segments_kernel, dim3((n_keys + 1 + 255) / 256), dim3(256), 0, ctx().stream, w.key_out.p, n, n_keys, w.seg.p);
-        const size_t n_seg_elems = (size_t)n_keys * dim;
-        hipLaunchKernelGGL(lloyd_segment_sum_kernel, dim3((unsigned)((n_seg_elems + 255) / 256)), dim3(256), 0, ctx().stream, w.X.p, dim,
-                           n_seg_elems, w.seg.p, w.idx_out.p, w.segsum.p);
-        hipLaunchKernelGGL(lloyd_centroid_kernel, dim3((unsigned)((K * dim + 255) / 256)), dim3(256), 0, ctx().stream, dim, K, n_blocks,
-                           w.seg.p, w.segsum.p, w.csum.p, w.csize.p);
+        hipLaunchKernelGGL(lloyd_segments_kernel, dim3(p.grid_segments), dim3(256), 0, ctx().stream, w.key_out.p, p.n, p.n_keys, w.seg.p);
+        hipLaunchKernelGGL(lloyd_segment_sum_kernel, dim3(p.grid_segment_sum), dim3(256), 0, ctx().stream, w.X.p, p.dim, p.n_seg_elems, w.seg.p,
+                           w.idx_out.p, w.segsum.p);
+        hipLaunchKernelGGL(lloyd_centroid_kernel, dim3(p.grid_centroid), dim3(256), 0, ctx().stream, p.dim, p.K, p.n_blocks, w.seg.p, w.segsum.p,
+                           w.csum.p, w.csize.p);
         SR_HIP(hipGetLastError());
         w.bsum.download(bsum.data(), bsum.size());
         w.csum.download(csum.data(), csum.size());
         w.csize.download(csize.data(), csize.size());
         int rechecked = 0;
-        const bool fast_pass = w.n_list.p != nullptr && kmeans_assign_engine_option() == 0 && dim <= 40;
-        if (fast_pass) w.n_list.download(&rechecked, 1);
+        if (last.fast) w.n_list.download(&rechecked, 1);
         sync_stream();
-        if (fast_pass) {
+        if (last.fast) {
             g_km_fast_passes++;
             g_km_fast_rechecked += rechecked;
         }
-        double sum = 0;
-        for (int b = 0; b < n_blocks; b++) sum += bsum[b];
-        if (sum < best) {
-            best = sum;
-            best_centroids = centroids;
-        }
-        if (verbosity >= 2) printf("k-means iteration %3d: %f\n", iter, sum);
-        if (std::fabs(last - sum) < 1e-6) break;
-        if (sum > best * 1.5) break;                          // terminate_cost_factor
-        for (int k = 0; k < K; k++)
-            for (int d = 0; d < dim; d++)
-                centroids[(size_t)k * dim + d] = csum[(size_t)k * dim + d] / (double)csize[k];    // an empty cluster divides by 0, as the reference
-        last = sum;
+        return rechecked;
     }
-    centroids = best_centroids;
-}
 
-// squared distance over the coordinates a sparse instance keeps (|x| >= 1e-15, kmeans++.cc:43-51, :53-60)
-inline double sparse_distsqr(const double *x, const double *c, int dim) {
-    double dist = 0;
-    for (int d = 0; d < dim; d++) {
-        if (std::fabs(x[d]) < 1e-15) continue;
-        const double delta = x[d] - c[d];
-        dist += delta * delta;
+    KmBackend ops() {
+        return {[this](auto &&...a) { assign(a...); }, [this](auto &&...a) { return lloyd_sums(a...); }};
     }
-    return dist;
-}
-
-// Weighted Lloyd on the candidate set (kmeans.cc:249-342).
-void lloyd_weighted(const std::vector<double> &P, const std::vector<double> &weight, int np, int dim, int K,
-                    int concurrency, std::vector<double> &centroids) {
-    std::vector<double> best_centroids;
-    double best = std::numeric_limits<double>::max(), last = std::numeric_limits<double>::max();
-    const int block = (int)std::ceil((double)np / concurrency);
-    const int n_blocks = (np + block - 1) / block;
-    std::vector<std::vector<double>> buf((size_t)n_blocks, std::vector<double>((size_t)K * dim)), csz((size_t)n_blocks, std::vector<double>((size_t)K));
-    for (int iter = 0; iter < KM_MAX_ITER; iter++) {
-        std::vector<double> block_sum((size_t)n_blocks, 0.0);
-        auto work = [&](int b) {
-            std::fill(buf[b].begin(), buf[b].end(), 0.0);
-            std::fill(csz[b].begin(), csz[b].end(), 0.0);
-            double s = 0;
-            for (int i = b * block; i < std::min(np, (b + 1) * block); i++) {
-                const double *x = P.data() + (size_t)i * dim;
-                double mind = std::numeric_limits<double>::max();
-                int id = -1;
-                for (int j = 0; j < K; j++) {
-                    const double dq = sparse_distsqr(x, centroids.data() + (size_t)j * dim, dim) * weight[i];
-                    if (dq < mind) {
-                        mind = dq;
-                        id = j;
-                    }
-                }
-                if (id >= 0) {
-                    csz[b][id] += weight[i];
-                    double *c = buf[b].data() + (size_t)id * dim;
-                    for (int d = 0; d < dim; d++)
-                        if (std::fabs(x[d]) >= 1e-15) c[d] += x[d] * weight[i];
-                }
-                s += mind;
-            }
-            block_sum[b] = s;
-        };
-        {
-            const int n_threads = std::max(1, std::min({n_blocks, (int)std::thread::hardware_concurrency(), 64}));
-            auto run = [&](int t) { for (int b = t; b < n_blocks; b += n_threads) work(b); };
-            std::vector<std::thread> th;
-            if ((size_t)np * K * dim > ((size_t)1 << 22))
-                for (int t = 1; t < n_threads; t++) th.emplace_back(run, t);
-            else
-                for (int t = 1; t < n_threads; t++) run(t);
-            run(0);
-            for (auto &t : th) t.join();
-        }
-        double sum = 0;
-        for (int b = 0; b < n_blocks; b++) sum += block_sum[b];
-        if (sum < best) {
-            best = sum;
-            best_centroids = centroids;
-        }
-        if (std::fabs(last - sum) < 1e-6) break;
-        std::vector<int> size((size_t)K, 0);                  // an int accumulator, as kmeans.cc:303-308
-        for (int b = 0; b < n_blocks; b++)
-            for (int k = 0; k < K; k++) size[k] += csz[b][k];
-        std::fill(centroids.begin(), centroids.end(), 0.0);
-        for (int b = 0; b < n_blocks; b++)
-            for (size_t e = 0; e < (size_t)K * dim; e++) centroids[e] += buf[b][e];
-        for (int k = 0; k < K; k++)
-            for (int d = 0; d < dim; d++) centroids[(size_t)k * dim + d] /= size[k];
-        last = sum;
-    }
-    centroids = best_centroids;
-}
-
-// KMeansIISolver::cluster (kmeansII.cc:82-171) with its defaults oversampling_factor = size_factor = 2.
-std::vector<double> kmeans_parallel_init(const float *X, long n, int dim, int K, int concurrency, RandStream &rs, int verbosity) {
-    const double oversampling_factor = 2.0, size_factor = 2.0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
-    RefRandom solver_random(rs());                            // KMeansIISolver::random (kmeansII.hh:41)
-    std::vector<double> cand;                                 // candidate centres, [count][dim]
-    auto push_point = [&](long i) {
-        for (int d = 0; d < dim; d++) cand.push_back((double)X[(size_t)i * dim + d]);
-    };
-    push_point((long)(rs() % n));
-    std::vector<double> dist((size_t)n, std::numeric_limits<double>::max());
-    std::vector<int> belong((size_t)n, 0);                    // vector<int> belong(n): zero-initialised (kmeansII.cc:97)
-    long last_size = 0;
-    for (int iter = 0;; iter++) {
-        const long size = (long)(cand.size() / dim);
-        device_assign(n, dim, cand, (int)last_size, (int)size, dist, belong, false);
-        if ((double)size > size_factor * K) break;
-        const double distsqr_sum = blocked_sum(dist, n, concurrency);
-        last_size = size;
-        for (long i = 0; i < n; i++) {
-            const double random_weight = rs() / (double)RAND_MAX * distsqr_sum;
-            if (random_weight < dist[i] * oversampling_factor * K) push_point(i);
-        }
-        const long added = (long)(cand.size() / dim) - last_size;
-        if (verbosity >= 2) printf("k-means|| round %d: %f, new %ld, all %ld\n", iter, distsqr_sum, added, last_size + added);
-        if (added == 0) break;
-    }
-    while ((double)(cand.size() / dim) <= size_factor * K) push_point(solver_random.rand_int((int)n));
-    const int np = (int)(cand.size() / dim);
-    const double t_rounds = now();
-    std::vector<double> weight((size_t)np, 0.0);
-    for (long i = 0; i < n; i++) weight[belong[i]] += 1.0;
-
-    // weighted k-means++ over the candidates (KMeansppSolver::cluster_weighted, kmeans++.cc:161-212)
-    RefRandom pp_random(rs());                                // KMeansppSolver::random (kmeans++.hh:32)
-    std::vector<double> centroids((size_t)K * dim, 0.0);
-    auto copy_sparse = [&](int from, int k) {                 // Vector2Instance drops |x| < 1e-15, Instance2Vector leaves those 0
-        for (int d = 0; d < dim; d++) {
-            const double v = cand[(size_t)from * dim + d];
-            centroids[(size_t)k * dim + d] = std::fabs(v) < 1e-15 ? 0.0 : v;
-        }
-    };
-    copy_sparse(pp_random.rand_int() % np, 0);
-    std::vector<double> pdist((size_t)np, std::numeric_limits<double>::max());
-    // The candidates' distance updates are independent of one another (only the blocked sum below has an order): when the
-    // candidate set is large (2 K+ candidates x K centres x dim: 0.24 s on one thread at K = 2048) a few host threads,
-    // started once and stepped through the K rounds by a pair of counters, share them.
-    const int pp_threads = (size_t)np * dim > ((size_t)1 << 16) ? std::max(1, std::min((int)std::thread::hardware_concurrency(), 16)) : 1;
-    std::atomic<int> round_go{0}, round_done{0};
-    auto upd = [&](int t, int k) {
-        const double *c = centroids.data() + (size_t)(k - 1) * dim;
-        const int lo = (int)((long)np * t / pp_threads), hi = (int)((long)np * (t + 1) / pp_threads);
-        for (int i = lo; i < hi; i++)
-            pdist[i] = std::min(pdist[i], sparse_distsqr(cand.data() + (size_t)i * dim, c, dim) * weight[i]);
-    };
-    // (joined on every way out: an exception between here and the end -- bad_alloc, a fail() -- would otherwise destroy
-    // joinable threads, i.e. std::terminate, with the workers spinning on a round that never comes)
-    std::atomic<bool> abort_workers{false};
-    struct Joiner {
-        std::vector<std::thread> th;
-        std::atomic<bool> &abort;
-        ~Joiner() {
-            abort.store(true, std::memory_order_release);
-            for (auto &t : th)
-                if (t.joinable()) t.join();
-        }
-    } workers{{}, abort_workers};
-    auto &pp_workers = workers.th;
-    for (int t = 1; t < pp_threads; t++)
-        pp_workers.emplace_back([&, t] {
-            for (int k = 1; k < K; k++) {
-                while (round_go.load(std::memory_order_acquire) < k) {
-                    if (abort_workers.load(std::memory_order_acquire)) return;
-                    std::this_thread::yield();
-                }
-                upd(t, k);
-                round_done.fetch_add(1, std::memory_order_release);
-            }
-        });
-    for (int k = 1; k < K; k++) {
-        round_go.store(k, std::memory_order_release);              // centroid k - 1 is in place
-        upd(0, k);
-        while (round_done.load(std::memory_order_acquire) < (pp_threads - 1) * k) std::this_thread::yield();
-        const double distsqr_sum = blocked_sum(pdist, np, concurrency);
-        double random_weight = pp_random.rand_int() / (double)RAND_MAX * distsqr_sum;
-        for (int i = 0; i < np; i++) {
-            random_weight -= pdist[i];
-            if (random_weight <= 0) {
-                copy_sparse(i, k);
-                break;
-            }
-        }
-    }
-    for (auto &t : pp_workers) t.join();
-    const double t_pp = now();
-    lloyd_weighted(cand, weight, np, dim, K, concurrency, centroids);
-    const double t_lw = now();
-    lloyd_full(X, n, dim, K, concurrency, centroids, verbosity);
-    if (verbosity >= 2)
-        printf("k-means|| phases: oversampling rounds %.3f s (%d candidates), weighted k-means++ %.3f s, weighted Lloyd %.3f s, "
-               "Lloyd on the full data %.3f s\n", t_rounds - t_start, np, t_pp - t_rounds, t_lw - t_pp, now() - t_lw);
-    return centroids;
-}
+};
 
 }  // namespace
 
@@ -786,89 +498,29 @@ void kmeans_fast_stats(long *passes, long *rechecked) {
     if (rechecked) *rechecked = g_km_fast_rechecked.load();
 }
 
-// The reference library's other draws from rand(), made by the legacy entry points so that the library's stream
-// stays in step with the reference's: one per Gaussian that GMM::load constructs (gmm.cc:671-676), one for the
-// trainer plus one per Gaussian in train_model_from_ubm (gmmubm.cc:29-38).
-void burn_reference_rand(int count) {
-    std::lock_guard<std::mutex> lock(g_rand_mutex);
-    for (int i = 0; i < count; i++) (void)g_reference_rand.next();
-}
-// fork support (common.cpp, fork_proxy.cpp): a forked child gets a fresh lock; the generator's state travels to the helper
-// process that computes on a forked child's behalf and back, so that the library-wide stream stays the one the reference's
-// process-wide rand() would be
-void reference_rand_fork_child() { new (&g_rand_mutex) std::mutex(); }
-void reference_rand_state(int32_t *words36, bool set) {
-    std::lock_guard<std::mutex> lock(g_rand_mutex);
-    if (set) {
-        for (int i = 0; i < 34; i++) g_reference_rand.r[i] = words36[i];
-        g_reference_rand.f = words36[34];
-        g_reference_rand.b = words36[35];
-    } else {
-        for (int i = 0; i < 34; i++) words36[i] = g_reference_rand.r[i];
-        words36[34] = g_reference_rand.f;
-        words36[35] = g_reference_rand.b;
-    }
-}
-// the first `count` values of a fresh generator (test hook: compared with the C library's rand())
-void reference_rand_sample(int *out, int count) {
-    GlibcRand g;
-    for (int i = 0; i < count; i++) out[i] = g.next();
-}
-
-// init_gaussians (gmm.cc:306-361).  seed < 0: the reference's stream (the library-wide restated rand()).
 void init_gmm_like_reference(GMM &g, const float *X, long n, int dim, const Parameter &param, long seed) {
     const int K = g.nr_mixtures;
-    const int concurrency = std::max(1, param.concurrency);
     g.dim = dim;
-    RandStream rs(seed);
-    RefRandom trainer_random(rs());                           // GMMTrainerBaseline::random, seeded when the trainer is built (pygmm.cc:65)
-    for (int k = 0; k < K; k++) (void)rs();                   // every `new Gaussian` seeds a Random of its own (gmm.hh:44, gmm.cc:327-329)
-    // data variance, unbiased, one sigma vector shared by all mixtures (gmm.cc:309-325, :352-354)
-    std::vector<double> mean(dim, 0.0), var(dim, 0.0);
-    for (long i = 0; i < n; i++)
-        for (int d = 0; d < dim; d++) mean[d] += X[(size_t)i * dim + d];
-    for (int d = 0; d < dim; d++) mean[d] /= (double)n;
-    for (long i = 0; i < n; i++)
-        for (int d = 0; d < dim; d++) {
-            const double v = X[(size_t)i * dim + d] - mean[d];
-            var[d] += v * v;
-        }
-    g.sigma.assign((size_t)K * dim, 0.0);
-    for (int k = 0; k < K; k++)
-        for (int d = 0; d < dim; d++) g.sigma[(size_t)k * dim + d] = std::sqrt(var[d] * (1.0 / (double)(n - 1)));
-    for (double s : g.sigma)
-        if (!(s > 0)) fail("training data has zero variance in some dimension");
-    g.mean.assign((size_t)K * dim, 0.0);
-    if (param.init_with_kmeans > 0) {
-        ensure_device();
-        kws().X.upload(X, (size_t)n * dim);
-        const std::vector<double> c = kmeans_parallel_init(X, n, dim, K, concurrency, rs, param.verbosity);
-        for (size_t e = 0; e < (size_t)K * dim; e++) g.mean[e] = c[e];
-        for (double v : g.mean)
-            if (!std::isfinite(v)) fail("k-means initialisation left an empty cluster (the reference divides by zero here as well)");
-    } else {
-        for (int k = 0; k < K; k++) {                         // gmm.cc:346-349
-            const long pick = trainer_random.rand_int((int)n);
-            for (int d = 0; d < dim; d++) g.mean[(size_t)k * dim + d] = X[(size_t)pick * dim + d];
-        }
+    DeviceBackend dev{X, n, dim};
+    KmStart s;
+    const std::string why = init_like_reference(dev.ops(), X, n, dim, K, std::max(1, param.concurrency), param.init_with_kmeans, param.verbosity, seed, s);
+    // (a refused start leaves the handle what it got as far as: sigma, then mean)
+    if (!s.sigma.empty()) {
+        g.sigma.resize((size_t)K * dim);
+        for (int k = 0; k < K; k++) std::copy(s.sigma.begin(), s.sigma.end(), g.sigma.begin() + (size_t)k * dim);
     }
+    if (!s.mean.empty()) g.mean = s.mean;
+    if (!why.empty()) fail("%s", why.c_str());
     g.weights.assign(K, 1.0 / K);                             // gmm.cc:356-360
     g.drop_single();
 }
 
-}  // namespace sr
-
-namespace sr {
-// Labels of the library's seeded k-means (k-means|| + Lloyd on the full data, then the nearest centre of every point): the
-// initialisation of a full-covariance fit (gmm_full.hip, sklearn's init_params='kmeans' with this library's k-means).
 std::vector<int> kmeans_labels(const float *X, long n, int dim, int K, long seed) {
-    ensure_device();
-    kws().X.upload(X, (size_t)n * dim);
-    RandStream rs(seed);
-    const std::vector<double> c = kmeans_parallel_init(X, n, dim, K, 1, rs, 0);
-    std::vector<double> dist((size_t)n);
-    std::vector<int> belong((size_t)n);
-    device_assign(n, dim, c, 0, K, dist, belong, true);
-    return belong;
+    DeviceBackend dev{X, n, dim};
+    std::vector<int> labels;
+    const std::string why = kmeans_labels_on(dev.ops(), X, n, dim, K, seed, labels);
+    if (!why.empty()) fail("%s", why.c_str());
+    return labels;
 }
+
 }  // namespace sr

@@ -21,6 +21,7 @@
 #include "score.hpp"
 #include "em_f64_dev.hpp"
 #include "map_plan.hpp"
+#include "ref_rand.hpp"
 
 #include "../../include/pygmm_hip.h"
 
@@ -36,7 +37,6 @@ namespace sr {
 int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param, long seed);      // em.hip
 int em_stats_engine();
 int reference_side_effects();
-void burn_reference_rand(int count);            // kmeans_init.hip
 
 namespace {
 
