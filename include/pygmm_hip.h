@@ -398,6 +398,8 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    the groups run in chunks that fit.  Results do not depend on it, bit for bit.
  *   "norm_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the scratch of sr_score_norm's as2 mode (the selections, the shifted
  *                    copies and the four products): the test segments run in chunks that fit.  Results do not depend on it, bit for bit.
+ *   "plda_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of what sr_plda_score keeps per test segment (its centred row, its row
+ *                    of X P_c and its two quadratic forms): the segments run in chunks that fit.  Results do not depend on it, bit for bit.
  *   "jfa_lds_rows"   largest R whose blocks the JFA factorisation copies into LDS (1 .. 112; 0 = automatic: 112); above it the
  *                    block is factored in place in global memory with panels in LDS.  1 forces that path at any R > 1.
  * The rest select kernel variants for A/B runs and tests. */
@@ -827,6 +829,70 @@ int sr_score_norm_select(int64_t rows, int64_t C, int top_n, const double *X /*[
                          double *mu /*[rows] or NULL*/, double *sigma /*[rows] or NULL*/);
 int sr_score_norm_plan(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, int64_t scratch_bytes, int n_cu, int64_t *out,
                        int n_out);
+
+/* ---- The i-vector back end (csrc/plda.hip, csrc/plda_plan.cpp): what follows i-vector extraction (sr_jfa_factors with one group per
+ * session and the total-variability matrix as W), on the device, float64 throughout, row-major, vectors of 1 <= R <= 512 dimensions.
+ * sr_backend_fit: kind 0 (whiten): mu [R] the mean of the rows of X [n][R] and A [R][R] = chol(Sigma)^-1, Sigma the total covariance
+ *   (ddof = 0), so that (X - mu) A^T has covariance I; kind 1 (wccn): A = chol(W)^-1, W the within-class covariance of the rows about
+ *   the means of their classes ids [n] in 0 .. n_labels - 1.  A is lower triangular.  A covariance that does not factor is refused.
+ * sr_backend_apply: Y [n][R] = (X - mu) A^T; with length_norm != 0 every row scaled to unit 2-norm, a row whose norm is 0 or not finite
+ *   becoming exact zeros and counted in zero_rows (or NULL).
+ * sr_cosine_score: out [J][T] = <e_j, x_t> / (|e_j| |x_t|): one product and the row norms; a pair with a norm of 0 scores 0.0.
+ * Two-covariance Gaussian PLDA: x_ij = mu + y_i + e_ij, y ~ N(0, Sb), e ~ N(0, Sw), Sb and Sw full [R][R].
+ * sr_plda_train: n_iter EM rounds on X [n][R] with 0-based speaker labels ids [n] (every label 0 .. n_labels - 1 occurs), from the Sb
+ *   and Sw given (default_start 0), or with both starting from half the total covariance T2 / (2 n) formed on the device
+ *   (default_start 1: what Sb and Sw hold is not read); they receive the result.  mu [R] (or NULL) receives the mean of the rows,
+ *   formed once in row order.  Per round, with
+ *   n_i the rows of speaker i, f_i the sum of its centred rows, T2 the scatter of all centred rows:
+ *     Phi_c = (Sb^-1 + c Sw^-1)^-1 per distinct count c      yhat_i = Phi_{n_i} Sw^-1 f_i      Sb <- (sum_i Phi_{n_i} + Yhat^T Yhat) / S
+ *     Sw <- (T2 - F^T Yhat - Yhat^T F + Yhat^T diag(n_i) Yhat + sum_i n_i Phi_{n_i}) / n
+ *   The speakers are sorted by count, so a count class is a contiguous row range: one factorisation and one inverse per distinct count
+ *   per round.  n_iter rounds in one call give the bits of n_iter calls of one round.  iterations / n_classes / stop (each or NULL):
+ *   the rounds done, the distinct counts, and why the rounds ended: 0 all ran, 1 Sb did not factor, 2 Sw did not, 3 a Sb^-1 + c Sw^-1
+ *   did not, 4 a round produced a non-finite value.  On 1 .. 4 Sb and Sw hold the last pair that factored (the input pair when the
+ *   first round stops) and `iterations` says which; no NaN reaches the outputs.  The pair the LAST round returns is checked for
+ *   finite values only, not factored: stop 0 does not promise that a further call, or sr_plda_score, can factor it -- that call
+ *   says so itself (iterations 0 and a stop code; bad_classes).
+ * sr_plda_score: out [J][T], the log-likelihood ratio of "segment t is of model j's speaker" against "of another"; model j has
+ *   enrol_n[j] >= 1 enrolment vectors whose raw sum is E[j] ([J][R]); X [T][R] the test vectors.  With c = enrol_n[j],
+ *   yhat_j = Phi_c Sw^-1 (E[j] - c mu), P_c = (Phi_c + Sw)^-1, P_0 = (Sb + Sw)^-1, x = x_t - mu:
+ *     out[j][t] = -1/2 ln det(Phi_c + Sw) - 1/2 (x - yhat_j)^T P_c (x - yhat_j) + 1/2 ln det(Sb + Sw) + 1/2 x^T P_0 x
+ *   The cross term Yhat_c P_c X^T is one product per distinct count straight into the output's rows; the test segments run in chunks
+ *   under "plda_scratch_mib".  A score is the same bits for its model alone, its segment alone, in any batch and under any bound.
+ *   A count class whose blocks do not factor gets exact zeros in its rows and is counted in bad_classes (or NULL).
+ *   Outside the bound, growing with the number nc of DISTINCT counts (at most J): a Phi_c and a P_c per count, (3 nc + 6) R^2 doubles
+ *   with the factorisation's scratch, and one X P_c product over all T segments per count -- 2 T R^2 operations each against the
+ *   cross term's 2 J T R in all.  A trial list with many distinct counts pays for each; enrol_mode "average" has one.
+ * sr_plda_plan: what a call decides (csrc/plda_plan.cpp; host only when n_cu > 0), for tests.  kind 0: training, counts = ids [rows],
+ *   groups = n_labels; kind 1: scoring, counts = enrol_n [rows], groups ignored.  Writes 36 fields (n_out >= 36) and returns 36, -1 on
+ *   refusal: kind, R, rows, groups, T, distinct counts, vectors per launch of T2's sum and the launches, speakers per launch of the
+ *   sums over speakers and the launches, test segments per chunk and the chunks, bytes per segment and of a full chunk inside the
+ *   bound, bytes of the R x R blocks and of the row arrays, the factorisation path (0 LDS, 1 global memory) and the largest R of the
+ *   LDS path, the factorisation's and the GEMM's LDS bytes, the grids of the centring (x), the class sums (x, y), the factorisations
+ *   (x), the widest row product (x, y), the R x R sums (x, y), the row dot products (x), the cross term (x, y), the assembly (x), the
+ *   factorisation's rounds over the chip, the built limits of R and of the rows, the column groups (of four) of the factor's
+ *   inverse on the global-memory path (0 on the LDS path).  perm (or NULL) [groups]: sorted position -> label or model;
+ *   classes (or NULL) [3 * groups]: (count, first sorted position, size) of every class, ascending count.
+ * Refused, before the device is touched, with a message that names the argument and the remedy: R < 1 or R > 512; n, J or T < 1 or
+ * above 65535 * 64; a label out of range or without a row; a non-finite input; enrol_n < 1; an Sb or Sw that is not symmetric; a
+ * bound below one chunk.  Refused in a process forked after the GPU runtime was initialised.
+ * Timer kinds (none is added): SR_T_JFA_GRAM the elementwise kernels, the class sums and the row dot products; SR_T_JFA_FACTOR the
+ * factorisations; SR_T_JFA_GEMM_B the products with Sw^-1, P_c and A; SR_T_JFA_GEMM_L those with Phi_c and Yhat P_c; SR_T_JFA_GEMM_A
+ * the sums over vectors and speakers; SR_T_JFA_GEMM_C the cross term and the cosine's product; SR_T_JFA_UPDATE the new covariances,
+ * the length normalisation and the score assembly. */
+int sr_backend_fit(int kind, int64_t n, int R, const double *X /*[n][R]*/, const int64_t *ids /*[n], wccn; else NULL*/, int64_t n_labels,
+                   double *mu /*[R]*/, double *A /*[R][R]*/);
+int sr_backend_apply(int64_t n, int R, const double *X /*[n][R]*/, const double *mu /*[R]*/, const double *A /*[R][R]*/, int length_norm,
+                     double *Y /*[n][R]*/, int64_t *zero_rows /*or NULL*/);
+int sr_cosine_score(int64_t J, int64_t T, int R, const double *E /*[J][R]*/, const double *X /*[T][R]*/, double *out /*[J][T]*/);
+int sr_plda_train(int64_t n, int R, const double *X /*[n][R]*/, const int64_t *ids /*[n]*/, int64_t n_labels, int n_iter, int default_start,
+                  double *mu /*[R] or NULL*/, double *Sb /*[R][R] in/out*/, double *Sw /*[R][R] in/out*/, int *iterations /*or NULL*/,
+                  int *n_classes /*or NULL*/, int *stop /*or NULL*/);
+int sr_plda_score(int64_t J, int64_t T, int R, const double *mu /*[R]*/, const double *Sb /*[R][R]*/, const double *Sw /*[R][R]*/,
+                  const double *E /*[J][R]*/, const int64_t *enrol_n /*[J]*/, const double *X /*[T][R]*/, double *out /*[J][T]*/,
+                  int64_t *bad_classes /*or NULL*/);
+int sr_plda_plan(int kind, int R, int64_t rows, int64_t groups, int64_t T, const int64_t *counts /*[rows]*/, int64_t scratch_bytes, int lds_rows,
+                 int n_cu, int64_t *out, int n_out, int64_t *perm /*[groups] or NULL*/, int64_t *classes /*[3 * groups] or NULL*/);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,7 @@ EXT_SYMBOLS = [
     "sr_multi_slot_pieces", "sr_multi_plan",
     "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
     "sr_score_norm", "sr_score_norm_select", "sr_score_norm_plan",
+    "sr_backend_fit", "sr_backend_apply", "sr_cosine_score", "sr_plda_train", "sr_plda_score", "sr_plda_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -255,6 +256,12 @@ def lib():
         "sr_score_norm": (i32, [i32, i64, i64, i64, i64, i32, dp, dp, dp, dp, dp, C.POINTER(i64)]),
         "sr_score_norm_select": (i32, [i64, i64, i32, dp, C.POINTER(i64), dp, dp]),
         "sr_score_norm_plan": (i32, [i32, i64, i64, i64, i64, i32, i64, i32, C.POINTER(i64), i32]),
+        "sr_backend_fit": (i32, [i32, i64, i32, dp, C.POINTER(i64), i64, dp, dp]),
+        "sr_backend_apply": (i32, [i64, i32, dp, dp, dp, i32, dp, C.POINTER(i64)]),
+        "sr_cosine_score": (i32, [i64, i64, i32, dp, dp, dp]),
+        "sr_plda_train": (i32, [i64, i32, dp, C.POINTER(i64), i64, i32, i32, dp, dp, dp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "sr_plda_score": (i32, [i64, i64, i32, dp, dp, dp, dp, C.POINTER(i64), dp, dp, C.POINTER(i64)]),
+        "sr_plda_plan": (i32, [i32, i32, i64, i64, i64, C.POINTER(i64), i64, i32, i32, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -593,6 +600,33 @@ def score_norm_plan(mode: str, J: int, T: int, Cz: int, Ct: int, top_n: int = 0,
     check(lib().sr_score_norm_plan(m, int(J), int(T), int(Cz), int(Ct), int(top_n), int(scratch_bytes), int(n_cu), v, 40), "sr_score_norm_plan")
     d = dict(zip(NORM_PLAN_FIELDS, (int(x) for x in v)))
     d["mode"] = NORM_MODES[d["mode"]]
+    return d
+
+
+PLDA_PLAN_FIELDS = ("kind", "R", "rows", "groups", "T", "n_classes", "sum_chunk", "sum_chunks", "grp_chunk", "grp_chunks", "chunk", "n_chunks",
+                    "seg_bytes", "bytes_scratch", "bytes_blocks", "bytes_rows", "path", "lds_rows", "factor_lds", "gemm_lds", "centre_grid",
+                    "class_sums_x", "class_sums_y", "invert_grid", "gemm_rows_x", "gemm_rows_y", "gemm_acc_x", "gemm_acc_y", "rowdot_grid",
+                    "gemm_cross_x", "gemm_cross_y", "assemble_grid", "invert_rounds", "max_R", "max_rows", "tri_inverse_y")
+
+
+def plda_plan(kind: str, R: int, counts, T: int = 0, n_labels=None, scratch_bytes: int = 1 << 30, lds_rows: int = 0, n_cu: int = 256) -> dict:
+    """What ``sr_plda_train`` (``kind`` "train": ``counts`` the 0-based labels, one per training vector) or ``sr_plda_score`` ("score":
+    ``counts`` the models' enrolment counts, ``T`` test segments) decides (csrc/plda_plan.cpp; no GPU needed when n_cu > 0): the
+    refusals, the count classes ("classes": (count, first sorted position, size), ascending count) and the permutation that sorts
+    the speakers or models by count ("perm": sorted position -> label or model), the chunks, the factorisation path, the bytes, the
+    grid of every launch and the built limits."""
+    counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+    k = ("train", "score").index(kind) if kind in ("train", "score") else -1
+    rows = int(counts.size)
+    groups = rows if k != 0 else int(n_labels if n_labels is not None else (counts.max() + 1 if rows else 0))
+    width = max(1, min(groups, rows) if k == 0 else rows)
+    v, perm, classes = (C.c_int64 * 36)(), np.zeros(width, dtype=np.int64), np.zeros(3 * width, dtype=np.int64)
+    check(lib().sr_plda_plan(k, int(R), rows, groups, int(T), as_i64p(counts), int(scratch_bytes), int(lds_rows), int(n_cu), v, 36, as_i64p(perm),
+                             as_i64p(classes)), "sr_plda_plan")
+    d = dict(zip(PLDA_PLAN_FIELDS, (int(x) for x in v)))
+    d["kind"] = kind
+    d["perm"] = perm[:d["groups"]]
+    d["classes"] = [tuple(int(x) for x in classes[3 * c:3 * c + 3]) for c in range(d["n_classes"])]
     return d
 
 

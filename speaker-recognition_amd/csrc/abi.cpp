@@ -17,6 +17,7 @@
 #include "bw_plan.hpp"
 #include "jfa_plan.hpp"
 #include "norm_plan.hpp"
+#include "plda_plan.hpp"
 #include "map_plan.hpp"
 #include "ref_rand.hpp"
 
@@ -46,6 +47,15 @@ void score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_
 void score_norm_select(int64_t rows, int64_t C, int top_n, const double *X, int64_t *idx, double *mu, double *sigma);
 void set_norm_scratch_mib(long v);
 long norm_scratch_mib();
+// plda.hip
+void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S, int n_iter, int default_start, double *mu_out, double *Sb,
+                double *Sw, int *iterations, int *n_classes, int *stop);
+void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb, const double *Sw, const double *E, const int64_t *enrol_n,
+                const double *X, double *out, int64_t *bad_classes);
+void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids, int64_t S, double *mu_out, double *A);
+void backend_apply(int64_t n, int R, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows);
+void cosine_score(int64_t J, int64_t T, int R, const double *E, const double *X, double *out);
+void set_plda_scratch_mib(long v);
 // silence.hip
 void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
 void set_silence_block(long v);
@@ -1264,6 +1274,79 @@ int sr_score_norm_plan(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, i
     SR_CATCH(-1)
 }
 
+// ---- the i-vector back end (plda.hip).  Every refusal comes before the device is touched. ----
+
+int sr_backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids, int64_t n_labels, double *mu, double *A) {
+    SR_TRY
+    backend_fit(kind, n, R, X, ids, n_labels, mu, A);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_backend_apply(int64_t n, int R, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows) {
+    SR_TRY
+    backend_apply(n, R, X, mu, A, length_norm, Y, zero_rows);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_cosine_score(int64_t J, int64_t T, int R, const double *E, const double *X, double *out) {
+    SR_TRY
+    cosine_score(J, T, R, E, X, out);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t n_labels, int n_iter, int default_start, double *mu, double *Sb,
+                  double *Sw, int *iterations, int *n_classes, int *stop) {
+    SR_TRY
+    plda_train(n, R, X, ids, n_labels, n_iter, default_start, mu, Sb, Sw, iterations, n_classes, stop);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb, const double *Sw, const double *E, const int64_t *enrol_n,
+                  const double *X, double *out, int64_t *bad_classes) {
+    SR_TRY
+    plda_score(J, T, R, mu, Sb, Sw, E, enrol_n, X, out, bad_classes);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_plda_plan(int kind, int R, int64_t rows, int64_t groups, int64_t T, const int64_t *counts, int64_t scratch_bytes, int lds_rows, int n_cu,
+                 int64_t *out, int n_out, int64_t *perm, int64_t *classes) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 36) fail("sr_plda_plan writes 36 fields");
+    if (kind != PLDA_TRAIN && kind != PLDA_SCORE) fail("sr_plda_plan: the kind is 0 (training) or 1 (scoring)");
+    std::string why;
+    PldaPlan p;
+    auto plan = [&](int cu) {
+        const bool ok = kind == PLDA_TRAIN ? plan_plda_train(rows, R, counts, groups, lds_rows, cu, p, why)
+                                           : plan_plda_score(rows, T, R, counts, scratch_bytes, lds_rows, cu, p, why);
+        if (!ok) fail("%s", why.c_str());
+    };
+    if (n_cu > 0) {
+        plan(n_cu);
+    } else {
+        plan(1);                               // the refusals first
+        ensure_device();
+        plan(ctx().n_cu);
+    }
+    const int64_t v[36] = {p.kind, p.R, p.rows, p.groups, p.T, (int64_t)p.classes.size(), p.sum_chunk, p.sum_chunks, p.grp_chunk, p.grp_chunks,
+                           p.chunk, p.n_chunks, p.seg_bytes, p.bytes_scratch, p.bytes_blocks, p.bytes_rows, p.path, p.lds_rows, p.factor_lds,
+                           p.gemm_lds, p.centre.x, p.class_sums.x, p.class_sums.y, p.invert.x, p.gemm_rows.x, p.gemm_rows.y, p.gemm_acc.x,
+                           p.gemm_acc.y, p.rowdot.x, p.gemm_cross.x, p.gemm_cross.y, p.assemble.x, p.invert_rounds,
+                           PLDA_MAX_R, PLDA_MAX_ROWS, p.tri.y};
+    std::memcpy(out, v, sizeof v);
+    if (perm) std::memcpy(perm, p.perm.data(), p.perm.size() * sizeof(int64_t));
+    if (classes)
+        for (size_t c = 0; c < p.classes.size(); c++)
+            classes[3 * c] = p.classes[c].count, classes[3 * c + 1] = p.classes[c].start, classes[3 * c + 2] = p.classes[c].size;
+    return 36;
+    SR_CATCH(-1)
+}
+
 int sr_train_f32(GMM *gmm, GMM *ubm_or_null, const float *X, long n, int dim,
                  const struct Parameter *param, long seed) {
     SR_TRY
@@ -1438,6 +1521,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "norm_scratch_mib") {
         if (value < 1 || value > (1L << 20)) fail("norm_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(NORM_DEFAULT_SCRATCH >> 20));
         set_norm_scratch_mib(value);
+    } else if (k == "plda_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("plda_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(PLDA_DEFAULT_SCRATCH >> 20));
+        set_plda_scratch_mib(value);
     } else if (k == "jfa_lds_rows") {
         if (value < 0 || value > JFA_LDS_MAX_R) fail("jfa_lds_rows must be 0 (automatic) or 1 .. %d rows", JFA_LDS_MAX_R);
         set_jfa_lds_rows(value);

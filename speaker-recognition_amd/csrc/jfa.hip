@@ -6,7 +6,7 @@
 //   y_g = L_g^-1 b_g                         Q_g = L_g^-1 + y_g y_g^T
 //   A_c = sum_g N[g][c] Q_g                  C   = sum_g y_g Fc_g^T                W_c <- A_c^-1 C_c
 // Everything is float64.  Four kernels, none touching the pass counters (trial scoring, jfa_score.hip, launches the first three
-// through the launchers declared in jfa_dev.hpp, which also holds the Cholesky of the fourth):
+// through the launchers declared in jfa_dev.hpp, which also holds the Cholesky and the two inverse routines of the fourth):
 //   jfa_scale_kernel    W ./ E, once per call (the B operand of the b product).
 //   jfa_gram_kernel     P [K][R][R]: a 16 x 16 tile of one mixture per workgroup, the two row panels of W_c through LDS; the product
 //                       W[i][d] W[j][d] is formed first, so P is symmetric to the bit.
@@ -157,42 +157,6 @@ __device__ void jfa_solve(const double *M, int R, double *T, int64_t ldt, int nr
         for (int64_t e = tid; e < n; e += JFA_WG) {
             const int i = (int)(e / nrhs), r = (int)(e % nrhs);
             T[i * ldt + r] = __builtin_fma(-M[(int64_t)j * R + i], T[j * ldt + r], T[i * ldt + r]);
-        }
-        __syncthreads();
-    }
-}
-
-// The factor's inverse X = F^-1 over F, row by row: X[i][j] = -(sum_{j <= k < i} F[i][k] X[k][j]) / F[i][i], X[i][i] = 1 / F[i][i].
-// Row i of F is needed by row i of X only, so it goes through `row` and is overwritten.
-__device__ void jfa_tri_inverse(double *M, int R, double *row /* [R] */) {
-    const int tid = threadIdx.x;
-    for (int i = 0; i < R; i++) {
-        for (int k = tid; k <= i; k += JFA_WG) row[k] = M[(int64_t)i * R + k];
-        __syncthreads();
-        const double dii = row[i];
-        for (int j = tid; j < i; j += JFA_WG) {
-            double s = 0.0;
-            for (int k = j; k < i; k++) s = __builtin_fma(row[k], M[(int64_t)k * R + j], s);
-            M[(int64_t)i * R + j] = -s / dii;
-        }
-        if (tid == 0) M[(int64_t)i * R + i] = 1.0 / dii;
-        __syncthreads();
-    }
-}
-
-// X^T X (+ y y^T) over X, row by row, mirrored into the upper triangle: row i of the result needs rows >= i of X, which later rows
-// do not touch.  Column i of X goes through `col`.
-__device__ void jfa_inverse_from_tri(double *M, int R, double *col /* [R] */, const double *y /* [R] or null */) {
-    const int tid = threadIdx.x;
-    for (int i = 0; i < R; i++) {
-        for (int k = i + tid; k < R; k += JFA_WG) col[k] = M[(int64_t)k * R + i];
-        __syncthreads();
-        for (int j = tid; j <= i; j += JFA_WG) {
-            double s = 0.0;
-            for (int k = i; k < R; k++) s = __builtin_fma(col[k], M[(int64_t)k * R + j], s);
-            if (y) s += y[i] * y[j];
-            M[(int64_t)i * R + j] = s;
-            M[(int64_t)j * R + i] = s;
         }
         __syncthreads();
     }

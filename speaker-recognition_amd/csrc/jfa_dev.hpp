@@ -1,6 +1,7 @@
-// jfa_dev.hpp -- what jfa.hip (factor estimation), jfa_score.hip (trial scoring) and jfa_stats.hip (resident statistics, centring,
-// z / d) share: the two handle types, the panel Cholesky of one R x R block by one workgroup, and the host launchers each of the
-// three defines for the others (bw_stats.hip includes it for the statistics handle its resident entry fills).
+// jfa_dev.hpp -- what jfa.hip (factor estimation), jfa_score.hip (trial scoring), jfa_stats.hip (resident statistics, centring,
+// z / d) and plda.hip (the i-vector back end) share: the two handle types, the panel Cholesky of one R x R block by one workgroup
+// and the two routines that turn its factor into the inverse, and the host launchers each of the first three defines for the
+// others (bw_stats.hip includes it for the statistics handle its resident entry fills).
 #pragma once
 
 #include "jfa_plan.hpp"
@@ -96,6 +97,42 @@ SRStats *stats_new(int64_t n, int K, int D);      // an empty registered handle 
         __syncthreads();                       // the panel is consumed, the trailing block written
     }
     return true;
+}
+
+// The factor's inverse X = F^-1 over F, row by row: X[i][j] = -(sum_{j <= k < i} F[i][k] X[k][j]) / F[i][i], X[i][i] = 1 / F[i][i].
+// Row i of F is needed by row i of X only, so it goes through `row` and is overwritten.
+[[maybe_unused]] static __device__ void jfa_tri_inverse(double *M, int R, double *row /* [R] */) {
+    const int tid = threadIdx.x;
+    for (int i = 0; i < R; i++) {
+        for (int k = tid; k <= i; k += JFA_WG) row[k] = M[(int64_t)i * R + k];
+        __syncthreads();
+        const double dii = row[i];
+        for (int j = tid; j < i; j += JFA_WG) {
+            double s = 0.0;
+            for (int k = j; k < i; k++) s = __builtin_fma(row[k], M[(int64_t)k * R + j], s);
+            M[(int64_t)i * R + j] = -s / dii;
+        }
+        if (tid == 0) M[(int64_t)i * R + i] = 1.0 / dii;
+        __syncthreads();
+    }
+}
+
+// X^T X (+ y y^T) over X, row by row, mirrored into the upper triangle: row i of the result needs rows >= i of X, which later rows
+// do not touch.  Column i of X goes through `col`.
+[[maybe_unused]] static __device__ void jfa_inverse_from_tri(double *M, int R, double *col /* [R] */, const double *y /* [R] or null */) {
+    const int tid = threadIdx.x;
+    for (int i = 0; i < R; i++) {
+        for (int k = i + tid; k < R; k += JFA_WG) col[k] = M[(int64_t)k * R + i];
+        __syncthreads();
+        for (int j = tid; j <= i; j += JFA_WG) {
+            double s = 0.0;
+            for (int k = i; k < R; k++) s = __builtin_fma(col[k], M[(int64_t)k * R + j], s);
+            if (y) s += y[i] * y[j];
+            M[(int64_t)i * R + j] = s;
+            M[(int64_t)j * R + i] = s;
+        }
+        __syncthreads();
+    }
 }
 
 #endif
