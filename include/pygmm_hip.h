@@ -894,6 +894,61 @@ int sr_plda_score(int64_t J, int64_t T, int R, const double *mu /*[R]*/, const d
 int sr_plda_plan(int kind, int R, int64_t rows, int64_t groups, int64_t T, const int64_t *counts /*[rows]*/, int64_t scratch_bytes, int lds_rows,
                  int n_cu, int64_t *out, int n_out, int64_t *perm /*[groups] or NULL*/, int64_t *classes /*[3 * groups] or NULL*/);
 
+/* ---- The symmetric eigen-solver and what the i-vector back end builds on it (csrc/eig.hip, csrc/eig_plan.cpp, csrc/backend_eig.hip):
+ * LDA and PLDA scoring with the model diagonalised once.  On the device, float64 throughout, row-major, 1 <= R <= 512.
+ * sr_sym_eig: A [R][R] symmetric (the lower triangle is read; not assumed definite) -> w [R] DESCENDING and V [R][R], column k the unit
+ *   eigenvector of w[k].  Signs: every vector's component of largest magnitude is positive, the lowest index winning a tie.  Two-sided
+ *   block Jacobi: blocks of 32 columns (an odd number padded with an empty phantom block), a sweep the blocks - 1 rounds of the
+ *   round-robin tournament, a round three launches (the pairs' 64 x 64 sub-problems by cyclic Jacobi rotations in LDS, the column
+ *   update of A and V, the row update of A); R <= 64 is one launch.  Stops when the largest off-diagonal magnitude is
+ *   <= R 2^-52 max|A|, or at the cap of 40 sweeps.  sweeps / converged (each or NULL): the sweeps taken; 1, or 0 when the cap was
+ *   reached -- w and V then hold what there is, and the return value is still 0.  The same bits from run to run.
+ * sr_gen_eig: Sb v = psi Sw v for symmetric Sb and positive definite Sw [R][R]: L = chol(Sw), M = L^-1 Sb L^-T (symmetrised),
+ *   M = Q diag(psi) Q^T by the solver above, V = L^-T Q, so that V^T Sw V = I and V^T Sb V = diag(psi), psi [R] descending, the signs
+ *   those of Q.  status (or NULL): 0 ok; 1 Sw did not factor: psi and V are exact zeros; 2 the sweep cap was reached.
+ * sr_lda_fit: X [n][R] with 0-based class labels ids [n] (every label 0 .. n_labels - 1 occurs) -> mu [R] the mean of the rows (formed
+ *   in row order), and with Sw the within-class covariance about the class means (ddof 0, what sr_backend_fit kind 1 factors) and
+ *   Sb = (1 / n) sum_i n_i (m_i - mu)(m_i - mu)^T (so that Sb + Sw is the total covariance): A [P][R] the first P generalised
+ *   eigenvectors, as rows, and psi [P] their values, descending.  A Sw A^T = I_P: the projection arrives WCCN-normalised.
+ *   1 <= P <= min(R, n_labels - 1).  An Sw that does not factor is refused as sr_backend_fit refuses it.
+ * sr_backend_project: Y [n][P] = (X - mu) A^T for A [P][R], 1 <= P <= R; with length_norm != 0 every row scaled to unit 2-norm, a row
+ *   whose norm is 0 or not finite becoming exact zeros and counted in zero_rows (or NULL), as sr_backend_apply does.
+ * sr_plda_score_diag: sr_plda_score's result from the model diagonalised: mu [R], V [R][R] and psi [R] of sr_gen_eig(Sb, Sw); E,
+ *   enrol_n, X, out, bad_classes as sr_plda_score takes them.  With u_t = V^T (x_t - mu), G_j = V^T (E[j] - c mu), c = enrol_n[j],
+ *   h_cd = psi_d / (c psi_d + 1), s_cd = 1 + h_cd, s_0d = 1 + psi_d, m_jd = h_cd G_jd:
+ *     out[j][t] = -1/2 sum_d ln s_cd - 1/2 (sum_d u_td^2 / s_cd - 2 sum_d (m_jd / s_cd) u_td + sum_d m_jd^2 / s_cd)
+ *                 + 1/2 sum_d ln s_0d + 1/2 sum_d u_td^2 / s_0d
+ *   No factorisation: two products with V, ONE cross product over all models whatever their counts, one product U.^2 [T][R] by
+ *   [R][classes + 1]; the segments run in chunks under "plda_scratch_mib" (2 R + classes + 1 doubles a segment).  The same bits for a
+ *   model alone, a segment alone, in any batch, under any bound.  A psi that is not finite or below -1e-9 of the largest magnitude
+ *   zeroes and counts every class; a class with a (c + 1) psi_d + 1 <= 0 -- its s_cd would not be positive; c psi_d + 1 <= 0 is
+ *   among these -- is zeroed and counted (a backstop behind the first rule: it can only be met by a psi whose largest magnitude is
+ *   above 1e9 / (c + 1)).  No NaN is written.
+ * sr_eig_plan: what sr_sym_eig decides (csrc/eig_plan.cpp; host only when n_cu > 0), for tests.  Writes 24 fields (n_out >= 24) and
+ *   returns 24, -1 on refusal: R, the block width b, the blocks, 1 with a phantom block, the rounds of a sweep, the pairs of a round
+ *   (the phantom's included), 1 on the single-launch path (R <= 2 b: no rounds), the sweep cap, the cap of a pair's inner sweeps,
+ *   the LDS bytes of the solve and of the update stages, the grid of the solve stage (the working pairs), of the column stage (x, y, z)
+ *   and of the row stage (x, y), the launches of a sweep, the bytes of the working arrays, the rounds the widest launch makes over
+ *   the chip, the built limit of R, the rows of an update tile, 2 b, the lanes of a workgroup.  schedule (or NULL)
+ *   [rounds][pairs][2]: the block pairs (p < q) of every round; q == blocks names the phantom: that pair does no work.
+ * Refused, before the device is touched, with a message that names the argument and the remedy: R < 1 or R > 512; a null argument; a
+ * non-finite value; a matrix that is not symmetric (sr_plda_score's rule); P out of range; the label and row errors of
+ * sr_backend_fit; enrol_n < 1; a bound below one chunk.  Refused in a process forked after the GPU runtime was initialised.
+ * Timer kinds (none is added): SR_T_JFA_FACTOR the solver's launches and the Cholesky; SR_T_JFA_GEMM_C every product of these calls;
+ * SR_T_JFA_GEMM_A the covariance sums of sr_lda_fit; SR_T_JFA_GRAM the centring, the class sums and the row dot products;
+ * SR_T_JFA_UPDATE the elementwise kernels, the length normalisation and the score assembly. */
+int sr_sym_eig(int R, const double *A /*[R][R]*/, double *w /*[R]*/, double *V /*[R][R]*/, int *sweeps /*or NULL*/, int *converged /*or NULL*/);
+int sr_gen_eig(int R, const double *Sb /*[R][R]*/, const double *Sw /*[R][R]*/, double *psi /*[R]*/, double *V /*[R][R]*/, int *sweeps /*or NULL*/,
+               int *status /*or NULL*/);
+int sr_lda_fit(int64_t n, int R, const double *X /*[n][R]*/, const int64_t *ids /*[n]*/, int64_t n_labels, int P, double *mu /*[R]*/,
+               double *A /*[P][R]*/, double *psi /*[P]*/);
+int sr_backend_project(int64_t n, int R, int P, const double *X /*[n][R]*/, const double *mu /*[R]*/, const double *A /*[P][R]*/, int length_norm,
+                       double *Y /*[n][P]*/, int64_t *zero_rows /*or NULL*/);
+int sr_plda_score_diag(int64_t J, int64_t T, int R, const double *mu /*[R]*/, const double *V /*[R][R]*/, const double *psi /*[R]*/,
+                       const double *E /*[J][R]*/, const int64_t *enrol_n /*[J]*/, const double *X /*[T][R]*/, double *out /*[J][T]*/,
+                       int64_t *bad_classes /*or NULL*/);
+int sr_eig_plan(int R, int n_cu, int64_t *out, int n_out, int *schedule /*[rounds][pairs][2] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ EXT_SYMBOLS = [
     "sr_map_fit_batch", "sr_map_fit_batch_error", "sr_map_fit_batch_stats", "sr_map_fit_batch_bytes", "sr_map_fit_plan",
     "sr_score_norm", "sr_score_norm_select", "sr_score_norm_plan",
     "sr_backend_fit", "sr_backend_apply", "sr_cosine_score", "sr_plda_train", "sr_plda_score", "sr_plda_plan",
+    "sr_sym_eig", "sr_gen_eig", "sr_lda_fit", "sr_backend_project", "sr_plda_score_diag", "sr_eig_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -262,6 +263,12 @@ def lib():
         "sr_plda_train": (i32, [i64, i32, dp, C.POINTER(i64), i64, i32, i32, dp, dp, dp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "sr_plda_score": (i32, [i64, i64, i32, dp, dp, dp, dp, C.POINTER(i64), dp, dp, C.POINTER(i64)]),
         "sr_plda_plan": (i32, [i32, i32, i64, i64, i64, C.POINTER(i64), i64, i32, i32, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64)]),
+        "sr_sym_eig": (i32, [i32, dp, dp, dp, C.POINTER(i32), C.POINTER(i32)]),
+        "sr_gen_eig": (i32, [i32, dp, dp, dp, dp, C.POINTER(i32), C.POINTER(i32)]),
+        "sr_lda_fit": (i32, [i64, i32, dp, C.POINTER(i64), i64, i32, dp, dp, dp]),
+        "sr_backend_project": (i32, [i64, i32, i32, dp, dp, dp, i32, dp, C.POINTER(i64)]),
+        "sr_plda_score_diag": (i32, [i64, i64, i32, dp, dp, dp, dp, C.POINTER(i64), dp, dp, C.POINTER(i64)]),
+        "sr_eig_plan": (i32, [i32, i32, C.POINTER(i64), i32, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -627,6 +634,24 @@ def plda_plan(kind: str, R: int, counts, T: int = 0, n_labels=None, scratch_byte
     d["kind"] = kind
     d["perm"] = perm[:d["groups"]]
     d["classes"] = [tuple(int(x) for x in classes[3 * c:3 * c + 3]) for c in range(d["n_classes"])]
+    return d
+
+
+EIG_PLAN_FIELDS = ("R", "b", "blocks", "phantom", "rounds", "pairs", "single", "max_sweeps", "inner_sweeps", "solve_lds", "update_lds", "solve_grid",
+                   "cols_x", "cols_y", "cols_z", "rows_x", "rows_y", "launches_per_sweep", "bytes_work", "pair_rounds", "max_R", "tile_rows",
+                   "sub_problem", "wg")
+
+
+def eig_plan(R: int, n_cu: int = 256) -> dict:
+    """What ``sr_sym_eig`` decides for an R x R matrix (csrc/eig_plan.cpp; no GPU needed when n_cu > 0): the block width ``b``, the
+    blocks and the phantom, the rounds and pairs of a sweep, the single-launch path, the caps, the LDS bytes, the grids, and
+    "schedule": [rounds][pairs] block pairs (p, q), p < q, q == blocks naming the phantom (that pair does no work)."""
+    v = (C.c_int64 * 24)()
+    sched = np.zeros(2 * 16 * 8 + 2, dtype=np.int32)
+    check(lib().sr_eig_plan(int(R), int(n_cu), v, 24, as_i32p(sched)), "sr_eig_plan")
+    d = dict(zip(EIG_PLAN_FIELDS, (int(x) for x in v)))
+    d["schedule"] = [[(int(sched[2 * (r * d["pairs"] + k)]), int(sched[2 * (r * d["pairs"] + k) + 1])) for k in range(d["pairs"])]
+                     for r in range(d["rounds"])]
     return d
 
 

@@ -18,6 +18,7 @@
 #include "jfa_plan.hpp"
 #include "norm_plan.hpp"
 #include "plda_plan.hpp"
+#include "eig_plan.hpp"
 #include "map_plan.hpp"
 #include "ref_rand.hpp"
 
@@ -56,6 +57,13 @@ void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids
 void backend_apply(int64_t n, int R, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows);
 void cosine_score(int64_t J, int64_t T, int R, const double *E, const double *X, double *out);
 void set_plda_scratch_mib(long v);
+// eig.hip, backend_eig.hip
+void sym_eig(int R, const double *A, double *w, double *V, int *sweeps, int *converged);
+void gen_eig(int R, const double *Sb, const double *Sw, double *psi, double *V, int *sweeps, int *status);
+void lda_fit(int64_t n, int R, const double *X, const int64_t *ids, int64_t S, int P, double *mu_out, double *A, double *psi_out);
+void backend_project(int64_t n, int R, int P, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows);
+void plda_score_diag(int64_t J, int64_t T, int R, const double *mu, const double *V, const double *psi, const double *E, const int64_t *enrol_n,
+                     const double *X, double *out, int64_t *bad_classes);
 // silence.hip
 void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
 void set_silence_block(long v);
@@ -1344,6 +1352,67 @@ int sr_plda_plan(int kind, int R, int64_t rows, int64_t groups, int64_t T, const
         for (size_t c = 0; c < p.classes.size(); c++)
             classes[3 * c] = p.classes[c].count, classes[3 * c + 1] = p.classes[c].start, classes[3 * c + 2] = p.classes[c].size;
     return 36;
+    SR_CATCH(-1)
+}
+
+// ---- the symmetric eigen-solver and what the back end builds on it (eig.hip, backend_eig.hip).  Every refusal comes first. ----
+
+int sr_sym_eig(int R, const double *A, double *w, double *V, int *sweeps, int *converged) {
+    SR_TRY
+    sym_eig(R, A, w, V, sweeps, converged);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_gen_eig(int R, const double *Sb, const double *Sw, double *psi, double *V, int *sweeps, int *status) {
+    SR_TRY
+    gen_eig(R, Sb, Sw, psi, V, sweeps, status);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_lda_fit(int64_t n, int R, const double *X, const int64_t *ids, int64_t n_labels, int P, double *mu, double *A, double *psi) {
+    SR_TRY
+    lda_fit(n, R, X, ids, n_labels, P, mu, A, psi);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_backend_project(int64_t n, int R, int P, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows) {
+    SR_TRY
+    backend_project(n, R, P, X, mu, A, length_norm, Y, zero_rows);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_plda_score_diag(int64_t J, int64_t T, int R, const double *mu, const double *V, const double *psi, const double *E, const int64_t *enrol_n,
+                       const double *X, double *out, int64_t *bad_classes) {
+    SR_TRY
+    plda_score_diag(J, T, R, mu, V, psi, E, enrol_n, X, out, bad_classes);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_eig_plan(int R, int n_cu, int64_t *out, int n_out, int *schedule) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 24) fail("sr_eig_plan writes 24 fields");
+    std::string why;
+    EigPlan p;
+    if (n_cu > 0) {
+        if (!plan_eig(R, n_cu, p, why)) fail("%s", why.c_str());
+    } else {
+        if (!plan_eig(R, 1, p, why)) fail("%s", why.c_str());      // the refusals first
+        ensure_device();
+        if (!plan_eig(R, ctx().n_cu, p, why)) fail("%s", why.c_str());
+    }
+    const int64_t v[24] = {p.R, p.b, p.blocks, p.phantom, p.rounds, p.pairs, p.single, p.max_sweeps, p.inner_sweeps, p.solve_lds, p.update_lds,
+                           p.solve_grid, p.cols_x, p.cols_y, p.cols_z, p.rows_x, p.rows_y, p.launches_per_sweep, p.bytes_work, p.pair_rounds,
+                           PLDA_MAX_R, EIG_TILE_ROWS, EIG_N, EIG_WG};
+    std::memcpy(out, v, sizeof v);
+    if (schedule)
+        for (size_t i = 0; i < p.schedule.size(); i++) schedule[2 * i] = p.schedule[i].p, schedule[2 * i + 1] = p.schedule[i].q;
+    return 24;
     SR_CATCH(-1)
 }
 

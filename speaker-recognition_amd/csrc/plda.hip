@@ -26,6 +26,7 @@
 // factored, with the iteration and a stop code; scoring writes exact zeros into the class's rows and counts the class.
 // Deterministic: no atomics; every sum has a fixed order; a score depends on its model's count and sum and on its segment only, so
 // neither the batch nor the chunking of the segments under "plda_scratch_mib" shows, bit for bit.
+#include "eig_dev.hpp"
 #include "jfa_dev.hpp"
 #include "plda_plan.hpp"
 
@@ -359,6 +360,12 @@ static std::vector<double> mirrored(const double *M, int R) {
     return out;
 }
 
+void plda_launch_rownorm(hipStream_t st, double *Y, int64_t rows, int R, int *flags) {
+    ScopedKernelTimer tm(T_JFA_UPDATE);
+    hipLaunchKernelGGL(plda_rownorm_kernel, dim3((unsigned)((rows + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG)), dim3(PLDA_WG), 0, st, Y, rows, R, flags);
+    SR_HIP(hipGetLastError());
+}
+
 static void check_device(const char *what) {
     if (gpu_runtime_lost()) fail_gpu_runtime_lost(what);
     ensure_device();
@@ -385,6 +392,33 @@ static std::vector<double> centre_and_sum(hipStream_t st, PldaScratch &w, const 
     if (sums) launch_class_sums(st, w.Xc.p, w.start.p, w.F.p, S, R);
     sync_stream();                             // (mu and the plan's tables are host memory of this frame)
     return mu;
+}
+
+// ---- the same launchers for backend_eig.hip (eig_dev.hpp) ----
+
+void plda_launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,
+                        int64_t rows, int R) {
+    launch_centre(st, X, src, M, midx, coef, out, rows, R);
+}
+void plda_launch_class_sums(hipStream_t st, const double *Xs, const int64_t *row_start, double *F, int64_t S, int R) {
+    launch_class_sums(st, Xs, row_start, F, S, R);
+}
+void plda_launch_combine(hipStream_t st, const double *A, int64_t stride_a, const double *B, const double *coef, double *out, int64_t nb, int R) {
+    launch_combine(st, A, stride_a, B, coef, out, nb, R);
+}
+void plda_launch_rowdot(hipStream_t st, const double *A, const double *B, double *out, int64_t rows, int R) { launch_rowdot(st, A, B, out, rows, R); }
+void plda_accumulate_gram(hipStream_t st, const double *A, const double *B, double *C, int64_t rows, int64_t chunk, int R) {
+    accumulate_gram(st, A, B, C, rows, chunk, R);
+}
+int64_t plda_invert_blocks(hipStream_t st, const PldaPlan &pl, double *blocks, int64_t n, int mode, std::vector<int> &flags, std::vector<double> &logdet) {
+    return invert_blocks(st, per_device<PldaScratch>(), pl, blocks, n, mode, flags, logdet);
+}
+std::vector<double> plda_row_mean(const double *X, int64_t n, int R) { return row_mean(X, n, R); }
+std::vector<double> plda_mirrored(const double *M, int R) { return mirrored(M, R); }
+void plda_check_device(const char *what) { check_device(what); }
+void plda_check_matrix(const double *X, int64_t n, int R, const char *name, const char *rows_name) {
+    std::string why;
+    check_matrix(X, n, R, name, rows_name, why);
 }
 
 void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S, int n_iter, int default_start, double *mu_out, double *Sb,
@@ -662,12 +696,7 @@ void backend_apply(int64_t n, int R, const double *X, const double *mu, const do
     int64_t zeros = 0;
     if (length_norm) {
         w.flags.ensure((size_t)n);
-        {
-            ScopedKernelTimer tm(T_JFA_UPDATE);
-            hipLaunchKernelGGL(plda_rownorm_kernel, dim3((unsigned)((n + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG)), dim3(PLDA_WG), 0, st, w.Y.p, n, R,
-                               w.flags.p);
-            SR_HIP(hipGetLastError());
-        }
+        plda_launch_rownorm(st, w.Y.p, n, R, w.flags.p);
         std::vector<int> flags((size_t)n);
         w.flags.download(flags.data(), (size_t)n);
         sync_stream();
