@@ -400,6 +400,9 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *                    copies and the four products): the test segments run in chunks that fit.  Results do not depend on it, bit for bit.
  *   "plda_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of what sr_plda_score keeps per test segment (its centred row, its row
  *                    of X P_c and its two quadratic forms): the segments run in chunks that fit.  Results do not depend on it, bit for bit.
+ *   "calib_scratch_mib" the bound, in MiB (1 .. 2^20; default 8192), of what a calibration call (sr_calib_train / _eval / _apply / _counts)
+ *                    keeps resident on the device: the scores, the labels and the blocks' partial sums.  A call above it is refused.
+ *                    Results do not depend on it, bit for bit.
  *   "jfa_lds_rows"   largest R whose blocks the JFA factorisation copies into LDS (1 .. 112; 0 = automatic: 112); above it the
  *                    block is factored in place in global memory with panels in LDS.  1 forces that path at any R > 1.
  * The rest select kernel variants for A/B runs and tests. */
@@ -948,6 +951,62 @@ int sr_plda_score_diag(int64_t J, int64_t T, int R, const double *mu /*[R]*/, co
                        const double *E /*[J][R]*/, const int64_t *enrol_n /*[J]*/, const double *X /*[T][R]*/, double *out /*[J][T]*/,
                        int64_t *bad_classes /*or NULL*/);
 int sr_eig_plan(int R, int n_cu, int64_t *out, int n_out, int *schedule /*[rounds][pairs][2] or NULL*/);
+
+/* ---- Score calibration and fusion (csrc/calib.hip, csrc/calib_plan.cpp): prior-weighted linear logistic regression (Bruemmer's FoCal /
+ * BOSARIS) that turns the scores of a verification run into log-likelihood ratios, its objective Cllr, and the error counts behind the
+ * actual DCF.  On the device, float64 throughout.
+ *   X [S][n] row-major: X[s][i] is system s's score for trial i (a quality measure such as a duration is one more row).
+ *   lab [n] int8: 1 target, 0 non-target, any negative value "not a trial" -- skipped everywhere and counted; its scores may hold
+ *   anything (NaN included): they are replaced by a select and never enter the arithmetic.
+ *   theta = (w_1 .. w_S, b);  z_i = sum_s w_s X[s][i] + b;  tau = ln(P / (1 - P));  sp(a) = max(a, 0) + log1p(exp(-|a|));
+ *   f(theta) = (1 / ln 2) [P / n_t sum_tar sp(-(z_i + tau)) + (1 - P) / n_n sum_non sp(z_i + tau)] + lam / 2 sum_s w_s^2
+ *   with a_i = (X[0][i], .., X[S-1][i], 1), s_i = 1 / (1 + exp(-(z_i + tau))), c_i = P / n_t for targets, (1 - P) / n_n for non-targets:
+ *   g = (1 / ln 2) sum_i c_i (s_i - [target]) a_i + lam (w, 0),  H = (1 / ln 2) sum_i c_i s_i (1 - s_i) a_i a_i^T + lam diag(1 .. 1, 0).
+ *   The ridge lam is on the S weights only.  Cllr(llr, lab) is f at S = 1, theta = (1, 0), P = 0.5, lam = 0.
+ * THE BUILT LIMIT: up to 8 systems (S <= 8): calib_pass_kernel keeps f, g and the upper triangle of H, 55 float64 accumulators at S = 8,
+ * in registers, one instance per S.  At most 2^35 trials a call, 16 thresholds a counts call.
+ * sr_calib_train: damped Newton from theta0 (NULL: zeros).  A pass is one evaluation of (f, g, H): a workgroup of 256 lanes owns 4096
+ *   consecutive trials, one exp per trial, a fixed summation tree, no atomics; a one-workgroup step kernel adds the blocks' sums in fixed
+ *   order and takes the decisions:
+ *     pass at theta0;  loop:  H = L L^T by Cholesky; a pivot not > 0 (not above 16 x 2^-52 of its diagonal element: the rounding of its
+ *     own formation) or not finite -> stop SINGULAR;  d = -H^-1 g;  lam2 = -g^T d;  lam2 <= tol -> stop CONVERGED;  t = 1;  repeat: pass
+ *     at theta + t d;  f_new finite and <= f -> accept, leave;  t /= 2;  t < 2^-20 -> stop STALLED;  a further pass needed with max_pass
+ *     made -> stop CAP.
+ *   Stop codes: 0 CONVERGED, 1 CAP, 2 SINGULAR, 3 STALLED.  theta is always the last accepted point and always finite.  Separable data
+ *   with lam = 0 has no finite optimum: the call ends with whichever code it reaches; set a ridge.  The host enqueues pass + step up to
+ *   max_pass (1 .. 1000) times and reads back the stop word alone, after every 4th pair.  The bits of a result depend on (X, lab, P,
+ *   lam, theta0, tol, max_pass) only.
+ *   state [sr_calib_plan's state length = 16 + 4 (S + 1) + (S + 1)(S + 2) / 2 doubles], written on return:  [0] the stop code, [1] phase,
+ *   [2] passes, [3] accepted steps, [4] halvings, [5] f at theta, [6] t, [7] lam2, [8] n_t, [9] n_n, [10] skipped, [11] the pass cap,
+ *   [12] S, [16 ..] theta [S + 1], the pending trial point [S + 1], d [S + 1], g [S + 1] and the upper triangle of H at theta.
+ *   resume != 0: `state` is read first; it must come from a call with the same S and data that ended by CAP, and max_pass more passes
+ *   are made (theta0 is ignored).  max_pass = a, then a resume with b, equals one call with a + b, bit for bit.
+ * sr_calib_eval: one pass at theta -> f, g [S + 1] (or NULL), H [S + 1][S + 1] (or NULL).
+ * sr_calib_apply: out[i] = z_i for all n (no labels: every position).  The same trial gives the same bits alone and in any batch.
+ * sr_calib_counts: at m <= 16 thresholds thr (-inf and +inf allowed), with "accept iff llr >= thr": miss[j] the targets not accepted,
+ *   fa[j] the non-targets accepted.  Integers per workgroup, added on the host: exact.
+ * counts (or NULL) [3] of train / eval / counts: targets, non-targets, skipped.
+ * sr_calib_plan: what a call decides (csrc/calib_plan.cpp; host only when n_cu > 0), for tests.  Writes 28 fields (n_out >= 28) and
+ *   returns 28, -1 on refusal: S, n, the blocks of 4096 trials, the accumulators, the state length, the bytes of X, lab, the partial sums,
+ *   the state, apply's out, the thresholds, the counters; the resident bytes of train / eval, of apply, of counts; the grids of the
+ *   pass, step, apply and counts kernels; the rounds of the pass kernel over the chip; the built limits of S and of the thresholds;
+ *   trials per block; lanes per workgroup; the pairs between two reads of the stop word; the
+ *   built limits of max_pass and of n; a zero.  scratch_bytes > 0: refuse as a call under that bound would (call: 0 train, 1 apply, 2 counts).
+ * The scores go up once per call and stay resident for every pass.  "calib_scratch_mib" (sr_set_option; 1 .. 2^20 MiB, default 8192)
+ * bounds a call's resident bytes: a call above it is refused and told to raise the option or calibrate on fewer trials.
+ * Refused, before the device is touched, with a message that names the argument and the remedy: S < 1 or S > 8; n < 1 or above the
+ * limit; no target or no non-target; a label above 1; P not in (0, 1); lam < 0 or not finite; tol < 0; max_pass outside 1 .. 1000; a
+ * non-finite score at a trial (skipped positions are not checked); a non-finite theta0 / theta; a NaN threshold; a null argument; a
+ * state that cannot be resumed; resident bytes above the bound.  Refused in a process forked after the GPU runtime was initialised.
+ * Timer kinds (none is added): SR_T_JFA_GEMM_A the pass kernel; SR_T_JFA_FACTOR the step kernel; SR_T_JFA_UPDATE apply and counts. */
+int sr_calib_train(int S, int64_t n, const double *X /*[S][n]*/, const int8_t *lab /*[n]*/, double prior, double ridge, double tol, int max_pass,
+                   const double *theta0 /*[S+1] or NULL*/, int resume, double *state /*[state length]*/, int64_t *counts /*[3] or NULL*/);
+int sr_calib_eval(int S, int64_t n, const double *X /*[S][n]*/, const int8_t *lab /*[n]*/, double prior, double ridge, const double *theta /*[S+1]*/,
+                  double *f, double *g /*[S+1] or NULL*/, double *H /*[S+1][S+1] or NULL*/, int64_t *counts /*[3] or NULL*/);
+int sr_calib_apply(int S, int64_t n, const double *X /*[S][n]*/, const double *theta /*[S+1]*/, double *out /*[n]*/);
+int sr_calib_counts(int64_t n, const double *llr /*[n]*/, const int8_t *lab /*[n]*/, int m, const double *thr /*[m]*/, int64_t *miss /*[m]*/,
+                    int64_t *fa /*[m]*/, int64_t *counts /*[3] or NULL*/);
+int sr_calib_plan(int S, int64_t n, int n_thr, int call, int64_t scratch_bytes, int n_cu, int64_t *out, int n_out);
 
 #ifdef __cplusplus
 }

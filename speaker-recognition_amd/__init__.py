@@ -7,7 +7,8 @@ path: ``pygmm`` (src/gmm/python/pygmm.py), ``gmmset`` (src/testbench/gmmset.py),
 (src/gui/interface.py) and ``cli`` (src/speaker-recognition.py); ``jfa`` holds the front of
 src/jfa/ (per-session Baum-Welch statistics against a UBM) by the reference's names; ``scorenorm``
 normalises the score matrices of a verification run against impostor cohorts on the device
-(Z, T, ZT, S and adaptive S-norm) and reports EER and minDCF; ``ivector`` and ``plda`` are the i-vector leg: extraction by the
+(Z, T, ZT, S and adaptive S-norm) and reports EER and minDCF; ``calibration`` turns those scores into log-likelihood ratios by
+logistic regression on the device, fuses systems and reports Cllr, min Cllr and the actual DCF; ``ivector`` and ``plda`` are the i-vector leg: extraction by the
 factor estimator's names, then whitening, WCCN, length normalisation, cosine scoring and Gaussian PLDA on the device.
 """
 __version__ = "0.1.0"

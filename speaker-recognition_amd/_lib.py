@@ -52,6 +52,7 @@ EXT_SYMBOLS = [
     "sr_score_norm", "sr_score_norm_select", "sr_score_norm_plan",
     "sr_backend_fit", "sr_backend_apply", "sr_cosine_score", "sr_plda_train", "sr_plda_score", "sr_plda_plan",
     "sr_sym_eig", "sr_gen_eig", "sr_lda_fit", "sr_backend_project", "sr_plda_score_diag", "sr_eig_plan",
+    "sr_calib_train", "sr_calib_eval", "sr_calib_apply", "sr_calib_counts", "sr_calib_plan",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -257,6 +258,11 @@ def lib():
         "sr_score_norm": (i32, [i32, i64, i64, i64, i64, i32, dp, dp, dp, dp, dp, C.POINTER(i64)]),
         "sr_score_norm_select": (i32, [i64, i64, i32, dp, C.POINTER(i64), dp, dp]),
         "sr_score_norm_plan": (i32, [i32, i64, i64, i64, i64, i32, i64, i32, C.POINTER(i64), i32]),
+        "sr_calib_train": (i32, [i32, i64, dp, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, i32, dp, i32, dp, C.POINTER(i64)]),
+        "sr_calib_eval": (i32, [i32, i64, dp, C.POINTER(C.c_int8), C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(i64)]),
+        "sr_calib_apply": (i32, [i32, i64, dp, dp, dp]),
+        "sr_calib_counts": (i32, [i64, dp, C.POINTER(C.c_int8), i32, dp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "sr_calib_plan": (i32, [i32, i64, i32, i32, i64, i32, C.POINTER(i64), i32]),
         "sr_backend_fit": (i32, [i32, i64, i32, dp, C.POINTER(i64), i64, dp, dp]),
         "sr_backend_apply": (i32, [i64, i32, dp, dp, dp, i32, dp, C.POINTER(i64)]),
         "sr_cosine_score": (i32, [i64, i64, i32, dp, dp, dp]),
@@ -321,6 +327,10 @@ def as_dp(a: np.ndarray):
 
 def as_i64p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def as_i8p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int8))
 
 
 def as_i32p(a: np.ndarray):
@@ -608,6 +618,23 @@ def score_norm_plan(mode: str, J: int, T: int, Cz: int, Ct: int, top_n: int = 0,
     d = dict(zip(NORM_PLAN_FIELDS, (int(x) for x in v)))
     d["mode"] = NORM_MODES[d["mode"]]
     return d
+
+
+CALIB_CALLS = ("train", "apply", "counts")
+CALIB_STOPS = ("CONVERGED", "CAP", "SINGULAR", "STALLED")
+CALIB_PLAN_FIELDS = ("S", "n", "n_blocks", "acc", "state_len", "bytes_X", "bytes_lab", "bytes_partial", "bytes_state", "bytes_out", "bytes_thr",
+                     "bytes_counts", "resident_train", "resident_apply", "resident_counts", "pass_grid", "step_grid", "apply_grid", "counts_grid",
+                     "pass_rounds", "max_S", "max_thresholds", "block", "workgroup", "cadence", "max_pass", "max_n")
+
+
+def calib_plan(S: int, n: int, n_thr: int = 0, call: str = "train", scratch_bytes: int = 0, n_cu: int = 256) -> dict:
+    """What a calibration call decides for S systems and n trials (csrc/calib_plan.cpp; no GPU needed when n_cu > 0): the refusals, the
+    blocks of 4096 trials, the accumulators and the state length, the bytes of every array, each call's resident bytes, the grids and the
+    built limits.  ``scratch_bytes`` > 0: refuse as ``call`` ("train" -- also evaluation --, "apply" or "counts") under that bound would."""
+    v = (C.c_int64 * 28)()
+    c = CALIB_CALLS.index(call) if call in CALIB_CALLS else -1
+    check(lib().sr_calib_plan(int(S), int(n), int(n_thr), c, int(scratch_bytes), int(n_cu), v, 28), "sr_calib_plan")
+    return dict(zip(CALIB_PLAN_FIELDS, (int(x) for x in v)))
 
 
 PLDA_PLAN_FIELDS = ("kind", "R", "rows", "groups", "T", "n_classes", "sum_chunk", "sum_chunks", "grp_chunk", "grp_chunks", "chunk", "n_chunks",

@@ -17,6 +17,7 @@
 #include "bw_plan.hpp"
 #include "jfa_plan.hpp"
 #include "norm_plan.hpp"
+#include "calib_plan.hpp"
 #include "plda_plan.hpp"
 #include "eig_plan.hpp"
 #include "map_plan.hpp"
@@ -48,6 +49,14 @@ void score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_
 void score_norm_select(int64_t rows, int64_t C, int top_n, const double *X, int64_t *idx, double *mu, double *sigma);
 void set_norm_scratch_mib(long v);
 long norm_scratch_mib();
+// calib.hip
+void calib_train(int S, int64_t n, const double *X, const int8_t *lab, double prior, double ridge, double tol, int max_pass, const double *theta0,
+                 int resume, double *state, int64_t *counts);
+void calib_eval(int S, int64_t n, const double *X, const int8_t *lab, double prior, double ridge, const double *theta, double *f, double *g,
+                double *H, int64_t *counts);
+void calib_apply(int S, int64_t n, const double *X, const double *theta, double *out);
+void calib_counts(int64_t n, const double *llr, const int8_t *lab, int m, const double *thr, int64_t *miss, int64_t *fa, int64_t *counts);
+void set_calib_scratch_mib(long v);
 // plda.hip
 void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S, int n_iter, int default_start, double *mu_out, double *Sb,
                 double *Sw, int *iterations, int *n_classes, int *stop);
@@ -1282,6 +1291,60 @@ int sr_score_norm_plan(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, i
     SR_CATCH(-1)
 }
 
+// ---- score calibration and fusion (calib.hip).  Every refusal comes before the device is touched. ----
+
+int sr_calib_train(int S, int64_t n, const double *X, const int8_t *lab, double prior, double ridge, double tol, int max_pass, const double *theta0,
+                   int resume, double *state, int64_t *counts) {
+    SR_TRY
+    calib_train(S, n, X, lab, prior, ridge, tol, max_pass, theta0, resume, state, counts);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_calib_eval(int S, int64_t n, const double *X, const int8_t *lab, double prior, double ridge, const double *theta, double *f, double *g,
+                  double *H, int64_t *counts) {
+    SR_TRY
+    calib_eval(S, n, X, lab, prior, ridge, theta, f, g, H, counts);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_calib_apply(int S, int64_t n, const double *X, const double *theta, double *out) {
+    SR_TRY
+    calib_apply(S, n, X, theta, out);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_calib_counts(int64_t n, const double *llr, const int8_t *lab, int m, const double *thr, int64_t *miss, int64_t *fa, int64_t *counts) {
+    SR_TRY
+    calib_counts(n, llr, lab, m, thr, miss, fa, counts);
+    return 0;
+    SR_CATCH(-1)
+}
+
+int sr_calib_plan(int S, int64_t n, int n_thr, int call, int64_t scratch_bytes, int n_cu, int64_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 28) fail("sr_calib_plan writes 28 fields");
+    if (call < 0 || call > 2) fail("sr_calib_plan: call is 0 (train / eval), 1 (apply) or 2 (counts)");
+    std::string why;
+    CalibPlan p;
+    if (!plan_calib(S, n, n_thr, scratch_bytes, n_cu > 0 ? n_cu : 1, p, why)) fail("%s", why.c_str());          // the refusals first
+    if (scratch_bytes > 0 && !calib_check_bound(p, call == 1 ? "apply" : call == 2 ? "counts" : "train", scratch_bytes, why)) fail("%s", why.c_str());
+    if (n_cu <= 0) {
+        ensure_device();
+        if (!plan_calib(S, n, n_thr, scratch_bytes, ctx().n_cu, p, why)) fail("%s", why.c_str());
+    }
+    const int64_t v[28] = {p.S, p.n, p.n_blocks, p.acc, p.state_len, p.bytes_X, p.bytes_lab, p.bytes_partial, p.bytes_state, p.bytes_out,
+                           p.bytes_thr, p.bytes_counts, p.resident_train, p.resident_apply, p.resident_counts, p.pass_grid, p.step_grid,
+                           p.apply_grid, p.counts_grid, p.pass_rounds, CALIB_MAX_S, CALIB_MAX_THR, CALIB_BLOCK, CALIB_WG,
+                           CALIB_CADENCE, CALIB_MAX_PASS, CALIB_MAX_N, 0};
+    std::memcpy(out, v, sizeof v);
+    return 28;
+    SR_CATCH(-1)
+}
+
 // ---- the i-vector back end (plda.hip).  Every refusal comes before the device is touched. ----
 
 int sr_backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids, int64_t n_labels, double *mu, double *A) {
@@ -1590,6 +1653,9 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "norm_scratch_mib") {
         if (value < 1 || value > (1L << 20)) fail("norm_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(NORM_DEFAULT_SCRATCH >> 20));
         set_norm_scratch_mib(value);
+    } else if (k == "calib_scratch_mib") {
+        if (value < 1 || value > (1L << 20)) fail("calib_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(CALIB_DEFAULT_SCRATCH >> 20));
+        set_calib_scratch_mib(value);
     } else if (k == "plda_scratch_mib") {
         if (value < 1 || value > (1L << 20)) fail("plda_scratch_mib must be within 1 .. %ld (the default is %ld)", 1L << 20, (long)(PLDA_DEFAULT_SCRATCH >> 20));
         set_plda_scratch_mib(value);
