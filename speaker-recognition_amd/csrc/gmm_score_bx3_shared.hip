@@ -237,8 +237,9 @@ static void launch_shared(const SharedLaunch &a) {
 
 void launch_score_bx3_shared(const SharedLaunch &a, int KQ, int KL) {
 #define SR_SH_CASE(Q, L) if (KQ == Q && KL == L) return launch_shared<Q, L>(a);
+    // KQ = ceil(D/16), KL = ceil((D+1)/16) for D = 1 .. 48, the widest set pack_model_set offers this engine (shared_ok): equal, or one
+    // apart at D = 16, 32, 48.  tests/test_h2s_width_cases_cpu.py reads this list: a new pair needs a row in tests/h2s_width_cases.py
     SR_SH_CASE(1, 1) SR_SH_CASE(1, 2) SR_SH_CASE(2, 2) SR_SH_CASE(2, 3) SR_SH_CASE(3, 3) SR_SH_CASE(3, 4)
-    SR_SH_CASE(4, 4) SR_SH_CASE(4, 5)
 #undef SR_SH_CASE
     fail("no shared-sigma scoring kernel for %d + %d contraction steps", KQ, KL);
 }
