@@ -206,6 +206,35 @@ SRBatch *sr_silence_remove_batch(SRBatch *pcm, double fs, double frame_duration,
  * the energy kernel, positions of that utterance. */
 int sr_silence_plan(double fs, double frame_duration, double frame_shift, int64_t max_samples, int32_t *out, int n_out);
 
+/* Short-time feature normalisation (csrc/featnorm.hip) of every utterance of a FEATURES batch, each utterance and each column on
+ * its own; the result is a new FEATURES batch of the same layout on the same device.  An utterance of T frames and a window of
+ * `window` = W frames (2 .. 1024, even or odd): frame t looks at the N = min(W, T) rows from s0(t) = min(max(t - W / 2, 0), T - N)
+ * -- centred in the interior, shifted (not shortened) at both ends.
+ *   mode 0, warp (Pelecanos & Sridharan 2001): less = values of the window < x_t, eq = values == x_t (fp32 comparisons, the frame
+ *     itself included), the doubled mid-rank r2 = 2 less + eq - 1, out = (float) Q((r2 + 1) / (2 N)) with Q the standard normal
+ *     quantile (sr_norm_quantile), taken through the lower half of the distribution: ranks mirrored about the middle give values
+ *     that are each other's negatives to the bit, a constant stretch gives exactly 0.  A NaN cell gives NaN and rank -1 and is
+ *     counted; a NaN neighbour is neither less nor equal; +-inf rank like any value.
+ *   mode 1, cmn: out = (float)(x_t - mean), mean = (sum x) / N in float64, summed in window order.
+ *   mode 2, cmvn: out = (float)((x_t - mean) / sqrt(var)), var = (sum (x - mean)^2) / N, the second pass in window order too (the
+ *     population variance, no epsilon).  A window whose values all compare equal gives exactly 0 and is counted.  NaN propagates.
+ * degenerate_out: [U] counts (warp: NaN cells; cmvn: equal-valued windows; cmn: 0), or NULL.  ranks_out: host memory, [rows][dim]
+ * int32 r2 (warp only), or NULL -- for tests.  An utterance's output is the same bits alone, in any batch, under any "norm_tile"
+ * and from run to run.  Utterances of 0 rows stay empty.  NULL + sr_last_error() on refusal, before the device is touched: a PCM
+ * batch, a mode outside 0 .. 2, a window outside 2 .. 1024, ranks_out with another mode than 0; a process forked after its parent
+ * initialised the GPU runtime is refused as well.  Timed under SR_T_CMVN (no timer kind is added).
+ * sr_set_option("norm_tile", F): frames per workgroup, a multiple of 64 up to 1024; 0 = automatic (256). */
+SRBatch *sr_feature_norm_batch(SRBatch *feats, int mode, int window, int64_t *degenerate_out, int32_t *ranks_out);
+/* What such a call decides for columns of width dim and a longest utterance of max_frames under the current "norm_tile"
+ * (csrc/featnorm_plan.cpp; no GPU needed when n_cu > 0; n_cu <= 0: the current device's).  Writes 12 fields (n_out >= 12) and
+ * returns 12, -1 on refusal: frames per workgroup F, rows a workgroup stages at most, floats between two columns in LDS, columns
+ * per pass, passes, LDS bytes, workgroups of that utterance alone, the grid for it, 1 when the warped values of full windows come
+ * from a table, that table's length, lanes per workgroup, the largest window built. */
+int sr_feature_norm_plan(int mode, int window, int dim, int64_t max_frames, int n_cu, int32_t *out, int n_out);
+/* The standard normal quantile in float64: Wichura's AS241 (PPND16), the host instance of the function the kernels evaluate.
+ * 0 < p < 1; NaN otherwise. */
+double sr_norm_quantile(double p);
+
 /* Score every utterance of a feature batch against every model of the set in one fused pass:
  * sums_out[U][S] = sum_t LL_s(x_t) (double), argmax_out[U] = first maximum (gmmset.py:62-64),
  * frame_ll_out (optional, may be NULL) = [S][n_frames] fp32 per-frame log-likelihoods. */
@@ -389,6 +418,8 @@ int sr_profile_get(int kind, double *total_ms, long *launches);
  *   "map_fit_batch_bytes" the bound, in bytes (>= 1; default 1 GiB), of the float64 scratch of a group of speakers in sr_map_fit_batch.
  *                    Results do not depend on it, bit for bit.
  *   "silence_block"  positions per block of sr_silence_remove_batch's walk (1 .. 2^30; 0 = automatic: max(256, 4 E, positions of the longest utterance / 2048)).
+ *   "norm_tile"      frames per workgroup of sr_feature_norm_batch (a multiple of 64 up to 1024; 0 = automatic: 256).  Results do not
+ *                    depend on it, bit for bit.
  *   "topc_scratch_mib" the scratch bound of sr_score_batch_set_topc, in MiB (>= 1; default 1024): the pass runs in chunks of frames that fit.
  *   "bw_scratch_mib" the bound, in MiB (1 .. 2^20; default 1024), of the float64 slabs sr_bw_stats_batch keeps at a time: the range
  *                    table runs in groups that fit.  Results do not depend on it, bit for bit.

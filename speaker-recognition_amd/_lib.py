@@ -53,6 +53,7 @@ EXT_SYMBOLS = [
     "sr_backend_fit", "sr_backend_apply", "sr_cosine_score", "sr_plda_train", "sr_plda_score", "sr_plda_plan",
     "sr_sym_eig", "sr_gen_eig", "sr_lda_fit", "sr_backend_project", "sr_plda_score_diag", "sr_eig_plan",
     "sr_calib_train", "sr_calib_eval", "sr_calib_apply", "sr_calib_counts", "sr_calib_plan",
+    "sr_feature_norm_batch", "sr_feature_norm_plan", "sr_norm_quantile",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -275,6 +276,9 @@ def lib():
         "sr_backend_project": (i32, [i64, i32, i32, dp, dp, dp, i32, dp, C.POINTER(i64)]),
         "sr_plda_score_diag": (i32, [i64, i64, i32, dp, dp, dp, dp, C.POINTER(i64), dp, dp, C.POINTER(i64)]),
         "sr_eig_plan": (i32, [i32, i32, C.POINTER(i64), i32, C.POINTER(i32)]),
+        "sr_feature_norm_batch": (vp, [vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_int32)]),
+        "sr_feature_norm_plan": (i32, [i32, i32, i32, i64, i32, C.POINTER(C.c_int32), i32]),
+        "sr_norm_quantile": (dbl, [dbl]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -516,6 +520,30 @@ def silence_plan(fs, frame_duration: float = 0.02, frame_shift: float = 0.01, ma
     check(lib().sr_silence_plan(float(fs), float(frame_duration), float(frame_shift), int(max_samples), v, 12), "sr_silence_plan")
     names = ("L", "S", "g", "E", "B", "blocks", "variant", "blocks_per_wg", "list_cap", "grid", "chunk_lanes", "positions")
     return dict(zip(names, (int(x) for x in v)))
+
+
+FEATURE_NORM_MODES = ("warp", "cmn", "cmvn")
+FEATURE_NORM_PLAN_FIELDS = ("F", "span", "stride", "cols", "passes", "lds", "tiles", "grid", "table", "table_len", "workgroup", "max_window")
+
+
+def feature_norm_mode(mode) -> int:
+    """The C ABI's number of a normalisation mode name (-1 for anything else: the library refuses it)."""
+    return FEATURE_NORM_MODES.index(mode) if isinstance(mode, str) and mode in FEATURE_NORM_MODES else -1
+
+
+def feature_norm_plan(mode: str = "warp", window: int = 301, dim: int = 39, max_frames: int = 1, n_cu: int = 256) -> dict:
+    """What ``sr_feature_norm_batch`` decides for columns of width ``dim`` and a longest utterance of ``max_frames`` under the
+    current ``norm_tile`` option (csrc/featnorm_plan.cpp; no GPU needed when n_cu > 0): the refusals, frames per workgroup ``F``,
+    the rows a workgroup stages at most, the column stride in LDS, columns per pass and passes, LDS bytes, the workgroups of that
+    utterance and the grid, whether full windows read their warped values from a table, and the built limits."""
+    v = (C.c_int32 * 12)()
+    check(lib().sr_feature_norm_plan(feature_norm_mode(mode), int(window), int(dim), int(max_frames), int(n_cu), v, 12), "sr_feature_norm_plan")
+    return dict(zip(FEATURE_NORM_PLAN_FIELDS, (int(x) for x in v)))
+
+
+def norm_quantile(p: float) -> float:
+    """The standard normal quantile as the library computes it (AS241 in float64; csrc/norm_quantile.hpp); no GPU needed."""
+    return float(lib().sr_norm_quantile(float(p)))
 
 
 def topc_plan(K: int, D: int, S: int, top_c: int, n_frames: int, scratch_bytes: int = 1 << 30, n_cu: int = 256) -> dict:

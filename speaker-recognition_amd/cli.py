@@ -5,6 +5,7 @@
     speaker-recognition.py -t predict -i "./*.wav" -m model.out --reject-threshold 0.5
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --covariance full
     speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --remove-silence
+    speaker-recognition.py -t enroll  -i "./bob/ ./mary/" -m model.out --feature-norm warp --norm-window 301
 
 Wav files in each input directory are labelled with the directory's basename; wildcard inputs
 must be quoted (they go to glob).  Extra options (not in the reference) select the feature
@@ -58,6 +59,11 @@ def get_args(argv=None):
     parser.add_argument("--remove-silence", action="store_true",
                         help="drop silent frames before the feature stage (the reference's filters/silence.py, on the GPU). enroll: "
                              "stored in the model; predict: applied even if the model was enrolled without it")
+    parser.add_argument("--feature-norm", choices=["warp", "cmn", "cmvn"], default=None,
+                        help="short-time feature normalisation behind the feature stage, on the GPU (warp: feature warping; cmn / "
+                             "cmvn: sliding-window mean / mean and variance). enroll: stored in the model; predict: the model's own "
+                             "setting holds unless the flag is given")
+    parser.add_argument("--norm-window", type=int, default=None, help="frames of the --feature-norm window (2 .. 1024; default 301)")
     return parser.parse_args(argv)
 
 
@@ -92,10 +98,22 @@ def task_enroll(input_dirs, output_model, args=None):
     m.dump(output_model)
 
 
-def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove_silence=False, top_c=None):
+def _feature_norm_setting(args):
+    """The ``feature_norm`` value the flags ask for, None without --feature-norm (--norm-window alone changes nothing)."""
+    mode = getattr(args, "feature_norm", None)
+    if mode is None:
+        return None
+    window = getattr(args, "norm_window", None)
+    return mode if window is None else dict(mode=mode, window=window)
+
+
+def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove_silence=False, top_c=None, feature_norm=None):
     m = ModelInterface.load(input_model)
     if remove_silence:              # the flag overrides a model enrolled without it; a model's own setting holds otherwise
         m.remove_silence = True
+    if feature_norm is not None:    # likewise
+        m.feature_norm = feature_norm
+        m._norm_setting()
     out = []
     files = sorted(glob.glob(os.path.expanduser(input_files)))
     if top_c is not None:
@@ -158,7 +176,7 @@ def _make_interface(args):
     return ModelInterface(gmm_order=args.mixtures, feature_kwargs=fk, diff=args.deltas > 0,
                           nd=max(1, args.deltas), lpc=not args.no_lpc and args.deltas == 0,
                           gmm_kwargs={"seed": args.seed}, covariance_type=args.covariance,
-                          remove_silence=bool(getattr(args, "remove_silence", False)))
+                          remove_silence=bool(getattr(args, "remove_silence", False)), feature_norm=_feature_norm_setting(args))
 
 
 def main(argv=None):
@@ -168,7 +186,7 @@ def main(argv=None):
     if args.task == "enroll":
         task_enroll(args.input, args.model, args)
     elif args.task == "predict":
-        task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence, args.top_c)
+        task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence, args.top_c, _feature_norm_setting(args))
     else:
         print('task must be "enroll" or "predict"')
         sys.exit(2)

@@ -128,6 +128,23 @@ class Batch:
             raise SRError("sr_silence_remove_batch failed: %s" % _lib.last_error())
         return Batch(h)
 
+    def normalise(self, mode="warp", window=301, ranks=False, counts=False):
+        """Short-time feature normalisation of every utterance of a feature batch, on the device (sr_feature_norm_batch): -> a
+        new device-resident feature batch of the same layout.  ``mode``: "warp" (feature warping: each value mapped through its
+        mid-rank in a window of ``window`` frames onto a standard normal), "cmn" or "cmvn" (the window's mean, or mean and
+        variance, in float64).  The window is centred, and shifted -- not shortened -- at both ends of an utterance.
+        ``counts=True`` also returns the per-utterance int64 counts of degenerate cells (warp: NaN cells; cmvn: windows of equal
+        values, which give 0), ``ranks=True`` the int32 doubled mid-ranks [rows, dim] (warp only; for tests): the result is then
+        the tuple (batch[, ranks][, counts])."""
+        deg = np.zeros(max(1, self.n_utt), dtype=np.int64) if counts else None
+        rk = np.empty((self.n_rows, self.dim), dtype=np.int32) if ranks else None
+        h = lib().sr_feature_norm_batch(self._h, _lib.feature_norm_mode(mode), int(window), None if deg is None else _lib.as_i64p(deg),
+                                        None if rk is None else rk.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not h:
+            raise SRError("sr_feature_norm_batch failed: %s" % _lib.last_error())
+        out = (Batch(h),) + ((rk,) if ranks else ()) + ((deg[:self.n_utt],) if counts else ())
+        return out if len(out) > 1 else out[0]
+
     def __del__(self):
         try:
             if self._owner and self._h:
@@ -270,11 +287,16 @@ class MfccExtractor:
     def num_frames(self, n_samples: int) -> int:
         return int(lib().sr_mfcc_num_frames(self._h, int(n_samples)))
 
-    def extract_batch(self, pcm: Batch, nd: int = 0, cmvn: bool = True) -> Batch:
+    def extract_batch(self, pcm: Batch, nd: int = 0, cmvn: bool = True, norm=None, norm_window: int = 301) -> Batch:
+        """``norm`` ("warp", "cmn" or "cmvn"; default off): the features go through ``Batch.normalise(norm, norm_window)`` before
+        they are returned, both stages resident (the per-utterance ``cmvn`` is the caller's choice: usually False with it)."""
+        if norm is not None and _lib.feature_norm_mode(norm) < 0:
+            raise ValueError("norm must be None, 'warp', 'cmn' or 'cmvn' (got %r)" % (norm,))
         h = lib().sr_mfcc_extract_batch(self._h, pcm._h, int(nd), 1 if cmvn else 0)
         if not h:
             raise SRError("sr_mfcc_extract_batch failed: %s" % _lib.last_error())
-        return Batch(h)
+        out = Batch(h)
+        return out if norm is None else out.normalise(norm, norm_window)
 
     def extract(self, signal, nd: int = 0, cmvn: bool = True) -> np.ndarray:
         """One utterance -> float64 [T - nd, n_ceps*(nd+1)] (what MFCCExtractor.extract returns,

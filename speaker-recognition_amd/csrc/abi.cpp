@@ -13,6 +13,8 @@
 #include "mfcc_plan.hpp"
 #include "score.hpp"
 #include "silence_plan.hpp"
+#include "featnorm_plan.hpp"
+#include "norm_quantile.hpp"
 #include "topc_plan.hpp"
 #include "bw_plan.hpp"
 #include "jfa_plan.hpp"
@@ -77,6 +79,10 @@ void plda_score_diag(int64_t J, int64_t T, int R, const double *mu, const double
 void silence_remove_batch(SRBatch &pcm, double fs, double frame_duration, double frame_shift, double perc, SRBatch &out, int64_t *kept_out);
 void set_silence_block(long v);
 long silence_block();
+// featnorm.hip
+void feature_norm_batch(SRBatch &in, int mode, int window, SRBatch &out, int64_t *degenerate_out, int32_t *ranks_out);
+void set_feature_norm_tile(long v);
+long feature_norm_tile();
 }
 std::atomic<int> &stream_debug_capture_delay_ms();      // stream.cpp
 std::atomic<int> &multi_merge_option();
@@ -724,6 +730,39 @@ int sr_silence_plan(double fs, double frame_duration, double frame_shift, int64_
     return 12;
     SR_CATCH(-1)
 }
+
+// ---- short-time feature normalisation (featnorm.hip).  Every refusal comes before the device is touched. ----
+
+SRBatch *sr_feature_norm_batch(SRBatch *feats, int mode, int window, int64_t *degenerate_out, int32_t *ranks_out) {
+    SR_TRY
+    if (!feats) fail("null argument");
+    auto out = std::make_unique<SRBatch>();
+    feature_norm_batch(*feats, mode, window, *out, degenerate_out, ranks_out);
+    return out.release();
+    SR_CATCH(nullptr)
+}
+
+int sr_feature_norm_plan(int mode, int window, int dim, int64_t max_frames, int n_cu, int32_t *out, int n_out) {
+    SR_TRY
+    if (!out) fail("null argument");
+    if (n_out < 12) fail("sr_feature_norm_plan writes 12 fields");
+    FeatNormPlan p;
+    std::string why;
+    if (n_cu > 0) {
+        if (!plan_feature_norm(mode, window, true, dim, max_frames, feature_norm_tile(), n_cu, p, why)) fail("sr_feature_norm_plan: %s", why.c_str());
+    } else {
+        if (!plan_feature_norm(mode, window, true, dim, max_frames, feature_norm_tile(), 1, p, why)) fail("sr_feature_norm_plan: %s", why.c_str());
+        ensure_device();
+        if (!plan_feature_norm(mode, window, true, dim, max_frames, feature_norm_tile(), ctx().n_cu, p, why)) fail("sr_feature_norm_plan: %s", why.c_str());
+    }
+    const int64_t v[12] = {p.F, p.span_max, p.stride, p.cols, p.passes, p.lds_bytes, p.tiles_max, featnorm_grid(p.tiles_max, n_cu > 0 ? n_cu : ctx().n_cu),
+                           p.table ? 1 : 0, p.table_len, FEATNORM_WG, FEATNORM_MAX_W};
+    for (int i = 0; i < 12; i++) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    return 12;
+    SR_CATCH(-1)
+}
+
+double sr_norm_quantile(double p) { return norm_quantile(p); }
 
 int sr_score_batch_set(SRModelSet *set, SRBatch *features, double *sums_out, int *argmax_out,
                        float *frame_ll_out, int flags) {
@@ -1671,6 +1710,10 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "silence_block") {
         if (value < 0 || value > SILENCE_MAX_REL) fail("silence_block must be 0 (automatic) or 1 .. 2^30 positions per block");
         set_silence_block(value);
+    } else if (k == "norm_tile") {
+        if (value < 0 || value > FEATNORM_MAX_TILE || value % FEATNORM_WAVE != 0)
+            fail("norm_tile must be 0 (automatic) or a multiple of 64 up to 1024 frames per workgroup");
+        set_feature_norm_tile(value);
     } else if (k == "mfcc_generic") {
         mfcc_set_force_generic(value != 0);
     } else if (k == "mfcc_precision") {

@@ -16,6 +16,10 @@ energy-threshold silence removal of the reference's corpus preparation (``filter
 feature stage of ``enroll`` and every ``predict*`` -- the setting is stored with the model; int16, int8 or uint8 audio.  A signal
 it leaves too short for a frame gives None from ``predict*`` and raises from ``enroll``, as a short raw signal does.  With it,
 ``predict_many(gpus != 1)`` takes the one-GPU path.
+``feature_norm`` (None; "warp", "cmn", "cmvn", or a dict of ``mode`` / ``window``): short-time feature normalisation
+(``feature.norm``, on the device: feature warping or sliding-window CMN / CMVN over ``window`` = 301 frames) of whatever
+``mix_feature`` returns, in ``enroll`` and every ``predict*`` -- the setting is stored with the model.  With it,
+``predict_many(gpus != 1)`` takes the one-GPU path.
 VAD (``init_noise`` / ``filter``) is the LTSD detector of ``filters`` (third-party pyssp in the
 reference: restated, parity unpinned).
 """
@@ -39,12 +43,14 @@ class ModelInterface(object):
     UBM_MODEL_FILE = None
 
     def __init__(self, *, gmm_order=32, feature_kwargs=None, diff=False, nd=1, lpc=True, gmm_kwargs=None,
-                 verbose=True, covariance_type="diag", remove_silence=False):
+                 verbose=True, covariance_type="diag", remove_silence=False, feature_norm=None):
         if covariance_type not in ("diag", "full"):
             raise ValueError("covariance_type must be 'diag' or 'full' (got %r)" % (covariance_type,))
         self.covariance_type = covariance_type
         self.remove_silence = remove_silence
         self._silence_kwargs()          # (a bad value fails here, not at the first recording)
+        self.feature_norm = feature_norm
+        self._norm_setting()
         self.features = defaultdict(list)
         self.gmm_order = gmm_order
         self.feature_kwargs = dict(feature_kwargs or {})
@@ -89,6 +95,18 @@ class ModelInterface(object):
             return dict(rs)
         raise ValueError("remove_silence must be False, True or a dict of frame_duration / frame_shift / perc (got %r)" % (rs,))
 
+    def _norm_setting(self):
+        """None when feature normalisation is off (also for a model pickled before the setting existed), else (mode, window)."""
+        fn = getattr(self, "feature_norm", None)
+        if fn is None:
+            return None
+        from .feature.norm import check_setting
+        if isinstance(fn, str):
+            return check_setting(fn)
+        if isinstance(fn, dict) and "mode" in fn and set(fn) <= {"mode", "window"}:
+            return check_setting(fn["mode"], fn.get("window", 301))
+        raise ValueError("feature_norm must be None, 'warp', 'cmn', 'cmvn' or a dict of mode / window (got %r)" % (fn,))
+
     def _desilenced(self, items):
         """[(fs, signal), ...] as they reach the feature stage: unchanged, or through ``filters.silence`` -- one device call
         per sampling rate."""
@@ -109,7 +127,12 @@ class ModelInterface(object):
         return self._features_of(fs, signal)
 
     def _features_of(self, fs, signal):
-        return mix_feature((fs, signal), lpc=self.lpc, diff=self.diff, nd=self.nd, **self.feature_kwargs)
+        feat = mix_feature((fs, signal), lpc=self.lpc, diff=self.diff, nd=self.nd, **self.feature_kwargs)
+        setting = self._norm_setting()
+        if setting is None:
+            return feat
+        from .feature.norm import normalise_many
+        return normalise_many([feat], *setting)[0].astype(np.float64)
 
     def _features_many(self, items):
         """The feature matrices of [(fs, signal), ...] behind the silence removal; a signal it leaves too short for a frame
@@ -219,8 +242,8 @@ class ModelInterface(object):
         refuses ("Signal too short!"), is scored when it yields at least one frame and gets ``None`` when it yields none (as on
         the diagonal sharded route)."""
         items = list(items)
-        if self._silence_kwargs() is not None:
-            gpus = 1                # (silence removal is not part of the sharded route: its slots upload raw PCM themselves)
+        if self._silence_kwargs() is not None or self._norm_setting() is not None:
+            gpus = 1                # (neither is part of the sharded route: its slots upload raw PCM and extract for themselves)
         rates = {fs for fs, _ in items}
         full = getattr(self, "covariance_type", "diag") == "full"
         pcm_ok = len(rates) == 1 and items and all(np.asarray(sig).dtype == np.int16 and np.asarray(sig).ndim == 1 for _, sig in items)
