@@ -25,9 +25,6 @@
 
 namespace sr {
 
-long plda_scratch_mib();   // plda.hip
-long jfa_lds_rows();       // jfa.hip
-
 // M <- (M + M^T) / 2, a lane per element of the lower triangle.
 __global__ __launch_bounds__(PLDA_WG)
 void beig_symmetrise_kernel(double *__restrict__ M, int R) {

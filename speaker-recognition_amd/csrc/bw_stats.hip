@@ -28,6 +28,7 @@
 // sr_bw_stats_resident reduces into the buffers of a statistics handle (jfa_dev.hpp, jfa_stats.hip) and leaves them there.
 #include "batch.hpp"
 #include "bw_plan.hpp"
+#include "bw_stats.hpp"
 #include "gmm_model.hpp"
 #include "jfa_dev.hpp"
 #include "score.hpp"

@@ -20,6 +20,7 @@
 // Both kernels of the loop return at once when the state's stop word is set, so the host enqueues pass + step pairs without reading
 // anything back but that word, every CALIB_CADENCE-th pair.  No atomics; the block size is fixed, so the bits of a result depend on
 // (X, lab, P, lam, theta0, tol, max_pass) only -- not on the number of compute units, an option, or the run.
+#include "calib.hpp"
 #include "calib_plan.hpp"
 #include "common.hpp"
 #include "wave_ops.hpp"

@@ -1,5 +1,6 @@
 // common.cpp -- error parking, lazy device context, HIP-event kernel timers.
 #include "common.hpp"
+#include "fork_proxy.hpp"
 #include "ref_rand.hpp"
 
 #include <climits>
@@ -72,7 +73,6 @@ static std::mutex g_slot_mu;
 // ---- fork (common.hpp) ----
 static std::atomic<long> g_runtime_pid{0};       // the process that made the first HIP call (0: none yet)
 static std::atomic<bool> g_runtime_lost{false};
-void fork_proxy_atfork_child();       // fork_proxy.cpp
 static std::atomic<bool> g_atfork_installed{false};
 
 static void atfork_child() {

@@ -5,6 +5,7 @@
 
 #include "eig_plan.hpp"
 #include "jfa_dev.hpp"
+#include "plda.hpp"
 
 #include <vector>
 
@@ -13,8 +14,6 @@ namespace sr {
 // eig.hip: w [R] descending and V [R][R] (column k the unit eigenvector of w[k], its component of largest magnitude positive, the
 // lowest index winning a tie) of the symmetric A [R][R], whose lower triangle is read and which is overwritten.  Synchronises.
 void sym_eig_device(hipStream_t st, const EigPlan &pl, double *A, double *w, double *V, int *sweeps, int *converged);
-// eig.hip, the host entry behind sr_sym_eig (A, w, V host memory).
-void sym_eig(int R, const double *A, double *w, double *V, int *sweeps, int *converged);
 
 // plda.hip's launchers, as backend_eig.hip needs them (the kernels stay where they are).
 void plda_launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,

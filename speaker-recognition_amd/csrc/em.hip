@@ -12,6 +12,7 @@
 // N_k, sum g (x-mu_old), sum g (x-mu_old)^2 (centred on the current mean, so the variance
 // update does not cancel).  The M-step is O(K*D) and runs on the host in float64 with the
 // reference's formulas.
+#include "em.hpp"
 #include "em_mstep.hpp"
 #include "em_plan.hpp"
 #include "kmeans_init.hpp"
@@ -649,10 +650,6 @@ void em_reduce_kernel(const float *__restrict__ slabs, int n_slabs, int n_elem,
     for (int s = 0; s < n_slabs; s++) acc += (double)slabs[(size_t)s * n_elem + e];
     out[e] = acc;
 }
-
-// em_small.hip, em_f64.hip: true = done; false = handed back (gmm untouched)
-bool train_em_small(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
-bool train_em_f64(GMM &gmm, const GMM *ubm, const float *dX, long n, int dim, const Parameter &param, double relevance, int *iterations);
 
 // The model of one EM / MAP iteration as a set: the vector-ALU layout (the statistics kernels' records) and -- round 4 -- the
 // split-bf16 one, so that the posteriors' denominators and the total log-likelihood of every second iteration run on the matrix

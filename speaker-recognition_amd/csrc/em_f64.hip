@@ -19,6 +19,7 @@
 // The stop rule (gmm.cc:622-650) reads the total under the updated model off the NEXT iteration's e64_head, as em_small.hip does; a
 // live frame within 110 nats of the underflow boundary hands the fit to the iteration-at-a-time path (partial-product flushes).
 #include "score.hpp"
+#include "em.hpp"
 #include "em_f64_dev.hpp"
 
 #include "../../include/pygmm_hip.h"

@@ -28,6 +28,7 @@
 // term lies within 110 nats of the underflow boundary -- where the reference's flushes of PARTIAL products decide (lse.hpp,
 // gmm_flush.hip) -- and anything that is not finite.
 #include "score.hpp"
+#include "em.hpp"
 #include "map_plan.hpp"
 #include "wave_ops.hpp"
 

@@ -25,6 +25,7 @@
 #pragma clang fp contract(off)
 
 #include "batch.hpp"
+#include "featnorm.hpp"
 #include "featnorm_plan.hpp"
 #include "norm_quantile.hpp"
 

@@ -27,6 +27,7 @@
 #include "../../include/pygmm_hip.h"
 
 #include "common.hpp"
+#include "em.hpp"
 #include "fork_proxy.hpp"
 #include "gmm_model.hpp"
 #include "ref_rand.hpp"
@@ -49,10 +50,6 @@
 extern char **environ;
 
 namespace sr {
-
-int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param, long seed);   // em.hip
-void score_one_local(GMM *g, const float *X, long n, int dim, float *ll_out, double *sum_out, int flags);       // abi.cpp
-void score_models_local(GMM *const *models, int n_models, const float *X, long n, int dim, double *sums_out, int flags);   // abi.cpp
 
 namespace {
 
@@ -369,7 +366,7 @@ void put_model_tracked(Writer &w, Helper &h, const GMM &g, std::vector<std::pair
 
 }  // namespace
 
-// ---------------- client entry points (abi.cpp calls these when gpu_runtime_lost()) ----------------
+// ---------------- client entry points (abi_legacy.cpp calls these when gpu_runtime_lost()) ----------------
 
 // pthread_atfork child handler (common.cpp): only the forking thread exists; whoever held the record's mutex does not
 void fork_proxy_atfork_child() { helper().mu = new std::mutex(); }

@@ -20,5 +20,11 @@ void fork_proxy_note_option(const char *key, long value);
 void fork_proxy_set_max_models(long n);
 // pthread_atfork child handler: a fresh mutex for the helper record
 void fork_proxy_atfork_child();
+// abi_legacy.cpp: what the helper computes with, and what the entry points call in a process that still has its runtime
+void score_one_local(GMM *g, const float *X, long n, int dim, float *ll_out, double *sum_out, int flags);
+void score_models_local(GMM *const *models, int n_models, const float *X, long n, int dim, double *sums_out, int flags);
 
 }  // namespace sr
+
+// the helper process's main loop on its end of the socketpair (fork_helper.c finds it by name)
+extern "C" int sr_fork_helper_main(int fd);

@@ -33,6 +33,7 @@
 #include "gmm_model.hpp"
 #include "lse.hpp"
 #include "score.hpp"
+#include "topc.hpp"
 #include "topc_plan.hpp"
 
 #include <algorithm>

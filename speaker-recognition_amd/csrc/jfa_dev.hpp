@@ -4,8 +4,9 @@
 // others (bw_stats.hip includes it for the statistics handle its resident entry fills).
 #pragma once
 
+#include "common.hpp"
+#include "jfa.hpp"
 #include "jfa_plan.hpp"
-#include "score.hpp"
 
 #include <vector>
 
@@ -52,6 +53,9 @@ const SRStats &stats_live(const SRStats *s, const char *what);
 SRStats *stats_new(int64_t n, int K, int D);      // an empty registered handle on the calling thread's device, buffers allocated
 
 #ifdef __HIPCC__
+// jfa.hip's own two triangular solves (its kernels alone call it: device code is not linked across files)
+__device__ void jfa_solve(const double *M, int R, double *T, int64_t ldt, int nrhs);
+
 // ---- the factorisation of one R x R block by one workgroup.  M: the block, row stride R, in LDS or in global memory. ----
 
 // Lower Cholesky factor over the lower triangle of M (the upper triangle is not read).  false: a pivot <= 0 or not finite (every

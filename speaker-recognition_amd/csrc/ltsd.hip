@@ -19,6 +19,7 @@
 // Kernel 2: a workgroup per window takes the 2*order+1 neighbour maxima per bin, divides by the
 // noise power and reduces (float64 sum).
 #include "batch.hpp"
+#include "mfcc.hpp"
 #include "wave_ops.hpp"
 
 #include <cmath>

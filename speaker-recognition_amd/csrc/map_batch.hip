@@ -19,7 +19,9 @@
 // second pass) and stops launching at 0.  A speaker whose flag rose (a live frame within E64_BAND of the underflow boundary, a NaN
 // density) freezes and is refitted alone by train_em afterwards: the iteration-at-a-time path, as its single fit takes it.
 #include "score.hpp"
+#include "em.hpp"
 #include "em_f64_dev.hpp"
+#include "map_batch.hpp"
 #include "map_plan.hpp"
 #include "ref_rand.hpp"
 
@@ -33,10 +35,6 @@
 #include <vector>
 
 namespace sr {
-
-int train_em(GMM &gmm, const GMM *ubm, const float *X, long n, int dim, const Parameter &param, long seed);      // em.hip
-int em_stats_engine();
-int reference_side_effects();
 
 namespace {
 
@@ -212,7 +210,7 @@ void map_fit_batch_stats(long *calls, long *speakers_batched, long *speakers_sin
     if (passes) *passes = g_passes.load();
 }
 
-// The arguments have been checked (abi.cpp).  status / iterations_out / messages: [S]; -> the number of speakers fitted.
+// The arguments have been checked (abi_stats.cpp).  status / iterations_out / messages: [S]; -> the number of speakers fitted.
 int map_fit_batch(GMM *const *models, int S, const GMM *ubm, const float *X, const int64_t *row_offsets, int dim, const Parameter &param,
                   long seed, int *iterations_out, int *status, std::vector<std::string> &messages) {
     ensure_device();

@@ -20,8 +20,6 @@
 
 namespace sr {
 
-bool mfcc_force_generic();
-
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }

@@ -19,6 +19,7 @@
 // with the argmax values behind them.  That log-sum-exp is exact: nothing of a full piece is resolved or scored again afterwards.
 #include "../../include/pygmm_hip.h"
 
+#include "abi_internal.hpp"
 #include "batch.hpp"
 #include "common.hpp"
 #include "gmm_full.hpp"

@@ -245,7 +245,6 @@ static std::atomic<long> &plda_scratch_option() {
 }
 void set_plda_scratch_mib(long v) { plda_scratch_option().store(v); }
 long plda_scratch_mib() { return plda_scratch_option().load(); }
-long jfa_lds_rows();       // jfa.hip
 
 namespace {
 struct PldaScratch {

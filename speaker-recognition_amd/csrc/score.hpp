@@ -221,8 +221,7 @@ void flush_resolve_host(SRModelSet &set, SRBatch &feat, const TileTable &tt, con
                         int *h_argmax);
 int &flush_order_option();     // 2 = partial products as the reference DSO's compiler forms them (default), 1 = source order
 void flush_stats(long *calls, long *pairs, long *frames);
-// PCM batch -> MFCC -> CMVN/deltas -> all models -> sums + argmax on the host (abi.cpp; pipelined over
-// chunks of utterances for large batches).
+// PCM batch -> MFCC -> CMVN/deltas -> all models -> sums + argmax on the host (abi_score.cpp).
 }  // namespace sr
 struct SRMfcc;
 namespace sr {
@@ -230,61 +229,9 @@ void predict_pcm(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, double *sums_
                  const OpenSetFetch *open = nullptr);
 // score_device + fetch with the open-set decision (gmm_score_host.cpp)
 void score_batch_set_open(SRModelSet &set, SRBatch &feat, double *sums_out, const OpenSetFetch &open, int flags);
-// gmm_topc.hip: top-C Gaussian selection against the background column `bg` (opt-in; the exact path never calls it).  Refusals --
-// a set that does not share sigma and weights, bg or top_c out of range, a PCM batch -- come before any device work.
-// topc_out [n_frames][top_c] / frame_ll_out [S][n_frames]: host memory or null.
-void score_batch_set_topc(SRModelSet &set, SRBatch &feat, int bg, int top_c, double *sums_out, int *argmax_out, int *topc_out,
-                          float *frame_ll_out, int flags);
-bool topc_set_tied(SRModelSet &set);       // does the set qualify?  (host only; the answer is kept)
-void set_topc_scratch_mib(long v);
-long topc_scratch_mib();
-// bw_stats.hip: per-utterance Baum-Welch statistics N [U][K], F [U][K * D] (host memory) of the feature batch against model `model`
-// of the set; ll [U] / dropped [U]: host memory or null.  Refusals (bw_plan.cpp: bw_check) come before any device work.
-void bw_stats_batch(SRModelSet &set, int model, SRBatch &feat, double *N_out, double *F_out, double *ll_out, int64_t *dropped_out);
-void set_bw_scratch_mib(long v);
-long bw_scratch_mib();
-void set_bw_range_frames(long v);
-long bw_range_frames();
-}  // namespace sr
-struct SRJfa;
-struct SRStats;
-namespace sr {
-// bw_stats.hip / jfa_stats.hip: the same passes with N and F left on the device in a statistics handle (jfa_dev.hpp); the handle's
-// life.  Every refusal comes before any device work.
-SRStats *bw_stats_resident(SRModelSet &set, int model, SRBatch &feat, double *ll_out, int64_t *dropped_out);
-SRStats *stats_from_host(int64_t n, int K, int D, const double *N, const double *F);
-void stats_info(const SRStats *s, int64_t *out, int n_out);
-void stats_get(const SRStats *s, double *N, double *F);
-SRStats *stats_take(const SRStats *s, const int64_t *rows, int64_t n_rows);
-void stats_close(SRStats *s);
-// jfa_stats.hip: grouping and centring on the device into a factor handle, what it holds, the z / d iteration on it, and the two
-// scorers on a statistics handle (jfa_plan.hpp has the formulas).
-SRJfa *jfa_open_centred(const SRStats *s, const double *E, const double *m, int mode, const int64_t *ids, int64_t n_labels, const double *d,
-                        const double *z, const double *v, int Ry, const double *y, const double *u, int Ru, const double *x);
-void jfa_statistics(SRJfa &h, double *N, double *Fc);
-void jfa_zd(SRJfa &h, double *d, int n_iter, double *z, double *a, double *b);
-void jfa_score_stats(int mode, const SRStats *tst, int64_t J, int Ry, int Ru, const double *m, const double *E, const double *d, const double *v,
-                     const double *u, const double *z, const double *y, const double *x, const unsigned char *mask, int64_t mask_rows,
-                     int64_t mask_cols, double *out, int64_t *empty_segments, int64_t *bad_segments);
-// jfa.hip: JFA factor estimation on resident statistics (eigenvoices, eigenchannels; jfa_plan.hpp has the formulas).  Every
-// refusal (jfa_plan.cpp) comes before any device work.  Host pointers throughout; W [R][K D] in / out where it says so.
-SRJfa *jfa_open(int64_t G, int K, int D, const double *N, const double *Fc, const double *E);
-void jfa_factors(SRJfa &h, const double *W, int R, double *y, double *A, double *C, int64_t *bad_groups);
-void jfa_update(int K, int D, int R, const double *A, const double *C, double *W, int64_t *skipped);
-void jfa_train(SRJfa &h, double *W, int R, int n_iter, double *y, int64_t *skipped);
-void jfa_close(SRJfa *h);
-// jfa_score.hip: the score matrix out [J][T] of J models against T test segments, mode 0 integrated (kscore_famous_19.m), 1 linear
-// (linear_scoring.m; needs x).  d, z, x, mask: null = absent.  Every refusal (jfa_plan.cpp) comes before any device work.
-void jfa_score(int mode, int64_t T, int64_t J, int K, int D, int Ry, int Ru, const double *N, const double *F, const double *m, const double *E,
-               const double *d, const double *v, const double *u, const double *z, const double *y, const double *x, const unsigned char *mask,
-               int64_t mask_rows, int64_t mask_cols, double *out, int64_t *empty_segments, int64_t *bad_segments);
-void set_jfa_scratch_mib(long v);
-long jfa_scratch_mib();
-void set_jfa_lds_rows(long v);
-long jfa_lds_rows();
 // Packs + uploads a model set on the current device.
 void upload_model_set(SRModelSet &s);
-// a GMM handle's own one-model set on the current device, packed and uploaded once (abi.cpp; invalidated by GMM::drop_single)
+// a GMM handle's own one-model set on the current device, packed and uploaded once (abi_model.cpp; invalidated by GMM::drop_single)
 std::shared_ptr<SRModelSet> single_model_set(const GMM *g);
 // the split-bf16 layout of a set that carries one (s.bx3), on the device: lazily, as every matrix-core layout (em.hip reads it too)
 void ensure_bx3_layout(SRModelSet &s);

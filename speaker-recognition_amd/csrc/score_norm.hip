@@ -30,6 +30,7 @@
 // column of Tt only, so the chunking of the test segments under "norm_scratch_mib" does not show, bit for bit.
 #include "jfa_dev.hpp"
 #include "norm_plan.hpp"
+#include "score_norm.hpp"
 
 #include <algorithm>
 #include <atomic>

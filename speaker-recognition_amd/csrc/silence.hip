@@ -22,6 +22,7 @@
 //      new batch; silence_copy_kernel moves the kept frames (32-bit copies where source, destination and lengths are even).
 // The decisions -- g, E, B, the shape of the maps launch -- are plan_silence's (silence_plan.cpp).
 #include "batch.hpp"
+#include "silence.hpp"
 #include "silence_plan.hpp"
 
 #include <algorithm>

@@ -27,6 +27,7 @@
 // of the capture and fixed for the session's life.  A tick that collect re-scores is decided again on its final sums.
 #include "../../include/pygmm_hip.h"
 
+#include "abi_internal.hpp"
 #include "batch.hpp"
 #include "gmm_full.hpp"
 #include "mfcc.hpp"
