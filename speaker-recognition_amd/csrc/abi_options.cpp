@@ -125,7 +125,8 @@ int sr_set_option(const char *key, long value) {
     } else if (k == "plda_scratch_mib") {
         set_scratch_mib(key, value, PLDA_DEFAULT_SCRATCH, set_plda_scratch_mib);
     } else if (k == "jfa_lds_rows") {
-        if (value < 0 || value > JFA_LDS_MAX_R) fail("jfa_lds_rows must be 0 (automatic) or 1 .. %d rows", JFA_LDS_MAX_R);
+        std::string why;
+        if (!dense_check_lds_rows(value, why)) fail("%s rows", why.c_str());
         set_jfa_lds_rows(value);
     } else if (k == "full_fit_batch_bytes") {
         if (value < 1) fail("full_fit_batch_bytes must be >= 1 (the default is %ld)", 1L << 30);

@@ -1,5 +1,5 @@
 // backend_eig.hip -- what the i-vector back end builds on the symmetric eigen-solver (eig.hip), float64 throughout:
-//   gen_eig       Sb v = psi Sw v:  L = chol(Sw) (jfa_cholesky through plda.hip's block inverse), M = L^-1 Sb L^-T by the triangular
+//   gen_eig       Sb v = psi Sw v:  L = chol(Sw) (dense_cholesky through plda.hip's block inverse), M = L^-1 Sb L^-T by the triangular
 //                 inverse and two products, symmetrised as the mean of its halves, M = Q diag(psi) Q^T by sym_eig_device, V = L^-T Q:
 //                 V^T Sw V = I, V^T Sb V = diag(psi), psi descending, the vectors' signs sym_eig's.
 //   lda_fit       mu, the within-class covariance Sw about the class means (what kind "wccn" forms) and the between-class covariance
@@ -13,10 +13,12 @@
 //                 Two products (U, G), ONE cross product over all models whatever their class, one narrow product U.^2 [T][R] by
 //                 [R][classes + 1], an assemble kernel; no factorisation.  The tables of h, 1 / s and the log sums are O(classes R)
 //                 and made on the host, d = 0 .. R - 1 in order.
-// The kernels here are elementwise; every product is jfa.hip's GEMM (launch_gemm), every centring, class sum, row dot product, row
+// The kernels here are elementwise; every product is the dense layer's GEMM (dense64.hpp), every centring, class sum, row dot product, row
 // norm and block inverse plda.hip's (eig_dev.hpp).  No atomics; fixed orders; a score depends on its model's count and sum and on its
 // segment only, so neither the batch nor the chunking under "plda_scratch_mib" shows, bit for bit.
+#include "dense64.hpp"
 #include "eig_dev.hpp"
+#include "jfa.hpp"              // the option jfa_lds_rows, nothing else of JFA's
 
 #include <algorithm>
 #include <cmath>
@@ -117,8 +119,8 @@ static int gen_eig_device(hipStream_t st, BeigScratch &s, const PldaPlan &pl, in
         return 1;
     }
     s.T1.ensure((size_t)rr), s.M.ensure((size_t)rr), s.Q.ensure((size_t)rr);
-    launch_gemm(T_JFA_GEMM_C, st, Sw, R, 1, Sb, R, 1, s.T1.p, R, R, R, R, false, 0);              // L^-1 Sb
-    launch_gemm(T_JFA_GEMM_C, st, s.T1.p, R, 1, Sw, 1, R, s.M.p, R, R, R, R, false, 0);           // (L^-1 Sb) L^-T
+    dense_gemm(T_JFA_GEMM_C, st, Sw, R, 1, Sb, R, 1, s.T1.p, R, R, R, R, false, 0);              // L^-1 Sb
+    dense_gemm(T_JFA_GEMM_C, st, s.T1.p, R, 1, Sw, 1, R, s.M.p, R, R, R, R, false, 0);           // (L^-1 Sb) L^-T
     {
         ScopedKernelTimer tm(T_JFA_UPDATE);
         hipLaunchKernelGGL(beig_symmetrise_kernel, dim3(flat_blocks(rr)), dim3(PLDA_WG), 0, st, s.M.p, R);
@@ -129,7 +131,7 @@ static int gen_eig_device(hipStream_t st, BeigScratch &s, const PldaPlan &pl, in
     if (!plan_eig(R, std::max(1, ctx().n_cu), ep, why)) fail("%s", why.c_str());
     int converged = 0;
     sym_eig_device(st, ep, s.M.p, psi, s.Q.p, sweeps, &converged);
-    launch_gemm(T_JFA_GEMM_C, st, Sw, 1, R, s.Q.p, R, 1, V, R, R, R, R, false, 0);                // V = L^-T Q
+    dense_gemm(T_JFA_GEMM_C, st, Sw, 1, R, s.Q.p, R, 1, V, R, R, R, R, false, 0);                // V = L^-T Q
     sync_stream();
     return converged ? 0 : 2;
 }
@@ -228,7 +230,7 @@ void backend_project(int64_t n, int R, int P, const double *X, const double *mu,
     s.A.upload(A, (size_t)P * R);
     s.Xc.ensure((size_t)(n * R)), s.Y.ensure((size_t)(n * P));
     plda_launch_centre(st, s.X.p, nullptr, s.mu.p, nullptr, nullptr, s.Xc.p, n, R);
-    launch_gemm(T_JFA_GEMM_C, st, s.Xc.p, R, 1, s.A.p, 1, R, s.Y.p, P, n, P, R, false, 0);        // (X - mu) A^T
+    dense_gemm(T_JFA_GEMM_C, st, s.Xc.p, R, 1, s.A.p, 1, R, s.Y.p, P, n, P, R, false, 0);        // (X - mu) A^T
     int64_t zeros = 0;
     if (length_norm) {
         s.flags.ensure((size_t)n);
@@ -301,7 +303,7 @@ void plda_score_diag(int64_t J, int64_t T, int R, const double *mu, const double
     s.Z.ensure((size_t)(chunk * R)), s.U.ensure((size_t)(chunk * R)), s.a.ensure((size_t)(chunk * (nc + 1)));
     s.out.ensure((size_t)(J * T));
     plda_launch_centre(st, s.E.p, nullptr, s.mu.p, nullptr, s.coef.p, s.F.p, J, R);               // f_j = e_j - n_j mu
-    launch_gemm(T_JFA_GEMM_C, st, s.F.p, R, 1, s.V.p, R, 1, s.G.p, R, J, R, R, false, 0);         // G = F V
+    dense_gemm(T_JFA_GEMM_C, st, s.F.p, R, 1, s.V.p, R, 1, s.G.p, R, J, R, R, false, 0);         // G = F V
     {
         ScopedKernelTimer tm(T_JFA_UPDATE);
         hipLaunchKernelGGL(beig_models_kernel, dim3(flat_blocks(J * R)), dim3(PLDA_WG), 0, st, s.G.p, s.cls.p, s.h.p, s.inv_s.p, s.Mm.p, s.Mt.p, J, R);
@@ -312,14 +314,14 @@ void plda_score_diag(int64_t J, int64_t T, int R, const double *mu, const double
         const int64_t t0 = ci * chunk, nt = std::min(chunk, T - t0);
         s.Z.upload(X + t0 * R, (size_t)(nt * R));
         plda_launch_centre(st, s.Z.p, nullptr, s.mu.p, nullptr, nullptr, s.U.p, nt, R);
-        launch_gemm(T_JFA_GEMM_C, st, s.U.p, R, 1, s.V.p, R, 1, s.Z.p, R, nt, R, R, false, 0);    // U = (X - mu) V, in Z
-        launch_gemm(T_JFA_GEMM_C, st, s.Mt.p, R, 1, s.Z.p, 1, R, s.out.p + t0, T, J, nt, R, false, 0);         // Mt U^T: every model at once
+        dense_gemm(T_JFA_GEMM_C, st, s.U.p, R, 1, s.V.p, R, 1, s.Z.p, R, nt, R, R, false, 0);    // U = (X - mu) V, in Z
+        dense_gemm(T_JFA_GEMM_C, st, s.Mt.p, R, 1, s.Z.p, 1, R, s.out.p + t0, T, J, nt, R, false, 0);         // Mt U^T: every model at once
         {
             ScopedKernelTimer tm(T_JFA_UPDATE);
             hipLaunchKernelGGL(beig_square_kernel, dim3(flat_blocks(nt * R)), dim3(PLDA_WG), 0, st, s.Z.p, s.U.p, nt * R);
             SR_HIP(hipGetLastError());
         }
-        launch_gemm(T_JFA_GEMM_C, st, s.U.p, R, 1, s.inv_s.p, 1, R, s.a.p, nc + 1, nt, nc + 1, R, false, 0);   // a = U.^2 [nt][R] by [R][nc + 1]
+        dense_gemm(T_JFA_GEMM_C, st, s.U.p, R, 1, s.inv_s.p, 1, R, s.a.p, nc + 1, nt, nc + 1, R, false, 0);   // a = U.^2 [nt][R] by [R][nc + 1]
         {
             ScopedKernelTimer tm(T_JFA_UPDATE);
             hipLaunchKernelGGL(beig_assemble_kernel, dim3(flat_blocks(J * nt)), dim3(PLDA_WG), 0, st, s.out.p, T, t0, J, nt, s.q.p, s.cls.p, s.a.p, nc,

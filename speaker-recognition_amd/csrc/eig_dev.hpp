@@ -1,10 +1,11 @@
 // eig_dev.hpp -- what eig.hip (the symmetric eigen-solver), backend_eig.hip (the generalised problem, LDA, the diagonalised PLDA
 // scorer) and plda.hip (whose launchers the second reuses) hand each other.  Everything here runs on the calling thread's device
-// and stream; the pointers are device memory unless a comment says host.
+// and stream; the pointers are device memory unless a comment says host.  Nothing of JFA's and nothing of the dense layer's: a file
+// that forms a product includes dense64.hpp itself.
 #pragma once
 
+#include "common.hpp"
 #include "eig_plan.hpp"
-#include "jfa_dev.hpp"
 #include "plda.hpp"
 
 #include <vector>
@@ -15,7 +16,8 @@ namespace sr {
 // lowest index winning a tie) of the symmetric A [R][R], whose lower triangle is read and which is overwritten.  Synchronises.
 void sym_eig_device(hipStream_t st, const EigPlan &pl, double *A, double *w, double *V, int *sweeps, int *converged);
 
-// plda.hip's launchers, as backend_eig.hip needs them (the kernels stay where they are).
+// plda.hip's launchers and host helpers, defined there under these names and used by backend_eig.hip as well (the kernels stay
+// where they are).
 void plda_launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,
                         int64_t rows, int R);
 void plda_launch_class_sums(hipStream_t st, const double *Xs, const int64_t *row_start, double *F, int64_t S, int R);

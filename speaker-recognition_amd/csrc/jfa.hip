@@ -5,17 +5,14 @@
 //   P_c = W_c diag(1 / E_c) W_c^T            L_g = I + sum_c N[g][c] P_c           b_g = W (Fc_g ./ E)
 //   y_g = L_g^-1 b_g                         Q_g = L_g^-1 + y_g y_g^T
 //   A_c = sum_g N[g][c] Q_g                  C   = sum_g y_g Fc_g^T                W_c <- A_c^-1 C_c
-// Everything is float64.  Four kernels, none touching the pass counters (trial scoring, jfa_score.hip, launches the first three
-// through the launchers declared in jfa_dev.hpp, which also holds the Cholesky and the two inverse routines of the fourth):
+// Everything is float64.  The four products  L = I + N P  (reduction over K),  b = Fc (W ./ E)^T  (over K D),  A += N^T Q  and
+// C += Y^T Fc  (over the groups of a chunk) are the dense layer's GEMM (dense64.hpp: strides instead of transposes; an accumulating
+// launch continues from what A and C hold).  Three kernels here, none touching the pass counters (trial scoring, jfa_score.hip,
+// launches the first two through the launchers declared in jfa_dev.hpp; the Cholesky and the two inverse routines inside the third
+// are the layer's, dense64_dev.hpp):
 //   jfa_scale_kernel    W ./ E, once per call (the B operand of the b product).
 //   jfa_gram_kernel     P [K][R][R]: a 16 x 16 tile of one mixture per workgroup, the two row panels of W_c through LDS; the product
 //                       W[i][d] W[j][d] is formed first, so P is symmetric to the bit.
-//   jfa_gemm_kernel     C (+)= A B on v_mfma_f64_16x16x4_f64 with both operands addressed by (row stride, column stride), so one
-//                       kernel serves  L = I + N P  (reduction over K),  b = Fc (W ./ E)^T  (over K D),  A += N^T Q  and
-//                       C += Y^T Fc  (over the groups of a chunk).  A workgroup owns a 64 x 64 tile, a wave 16 rows of it; the
-//                       operands pass through LDS sixteen reduction steps at a time; rows, columns and reduction steps beyond
-//                       the edges are read as zeros.  Accumulating launches start from what C holds, so a sum over groups that is
-//                       cut into chunks of whole reduction tiles is the same sequence of matrix instructions as the uncut one.
 //   jfa_factor_kernel   one workgroup per R x R block: right-looking Cholesky in panels of 16 columns (the panel, all its rows, in
 //                       LDS; the trailing update reads it from there), then either (groups) y by two triangular solves, the inverse
 //                       of the factor in place row by row, L^-T L^-1 in place, + y y^T, mirrored: Q_g over L_g; or (update) the D
@@ -25,6 +22,8 @@
 // C) and it is counted; a mixture of the update: W_c keeps its old value and it is counted.  Nothing non-finite is spread.
 // Deterministic: no atomics; a group's y depends on its own N, Fc and on W only; A and C are summed in group order whatever the
 // chunking -- the results do not depend on the scratch bound, bit for bit.
+#include "dense64.hpp"
+#include "dense64_dev.hpp"
 #include "jfa_dev.hpp"
 
 #include <algorithm>
@@ -33,9 +32,6 @@
 #include <vector>
 
 namespace sr {
-
-typedef double jfa_f64x4 __attribute__((ext_vector_type(4)));
-constexpr int JFA_TS = JFA_TILE + 4;                   // row stride of the GEMM operand tiles in LDS
 
 __global__ __launch_bounds__(JFA_WG)
 void jfa_scale_kernel(const double *__restrict__ W, const double *__restrict__ iE, double *__restrict__ WE, int64_t n, int64_t kd) {
@@ -72,71 +68,8 @@ void jfa_gram_kernel(const double *__restrict__ W, const double *__restrict__ iE
     if (i < R && j < R) P[((int64_t)c * R + i) * R + j] = acc;
 }
 
-// ---- C [M][N] (+)= A [M][Kred] B [Kred][N], A[m][k] at A + m sam + k sak, B[k][n] at B + k sbk + n sbn.  grid (N / 64, M / 64) ----
-// v_mfma_f64_16x16x4_f64: lane l supplies A[row l & 15][k l >> 4] and B[k l >> 4][column l & 15] and receives
-// D[row (l >> 4) + 4 r][column l & 15], r = 0..3 (bw_stats.hip).
-// diag_step > 0: 1 is added to every column that is a multiple of it (L = I + ...: the diagonal of a flattened R x R row).
-__global__ __launch_bounds__(JFA_WG)
-void jfa_gemm_kernel(const double *__restrict__ A, int64_t sam, int64_t sak, const double *__restrict__ B, int64_t sbk, int64_t sbn,
-                     double *__restrict__ C, int64_t ldc, int M, int64_t N, int64_t Kred, int accumulate, int diag_step) {
-    __shared__ double As[JFA_KSTEP][JFA_TS], Bs[JFA_KSTEP][JFA_TS];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 15, fl = lane >> 4;
-    const int64_t m0 = (int64_t)blockIdx.y * JFA_TILE, n0 = (int64_t)blockIdx.x * JFA_TILE;
-    const bool a_kfast = sak == 1, b_nfast = sbn == 1;
-    jfa_f64x4 acc[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; nb++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int64_t row = m0 + wave * 16 + fl + 4 * r, col = n0 + 16 * nb + j;
-            acc[nb][r] = (accumulate && row < M && col < N) ? C[row * ldc + col] : 0.0;
-        }
-    for (int64_t k0 = 0; k0 < Kred; k0 += JFA_KSTEP) {
-        double ra[4], rb[4];
-        int am[4], ak[4], bn[4], bk[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int idx = tid + JFA_WG * e;                      // 0 .. 1023: the 64 x 16 elements of either tile
-            am[e] = a_kfast ? idx >> 4 : idx & 63;
-            ak[e] = a_kfast ? idx & 15 : idx >> 6;
-            bn[e] = b_nfast ? idx & 63 : idx >> 4;
-            bk[e] = b_nfast ? idx >> 6 : idx & 15;
-            const int64_t gm = m0 + am[e], gka = k0 + ak[e], gn = n0 + bn[e], gkb = k0 + bk[e];
-            ra[e] = (gm < M && gka < Kred) ? A[gm * sam + gka * sak] : 0.0;
-            rb[e] = (gn < N && gkb < Kred) ? B[gkb * sbk + gn * sbn] : 0.0;
-        }
-        __syncthreads();                       // the previous tiles have been consumed by every wave
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            As[ak[e]][am[e]] = ra[e];
-            Bs[bk[e]][bn[e]] = rb[e];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < JFA_KSTEP / 4; s++) {
-            const double av = As[4 * s + fl][wave * 16 + j];
-#pragma unroll
-            for (int nb = 0; nb < 4; nb++) acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bs[4 * s + fl][16 * nb + j], acc[nb], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int nb = 0; nb < 4; nb++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int64_t row = m0 + wave * 16 + fl + 4 * r, col = n0 + 16 * nb + j;
-            if (row < M && col < N) {
-                double v = acc[nb][r];
-                if (diag_step > 0 && col % diag_step == 0) v += 1.0;
-                C[row * ldc + col] = v;
-            }
-        }
-}
-
 // T [R][nrhs] (row stride ldt; LDS or global memory) <- (F F^T)^-1 T with the factor F in M's lower triangle: two triangular solves.
-__device__ void jfa_solve(const double *M, int R, double *T, int64_t ldt, int nrhs) {
+static __device__ void jfa_solve(const double *M, int R, double *T, int64_t ldt, int nrhs) {
     const int tid = threadIdx.x;
     for (int j = 0; j < R; j++) {
         const double djj = M[(int64_t)j * R + j];
@@ -168,8 +101,8 @@ __global__ __launch_bounds__(JFA_WG)
 void jfa_factor_kernel(double *__restrict__ blocks, int R, int use_lds, int mode, const double *__restrict__ rhs, int64_t rhs_ld,
                        double *__restrict__ out, int D, int *__restrict__ flags) {
     extern __shared__ double jfa_lds[];
-    double *pan = jfa_lds;                     // [R][JFA_PS]
-    double *t = pan + (size_t)R * JFA_PS;      // [R]
+    double *pan = jfa_lds;                     // [R][DENSE_PS]
+    double *t = pan + (size_t)R * DENSE_PS;      // [R]
     double *buf = t + R;                       // [R]
     double *mat = buf + R;                     // [R][R], LDS path only
     const int tid = threadIdx.x;
@@ -182,7 +115,7 @@ void jfa_factor_kernel(double *__restrict__ blocks, int R, int use_lds, int mode
         M = mat;
         __syncthreads();
     }
-    const bool ok = jfa_cholesky(M, R, pan);
+    const bool ok = dense_cholesky(M, R, pan);
     __syncthreads();
     if (mode == 0) {
         double *yg = out + g * R;
@@ -196,8 +129,8 @@ void jfa_factor_kernel(double *__restrict__ blocks, int R, int use_lds, int mode
         __syncthreads();
         jfa_solve(M, R, t, 1, 1);
         for (int i = tid; i < R; i += JFA_WG) yg[i] = t[i];
-        jfa_tri_inverse(M, R, buf);
-        jfa_inverse_from_tri(M, R, buf, t);
+        dense_tri_inverse(M, R, buf);
+        dense_inverse_from_tri(M, R, buf, t);
         if (use_lds)
             for (int e = tid; e < rr; e += JFA_WG) Mg[e] = mat[e];
         if (tid == 0) flags[g] = 0;
@@ -239,15 +172,6 @@ struct JfaUpdateScratch {
     DevBuf<int> flags;
 };
 }  // namespace
-
-void launch_gemm(TimerKind kind, hipStream_t st, const double *A, int64_t sam, int64_t sak, const double *B, int64_t sbk, int64_t sbn, double *C,
-                 int64_t ldc, int64_t M, int64_t N, int64_t Kred, bool accumulate, int diag_step) {
-    ScopedKernelTimer t(kind);
-    const dim3 grid((unsigned)((N + JFA_TILE - 1) / JFA_TILE), (unsigned)((M + JFA_TILE - 1) / JFA_TILE));
-    hipLaunchKernelGGL(jfa_gemm_kernel, grid, dim3(JFA_WG), 0, st, A, sam, sak, B, sbk, sbn, C, ldc, (int)M, N, Kred, accumulate ? 1 : 0,
-                       diag_step);
-    SR_HIP(hipGetLastError());
-}
 
 void launch_scale(hipStream_t st, const double *W, const double *iE, double *WE, int64_t n, int64_t kd) {
     hipLaunchKernelGGL(jfa_scale_kernel, dim3((unsigned)((n + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, W, iE, WE, n, kd);
@@ -303,12 +227,12 @@ static void jfa_run_factors(SRJfa &h, int R, bool accumulate, const JfaPlan &pl)
     }
     for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
         const int64_t g0 = ci * pl.chunk, n = std::min(pl.chunk, G - g0);
-        launch_gemm(T_JFA_GEMM_L, st, h.N.p + g0 * K, K, 1, h.P.p, rr, 1, h.L.p, rr, n, rr, K, false, R + 1);                 // L = I + N P
-        launch_gemm(T_JFA_GEMM_B, st, h.Fc.p + g0 * kd, kd, 1, h.WE.p, 1, kd, h.B.p + g0 * R, R, n, R, kd, false, 0);         // b = Fc (W ./ E)^T
+        dense_gemm(T_JFA_GEMM_L, st, h.N.p + g0 * K, K, 1, h.P.p, rr, 1, h.L.p, rr, n, rr, K, false, R + 1);                 // L = I + N P
+        dense_gemm(T_JFA_GEMM_B, st, h.Fc.p + g0 * kd, kd, 1, h.WE.p, 1, kd, h.B.p + g0 * R, R, n, R, kd, false, 0);         // b = Fc (W ./ E)^T
         launch_factor(st, T_JFA_FACTOR, n, h.L.p, R, pl.path, 0, h.B.p + g0 * R, R, h.Y.p + g0 * R, 0, h.flags.p + g0);
         if (accumulate) {
-            launch_gemm(T_JFA_GEMM_A, st, h.N.p + g0 * K, 1, K, h.L.p, rr, 1, h.A.p, rr, K, rr, n, ci > 0, 0);                // A += N^T Q
-            launch_gemm(T_JFA_GEMM_C, st, h.Y.p + g0 * R, 1, R, h.Fc.p + g0 * kd, kd, 1, h.C.p, kd, R, kd, n, ci > 0, 0);     // C += Y^T Fc
+            dense_gemm(T_JFA_GEMM_A, st, h.N.p + g0 * K, 1, K, h.L.p, rr, 1, h.A.p, rr, K, rr, n, ci > 0, 0);                // A += N^T Q
+            dense_gemm(T_JFA_GEMM_C, st, h.Y.p + g0 * R, 1, R, h.Fc.p + g0 * kd, kd, 1, h.C.p, kd, R, kd, n, ci > 0, 0);     // C += Y^T Fc
         }
     }
 }

@@ -1,4 +1,5 @@
-// jfa_plan.cpp -- the decisions of the JFA factor estimation (jfa_plan.hpp).  Host-only.
+// jfa_plan.cpp -- the decisions of the JFA factor estimation, centring and trial scoring (jfa_plan.hpp); the GEMM's grids, the
+// factorisation's path and their LDS bytes are the dense layer's (dense64_plan.hpp).  Host-only.
 #include "jfa_plan.hpp"
 
 #include <algorithm>
@@ -93,22 +94,10 @@ bool jfa_check_stats(int64_t G, int K, int D, const double *N, const double *Fc,
     return true;
 }
 
-int jfa_lds_limit(int lds_rows) { return lds_rows <= 0 ? JFA_LDS_MAX_R : std::min(lds_rows, JFA_LDS_MAX_R); }
-
-int jfa_factor_lds_bytes(int R, int path) {
-    // the panel [R][JFA_NB + 1], two vectors [R], and on the LDS path the block itself
-    return (int)(((int64_t)R * (JFA_NB + 1) + 2 * (int64_t)R + (path == 0 ? (int64_t)R * R : 0)) * (int64_t)sizeof(double));
-}
-
-static JfaGrid gemm_grid(int64_t M, int64_t N) { return JfaGrid{(N + JFA_TILE - 1) / JFA_TILE, (M + JFA_TILE - 1) / JFA_TILE}; }
-
 bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_rows, int n_cu, JfaPlan &p, std::string &why) {
     p = JfaPlan();
     if (!jfa_check_shape(G, K, D, why) || !jfa_check_rank(R, why)) return false;
-    if (lds_rows < 0 || lds_rows > JFA_LDS_MAX_R) {
-        why = fmt("jfa_lds_rows must be 0 (automatic) or 1 .. %lld", JFA_LDS_MAX_R);
-        return false;
-    }
+    if (!dense_check_lds_rows(lds_rows, why)) return false;
     if (n_cu < 1) {
         why = "JFA factors: the plan needs the number of compute units";
         return false;
@@ -116,11 +105,11 @@ bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_row
     const int64_t rr = (int64_t)R * R, kd = (int64_t)K * D, block = rr * (int64_t)sizeof(double);
     const int64_t fit = scratch_bytes / block;
     if (fit >= G) p.chunk = G;
-    else p.chunk = fit / JFA_KSTEP * JFA_KSTEP;
-    p.chunk = std::min<int64_t>(p.chunk, (int64_t)65535 * JFA_TILE);       // (a chunk's row tiles are the L launch's grid y)
+    else p.chunk = fit / DENSE_KSTEP * DENSE_KSTEP;
+    p.chunk = std::min<int64_t>(p.chunk, (int64_t)65535 * DENSE_TILE);       // (a chunk's row tiles are the L launch's grid y)
     if (p.chunk < 1) {
         why = fmt("JFA factors: the scratch bound of %lld bytes is below one chunk of %lld bytes (16 groups' R x R blocks); raise the option jfa_scratch_mib",
-                  scratch_bytes, std::min<int64_t>(G, JFA_KSTEP) * block);
+                  scratch_bytes, std::min<int64_t>(G, DENSE_KSTEP) * block);
         return false;
     }
     if (rr * (int64_t)K > ((int64_t)1 << 40)) {
@@ -136,16 +125,16 @@ bool plan_jfa(int64_t G, int K, int D, int R, int64_t scratch_bytes, int lds_row
     p.bytes_W = 2 * p.bytes_C;
     p.bytes_y = 2 * G * R * 8;
     p.bytes_scratch = p.chunk * block;
-    p.lds_rows = jfa_lds_limit(lds_rows);
+    p.lds_rows = dense_lds_limit(lds_rows);
     p.path = R <= p.lds_rows ? 0 : 1;
     const int64_t gt = (R + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE;
-    p.gram = JfaGrid{K, gt * gt};         // (mixtures along x: the larger limit)
-    p.gemm_L = gemm_grid(p.chunk, rr);
-    p.gemm_b = gemm_grid(p.chunk, R);
-    p.gemm_A = gemm_grid(K, rr);
-    p.gemm_C = gemm_grid(R, kd);
+    p.gram = Grid2{K, gt * gt};         // (mixtures along x: the larger limit)
+    p.gemm_L = dense_gemm_grid(p.chunk, rr);
+    p.gemm_b = dense_gemm_grid(p.chunk, R);
+    p.gemm_A = dense_gemm_grid(K, rr);
+    p.gemm_C = dense_gemm_grid(R, kd);
     p.gram_lds = 2 * JFA_GRAM_TILE * (JFA_GRAM_DSTEP + 1) * (int)sizeof(double) + JFA_GRAM_DSTEP * (int)sizeof(double);
-    p.gemm_lds = 2 * JFA_KSTEP * (JFA_TILE + 4) * (int)sizeof(double);
+    p.gemm_lds = dense_gemm_lds_bytes();
     p.factor_lds = p.update_lds = jfa_factor_lds_bytes(R, p.path);
     p.factor_rounds = (p.chunk + n_cu - 1) / n_cu;
     return true;
@@ -204,11 +193,11 @@ bool plan_jfa_centre(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, 
     if (Ru > 0) {
         // a function of n, K D and the bound only: whole GEMM row tiles, so that a chunk's product is full tiles but the last
         const int64_t fit = scratch_bytes / row;
-        p.chunk = fit >= n ? n : fit / JFA_TILE * JFA_TILE;
-        p.chunk = std::min<int64_t>(p.chunk, (int64_t)65535 * JFA_TILE);
+        p.chunk = fit >= n ? n : fit / DENSE_TILE * DENSE_TILE;
+        p.chunk = std::min<int64_t>(p.chunk, (int64_t)65535 * DENSE_TILE);
         if (p.chunk < 1) {
             why = fmt("JFA centring: the scratch bound of %lld bytes is below one chunk of %lld bytes (64 sessions' rows of the x u product); "
-                      "raise the option jfa_scratch_mib", scratch_bytes, std::min<int64_t>(n, JFA_TILE) * row);
+                      "raise the option jfa_scratch_mib", scratch_bytes, std::min<int64_t>(n, DENSE_TILE) * row);
             return false;
         }
         p.bytes_scratch = p.chunk * row;
@@ -226,10 +215,10 @@ bool plan_jfa_centre(int64_t n, int64_t n_labels, int K, int D, int Ry, int Ru, 
         why = "JFA centring: more than 2^24 supervector columns; split the model";
         return false;
     }
-    if (Ru > 0) p.gemm_xu = gemm_grid(p.chunk, kd);
-    if (Ry > 0) p.gemm_yv = gemm_grid(labels, kd);
-    p.centre = JfaGrid{std::min(rows, mode == JFA_CENTRE_SESSIONS ? p.chunk : rows), col_blocks};
-    p.counts = JfaGrid{rows, (K + JFA_WG - 1) / JFA_WG};
+    if (Ru > 0) p.gemm_xu = dense_gemm_grid(p.chunk, kd);
+    if (Ry > 0) p.gemm_yv = dense_gemm_grid(labels, kd);
+    p.centre = Grid2{std::min(rows, mode == JFA_CENTRE_SESSIONS ? p.chunk : rows), col_blocks};
+    p.counts = Grid2{rows, (K + JFA_WG - 1) / JFA_WG};
     return true;
 }
 
@@ -250,9 +239,9 @@ bool jfa_score_check_shape(int64_t T, int64_t J, int K, int D, int Ry, int Ru, i
         return false;
     }
     const int64_t kd = (int64_t)K * D, cap = (int64_t)1 << 36;
-    if (T > (int64_t)65535 * JFA_TILE || J > JFA_SCORE_MAX_J || kd > ((int64_t)1 << 31) - 1 || T > cap / kd || J + 1 > cap / kd) {
+    if (T > (int64_t)65535 * DENSE_TILE || J > JFA_SCORE_MAX_J || kd > ((int64_t)1 << 31) - 1 || T > cap / kd || J + 1 > cap / kd) {
         why = fmt("JFA scoring: more than %lld test segments or %lld models, or statistics or models of more than 2^36 values; split the trial list",
-                  (int64_t)65535 * JFA_TILE, JFA_SCORE_MAX_J);
+                  (int64_t)65535 * DENSE_TILE, JFA_SCORE_MAX_J);
         return false;
     }
     return true;
@@ -308,43 +297,40 @@ bool jfa_score_check_inputs_resident(int64_t T, int64_t J, int K, int D, int Ry,
     return score_check_inputs(true, T, J, K, D, Ry, Ru, mode, nullptr, nullptr, m, E, d, v, u, z, y, x, mask, mask_rows, mask_cols, why);
 }
 
-static JfaGrid flat_grid(int64_t n) { return JfaGrid{(n + JFA_WG - 1) / JFA_WG, 1}; }
+static Grid2 flat_grid(int64_t n) { return Grid2{(n + JFA_WG - 1) / JFA_WG, 1}; }
 
 bool plan_jfa_score(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode, int64_t scratch_bytes, int lds_rows, int n_cu, JfaScorePlan &p,
                     std::string &why) {
     p = JfaScorePlan();
     if (!jfa_score_check_shape(T, J, K, D, Ry, Ru, mode, why)) return false;
-    if (lds_rows < 0 || lds_rows > JFA_LDS_MAX_R) {
-        why = fmt("jfa_lds_rows must be 0 (automatic) or 1 .. %lld", JFA_LDS_MAX_R);
-        return false;
-    }
+    if (!dense_check_lds_rows(lds_rows, why)) return false;
     if (n_cu < 1) {
         why = "JFA scoring: the plan needs the number of compute units";
         return false;
     }
     const int64_t rr = (int64_t)Ru * Ru, kd = (int64_t)K * D, J1 = J + 1;
     p.mode = mode;
-    p.lds_rows = jfa_lds_limit(lds_rows);
+    p.lds_rows = dense_lds_limit(lds_rows);
     p.path = Ru <= p.lds_rows ? 0 : 1;
     p.bytes_N = T * K * 8;
     p.bytes_F = T * kd * 8;
     p.bytes_uE = 2 * (int64_t)Ru * kd * 8;
     p.bytes_out = J * T * 8;
-    p.gemm_lds = 2 * JFA_KSTEP * (JFA_TILE + 4) * (int)sizeof(double);
-    p.gemm_yv = gemm_grid(J, kd);
+    p.gemm_lds = dense_gemm_lds_bytes();
+    p.gemm_yv = dense_gemm_grid(J, kd);
     if (mode == JFA_SCORE_LINEAR) {
         p.chunk = T;
         p.n_chunks = 1;
         p.bytes_M = p.bytes_ME = J * kd * 8;
         p.bytes_comp = T * kd * 8;
         p.synth = p.scale_M = flat_grid(J * kd);
-        p.gemm_xu = gemm_grid(T, kd);
+        p.gemm_xu = dense_gemm_grid(T, kd);
         p.comp = flat_grid(T * kd);
-        p.gemm_out = gemm_grid(J, T);
+        p.gemm_out = dense_gemm_grid(J, T);
         return true;
     }
     p.seg_bytes = (rr + J1 * Ru) * (int64_t)sizeof(double);
-    p.chunk = std::min<int64_t>(std::min<int64_t>(T, scratch_bytes / p.seg_bytes), (int64_t)65535 * JFA_TILE);      // (row tiles: the GEMMs' grid y)
+    p.chunk = std::min<int64_t>(std::min<int64_t>(T, scratch_bytes / p.seg_bytes), (int64_t)65535 * DENSE_TILE);      // (row tiles: the GEMMs' grid y)
     if (p.chunk < 1) {
         why = fmt("JFA scoring: the scratch bound of %lld bytes is below one test segment's blocks of %lld bytes (Ru x Ru and (J + 1) x Ru doubles); "
                   "raise the option jfa_scratch_mib or score fewer models at a time", scratch_bytes, p.seg_bytes);
@@ -365,15 +351,15 @@ bool plan_jfa_score(int64_t T, int64_t J, int K, int D, int Ry, int Ru, int mode
     p.synth = p.scale_M = flat_grid(J1 * kd);
     p.scale_u = flat_grid(Ru * kd);
     const int64_t gr = (Ru + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE, gj = (J1 + JFA_GRAM_TILE - 1) / JFA_GRAM_TILE;
-    p.gram = JfaGrid{K, gr * gr};
-    p.cross = JfaGrid{K, gj};
+    p.gram = Grid2{K, gr * gr};
+    p.cross = Grid2{K, gj};
     p.cross_z = gr;
-    p.gemm_L = gemm_grid(p.chunk, rr);
-    p.gemm_a = gemm_grid(p.chunk, Ru);
-    p.gemm_lin = gemm_grid(p.chunk, J1);
-    p.gemm_quad = gemm_grid(p.chunk, J1);
-    p.gemm_h = gemm_grid(p.chunk, Ru * J1);
-    p.kscore = JfaGrid{p.chunk, 1};
+    p.gemm_L = dense_gemm_grid(p.chunk, rr);
+    p.gemm_a = dense_gemm_grid(p.chunk, Ru);
+    p.gemm_lin = dense_gemm_grid(p.chunk, J1);
+    p.gemm_quad = dense_gemm_grid(p.chunk, J1);
+    p.gemm_h = dense_gemm_grid(p.chunk, Ru * J1);
+    p.kscore = Grid2{p.chunk, 1};
     p.gram_lds = 2 * JFA_GRAM_TILE * (JFA_GRAM_DSTEP + 1) * (int)sizeof(double) + JFA_GRAM_DSTEP * (int)sizeof(double);
     p.cross_lds = 3 * JFA_GRAM_TILE * (JFA_GRAM_DSTEP + 1) * (int)sizeof(double);
     p.kscore_lds = jfa_factor_lds_bytes(Ru, p.path);

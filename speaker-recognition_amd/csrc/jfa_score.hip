@@ -8,12 +8,12 @@
 //     The reference forms u' (N_t ./ E .* M_j) per pair (K D Ru operations); G is formed once per call and h for all pairs of a chunk
 //     is ONE product N [n x K] G [K x Ru (J + 1)]: K Ru operations a pair.
 //   linear (linear_scoring.m)        out[j][t] = sum_i ((z_j .* d + y_j v)[i] / E[i]) (F[t][i] - N[t][c(i)] (m + x_t u)[i]) / n_t.
-// Float64 throughout.  Every product goes through jfa.hip's jfa_gemm_kernel, the scalings and P through its scale and gram kernels
-// (jfa_dev.hpp); the kernels here:
+// Float64 throughout.  Every product goes through the dense layer's GEMM (dense64.hpp), the scalings and P through jfa.hip's scale
+// and gram kernels (jfa_dev.hpp); the kernels here:
 //   jfa_synth_kernel       M = [m;] (m +) z .* d + y v over the product y v, elementwise.
 //   jfa_cross_kernel       q and G: a 16 x 16 tile (channel factors x models) of one mixture per workgroup, as the gram kernel; G is laid
 //                          out [c][r][j], models fastest, so that h [t][r][j] has the models contiguous for the substitution.
-//   jfa_kscore_kernel      one workgroup per test segment: the panel Cholesky of L_t (jfa_dev.hpp; in LDS up to jfa_lds_rows rows, in
+//   jfa_kscore_kernel      one workgroup per test segment: the panel Cholesky of L_t (dense64_dev.hpp; in LDS up to jfa_lds_rows rows, in
 //                          place above), then ONE forward substitution over all J + 1 right-hand sides a_t - h[t][.][j], a lane per
 //                          model walking its column row by row, the column norms, the scores and the subtraction of column 0.
 //   jfa_compensate_kernel  linear mode's (F - N (m + x u)) / n_t over the product x u, elementwise.
@@ -21,6 +21,8 @@
 // independent, a segment has its own workgroup, a model its own lane): the same bits alone and in any batch, under any scratch bound.
 // Degenerate inputs: a segment with n_t = 0 gets a row of zeros (the reference divides by zero); a segment whose L_t does not factor
 // gets zeros and is counted.  Nothing non-finite is spread.
+#include "dense64.hpp"
+#include "dense64_dev.hpp"
 #include "jfa_dev.hpp"
 
 #include <algorithm>
@@ -88,8 +90,8 @@ void jfa_kscore_kernel(double *__restrict__ L, int Ru, int use_lds, const double
                        const double *__restrict__ quad, const double *__restrict__ nt, int64_t J1, int64_t T, int64_t t0,
                        double *__restrict__ out, int *__restrict__ flags) {
     extern __shared__ double jfa_score_lds[];
-    double *pan = jfa_score_lds;               // [Ru][JFA_PS]
-    double *s0 = pan + (size_t)Ru * JFA_PS;    // [2 Ru] spare: the UBM's score in its first element
+    double *pan = jfa_score_lds;               // [Ru][DENSE_PS]
+    double *s0 = pan + (size_t)Ru * DENSE_PS;    // [2 Ru] spare: the UBM's score in its first element
     double *mat = s0 + 2 * Ru;                 // [Ru][Ru], LDS path only
     const int tid = threadIdx.x;
     const int64_t g = blockIdx.x, t = t0 + g;
@@ -104,7 +106,7 @@ void jfa_kscore_kernel(double *__restrict__ L, int Ru, int use_lds, const double
             Mf = mat;
             __syncthreads();
         }
-        ok = jfa_cholesky(Mf, Ru, pan);
+        ok = dense_cholesky(Mf, Ru, pan);
         __syncthreads();
         if (tid == 0) flags[t] = ok ? 0 : 1;
     } else if (tid == 0) {
@@ -224,7 +226,7 @@ void jfa_score_device(const JfaScorePlan &pl, int64_t T, int64_t J, int K, int D
     w.ME.ensure((size_t)(rows * kd));
     w.out.ensure((size_t)(J * T));
     // the models: y v, then m + z .* d (row 0 = m in integrated mode), then ./ E
-    launch_gemm(T_JFA_GEMM_C, st, w.y.p, Ry, 1, w.v.p, kd, 1, w.M.p + ubm_row * kd, kd, J, kd, Ry, false, 0);
+    dense_gemm(T_JFA_GEMM_C, st, w.y.p, Ry, 1, w.v.p, kd, 1, w.M.p + ubm_row * kd, kd, J, kd, Ry, false, 0);
     {
         ScopedKernelTimer tm(T_JFA_GRAM);
         hipLaunchKernelGGL(jfa_synth_kernel, dim3((unsigned)((rows * kd + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, w.m.p,
@@ -255,11 +257,11 @@ void jfa_score_device(const JfaScorePlan &pl, int64_t T, int64_t J, int K, int D
         for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
             const int64_t t0 = ci * pl.chunk, n = std::min(pl.chunk, T - t0);
             const double *Nc = dN + t0 * K, *Fc = dF + t0 * kd;
-            launch_gemm(T_JFA_GEMM_L, st, Nc, K, 1, w.P.p, rr, 1, w.L.p, rr, n, rr, K, false, Ru + 1);                        // L = I + N P
-            launch_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.uE.p, 1, kd, w.a.p + t0 * Ru, Ru, n, Ru, kd, false, 0);                // a = F (u ./ E)^T
-            launch_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.ME.p, 1, kd, w.lin.p + t0 * J1, J1, n, J1, kd, false, 0);              // lin = F (M ./ E)^T
-            launch_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.q.p, 1, K, w.quad.p + t0 * J1, J1, n, J1, K, false, 0);                 // quad = N q^T
-            launch_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.G.p, Ru * J1, 1, w.h.p, Ru * J1, n, Ru * J1, K, false, 0);              // h = N G
+            dense_gemm(T_JFA_GEMM_L, st, Nc, K, 1, w.P.p, rr, 1, w.L.p, rr, n, rr, K, false, Ru + 1);                        // L = I + N P
+            dense_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.uE.p, 1, kd, w.a.p + t0 * Ru, Ru, n, Ru, kd, false, 0);                // a = F (u ./ E)^T
+            dense_gemm(T_JFA_GEMM_B, st, Fc, kd, 1, w.ME.p, 1, kd, w.lin.p + t0 * J1, J1, n, J1, kd, false, 0);              // lin = F (M ./ E)^T
+            dense_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.q.p, 1, K, w.quad.p + t0 * J1, J1, n, J1, K, false, 0);                 // quad = N q^T
+            dense_gemm(T_JFA_GEMM_A, st, Nc, K, 1, w.G.p, Ru * J1, 1, w.h.p, Ru * J1, n, Ru * J1, K, false, 0);              // h = N G
             launch_kscore(st, pl, n, w.L.p, Ru, w.a.p, w.h.p, w.lin.p, w.quad.p, d_nt, J1, T, t0, w.out.p, w.flags.p);
         }
         std::vector<int> host((size_t)T);
@@ -270,14 +272,14 @@ void jfa_score_device(const JfaScorePlan &pl, int64_t T, int64_t J, int K, int D
     } else {
         w.x.upload(x, (size_t)(T * Ru));
         w.h.ensure((size_t)(T * kd));          // the compensated statistics
-        launch_gemm(T_JFA_GEMM_C, st, w.x.p, Ru, 1, w.u.p, kd, 1, w.h.p, kd, T, kd, Ru, false, 0);                            // x u
+        dense_gemm(T_JFA_GEMM_C, st, w.x.p, Ru, 1, w.u.p, kd, 1, w.h.p, kd, T, kd, Ru, false, 0);                            // x u
         {
             ScopedKernelTimer tm(T_JFA_GRAM);
             hipLaunchKernelGGL(jfa_compensate_kernel, dim3((unsigned)((T * kd + JFA_WG - 1) / JFA_WG)), dim3(JFA_WG), 0, st, dF, dN, w.m.p, w.h.p,
                                d_nt, T * kd, K, D);
             SR_HIP(hipGetLastError());
         }
-        launch_gemm(T_JFA_GEMM_B, st, w.ME.p, kd, 1, w.h.p, 1, kd, w.out.p, T, J, T, kd, false, 0);                           // out = (M ./ E) Fc^T
+        dense_gemm(T_JFA_GEMM_B, st, w.ME.p, kd, 1, w.h.p, 1, kd, w.out.p, T, J, T, kd, false, 0);                           // out = (M ./ E) Fc^T
         w.out.download(out, (size_t)(J * T));
         sync_stream();
     }

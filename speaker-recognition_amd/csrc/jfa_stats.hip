@@ -4,7 +4,7 @@
 //                         (sr_bw_stats_resident) or uploaded once (sr_stats_from_host); validated when made -- on the host before
 //                         the upload, or by jfa_stats_check_kernel on the pass's result -- so that no consumer meets a NaN later.
 //   sr_jfa_open_centred   the grouping and centring jfa.py does in numpy, on the device, into an ordinary factor handle
-//                         (jfa_plan.hpp has the formulas): y v and a chunk of x u through jfa.hip's GEMM on v_mfma_f64_16x16x4_f64,
+//                         (jfa_plan.hpp has the formulas): y v and a chunk of x u through the dense layer's GEMM (dense64.hpp),      
 //                         then one streaming kernel.  jfa_centre_kernel: a workgroup owns 256 (or 512: two per lane, 16-byte
 //                         accesses, where K D is even) columns of one group's row and walks that group's sessions of the chunk in
 //                         ascending order from a host-built index; it reads F once, N once, the product once and writes Fc once.
@@ -15,6 +15,7 @@
 //   jfa_segment_totals    the scorers' n_t = a segment's K counts added in mixture order, as the host-array entry adds them.
 // No atomics anywhere: a group's row is the same bits alone, inside any batch, under any bound and from run to run -- row r of a
 // matrix-core product depends on row r of its first operand only, and every sum has one fixed order.
+#include "dense64.hpp"
 #include "jfa_dev.hpp"
 
 #include <algorithm>
@@ -493,7 +494,7 @@ SRJfa *jfa_open_centred(const SRStats *sp, const double *E, const double *m, int
             w.y.upload(rows_buf.data(), rows_buf.size());
             w.v.upload(v, (size_t)(Ry * kd));
             w.yv.ensure((size_t)(P * kd));
-            launch_gemm(T_JFA_GEMM_C, st, w.y.p, Ry, 1, w.v.p, kd, 1, w.yv.p, kd, P, kd, Ry, false, 0);          // y v
+            dense_gemm(T_JFA_GEMM_C, st, w.y.p, Ry, 1, w.v.p, kd, 1, w.yv.p, kd, P, kd, Ry, false, 0);          // y v
             dyv = w.yv.p;
         }
         if (u) {
@@ -515,7 +516,7 @@ SRJfa *jfa_open_centred(const SRStats *sp, const double *E, const double *m, int
         }
         for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
             const int64_t j0 = ci * pl.chunk, nc = std::min(pl.chunk, n - j0);
-            if (u) launch_gemm(T_JFA_GEMM_C, st, w.x.p + j0 * Ru, Ru, 1, w.u.p, kd, 1, w.xu.p, kd, nc, kd, Ru, false, 0);      // x u of the chunk
+            if (u) dense_gemm(T_JFA_GEMM_C, st, w.x.p + j0 * Ru, Ru, 1, w.u.p, kd, 1, w.xu.p, kd, nc, kd, Ru, false, 0);      // x u of the chunk
             int64_t n_entries = nc;
             const int4 *entries = nullptr;
             if (mode == JFA_CENTRE_GROUPS) {

@@ -1,4 +1,5 @@
-// norm_plan.cpp -- the decisions of score normalisation (norm_plan.hpp).  Host-only.
+// norm_plan.cpp -- the decisions of score normalisation (norm_plan.hpp); the grids and LDS bytes of as2's products are the dense
+// layer's (dense64_plan.hpp).  Host-only.
 #include "norm_plan.hpp"
 
 #include <algorithm>
@@ -126,8 +127,7 @@ bool norm_check_select(int64_t rows, int64_t C, int top_n, const double *X, std:
     return check_finite(X, rows * C, "X", why);
 }
 
-static NormGrid gemm_grid(int64_t M, int64_t N) { return NormGrid{(N + NORM_TILE - 1) / NORM_TILE, (M + NORM_TILE - 1) / NORM_TILE}; }
-static NormGrid flat_grid(int64_t n) { return NormGrid{(n + NORM_WG - 1) / NORM_WG, 1}; }
+static Grid2 flat_grid(int64_t n) { return Grid2{(n + NORM_WG - 1) / NORM_WG, 1}; }
 
 bool plan_score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_n, int64_t scratch_bytes, int n_cu, NormPlan &p,
                      std::string &why) {
@@ -167,20 +167,20 @@ bool plan_score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int
         p.bytes_scratch = p.fixed_bytes + p.chunk * p.seg_bytes;
         p.shift_enrol = flat_grid(J * C);
         p.shift_test = flat_grid(p.chunk * C);
-        p.gemm_enrol = p.gemm_test = gemm_grid(J, p.chunk);
-        p.gemm_lds = 2 * NORM_KSTEP * (NORM_TILE + 4) * (int)sizeof(double);
+        p.gemm_enrol = p.gemm_test = dense_gemm_grid(J, p.chunk);
+        p.gemm_lds = dense_gemm_lds_bytes();
     }
     p.n_chunks = (T + p.chunk - 1) / p.chunk;
     if (enrol) {
-        p.select_enrol = NormGrid{J, 1};
+        p.select_enrol = Grid2{J, 1};
         p.select_lds_enrol = norm_select_lds_bytes(Cz);
     }
     if (test) {
-        p.select_test = NormGrid{p.chunk, 1};
+        p.select_test = Grid2{p.chunk, 1};
         p.select_lds_test = norm_select_lds_bytes(Ct);
     }
-    if (norm_needs_zt(mode)) p.select_zt = NormGrid{Ct, 1};
-    p.apply = NormGrid{J, (p.chunk + NORM_WG - 1) / NORM_WG};
+    if (norm_needs_zt(mode)) p.select_zt = Grid2{Ct, 1};
+    p.apply = Grid2{J, (p.chunk + NORM_WG - 1) / NORM_WG};
     p.bytes_counts = mode == NORM_AS2 ? 2 * 4 * p.apply.x * p.apply.y : 0;
     const int64_t widest = std::max(std::max(p.select_enrol.x, p.select_test.x), p.select_zt.x);
     p.select_rounds = (widest + n_cu - 1) / n_cu;

@@ -1,12 +1,15 @@
 // norm_plan.hpp -- what score normalisation (score_norm.hip: Z, T, ZT, S and the two adaptive S-norms of a score matrix S [J][T] against
 // impostor cohorts) decides before it touches the device: the refusals, the cut of the test segments into chunks whose adaptive
 // scratch fits the bound, the bytes of every array, the launch shapes -- as a pure function of the mode, the shapes, top_n, the
-// bound and the number of compute units.
+// bound and the number of compute units.  The grids and the LDS bytes of as2's four products are the dense layer's
+// (dense64_plan.hpp).
 // Host-only C++17, nothing of HIP: score_norm.hip consumes it, sr_score_norm_plan hands it to tests, tests/host/norm_checks.cpp runs
 // it under the host sanitizers.
 //   Ez [J][Cz]   the models against the Z-cohort          Tt [Ct][T]   the T-cohort models against the test segments
 //   Zt [Ct][Cz]  the T-cohort models against the Z-cohort (zt only)
 #pragma once
+
+#include "dense64_plan.hpp"
 
 #include <cstdint>
 #include <string>
@@ -20,14 +23,8 @@ constexpr int NORM_BINS = 256;                  // bins of the radix select's hi
 // state: 16384 x 8 B = 128 KiB + 1 KiB + 96 B of the 160 KiB a gfx950 compute unit has.
 constexpr int64_t NORM_MAX_C = 16384;
 constexpr int NORM_SELECT_FIXED_LDS = NORM_BINS * 4 + 96;       // histogram + wave totals of the scans and the sums
-constexpr int64_t NORM_MAX_ROWS = (int64_t)65535 * 64;        // models or test segments of one call (row tiles of 64: the GEMM's grid y)
-constexpr int NORM_TILE = 64;                   // the GEMM's output tile (jfa_plan.hpp: JFA_TILE)
-constexpr int NORM_KSTEP = 16;                  // its reduction step
+constexpr int64_t NORM_MAX_ROWS = (int64_t)65535 * DENSE_TILE;        // models or test segments of one call (row tiles: the GEMM's grid y)
 constexpr int64_t NORM_DEFAULT_SCRATCH = (int64_t)1 << 30;
-
-struct NormGrid {
-    int64_t x = 0, y = 0;
-};
 
 struct NormPlan {
     int mode = 0;
@@ -42,12 +39,12 @@ struct NormPlan {
     int64_t bytes_moments = 0;      // mu, sigma and the degenerate flag of every row and column a mode takes moments of
     int64_t bytes_tnorm = 0;        // zt: the z-normalised copy of Tt
     int64_t bytes_counts = 0;       // as2: two integer counts per workgroup of the apply kernel
-    NormGrid select_enrol, select_test, select_zt;      // x = workgroups = rows (select_test: of a full chunk)
+    Grid2 select_enrol, select_test, select_zt;      // x = workgroups = rows (select_test: of a full chunk)
     int select_lds_enrol = 0, select_lds_test = 0;
-    NormGrid shift_enrol, shift_test;                   // the elementwise shifted copies (as2)
-    NormGrid gemm_enrol, gemm_test;                     // Es SelT^T and SelE Ts of a full chunk (each launched twice)
+    Grid2 shift_enrol, shift_test;                   // the elementwise shifted copies (as2)
+    Grid2 gemm_enrol, gemm_test;                     // Es SelT^T and SelE Ts of a full chunk (each launched twice)
     int gemm_lds = 0;
-    NormGrid apply;                                     // x = models, y = blocks of 256 test segments (of a full chunk in as2)
+    Grid2 apply;                                     // x = models, y = blocks of 256 test segments (of a full chunk in as2)
     int64_t select_rounds = 0;      // rounds the largest selection launch makes over the chip at one workgroup a unit
 };
 

@@ -8,11 +8,13 @@
 //   -1/2 ln det(Phi_c + Sw) - 1/2 (x - yhat_j)^T P_c (x - yhat_j) + 1/2 ln det(Sb + Sw) + 1/2 x^T P_0 x,
 //   P_c = (Phi_c + Sw)^-1,  P_0 = (Sb + Sw)^-1,  the quadratic form taken apart as  a_t - 2 (Yhat P_c X^T)[j][t] + q_j.
 // The speakers (models) are sorted by count in the plan (plda_plan.cpp), so a count class is a contiguous row range; every product
-// goes through jfa.hip's GEMM kernel (launch_gemm: both operands addressed by strides, so no transposed copies).  The kernels here:
+// goes through the dense layer's GEMM (dense64.hpp: both operands addressed by strides, so no transposed copies; the sums over rows
+// and over speakers are accumulating launches of PLDA_SUM_CHUNK rows, whole reduction tiles).  The kernels here:
 //   plda_centre_kernel       out[r] = X[src[r]] - coef[r] M[midx[r]]: centring, the gather into sorted order, the class means of WCCN.
 //   plda_class_sums_kernel   F[s] = the sum of the sorted speaker's rows, in row order: a segmented sum, a lane per (speaker, column).
 //   plda_combine_kernel      out[b] = A[b] + coef[b] B over a batch of R x R blocks (Sb^-1 + c Sw^-1; Phi_c + Sw; a covariance / n).
-//   plda_invert_kernel       one workgroup per R x R SPD block: jfa_cholesky and the log-determinant off the factor's diagonal.  For
+//   plda_invert_kernel       one workgroup per R x R SPD block: dense_cholesky (dense64_dev.hpp) and the log-determinant off the factor's
+//                            diagonal.  For
 //                            R <= jfa_lds_rows the block is in LDS and the same workgroup goes on to the factor's inverse
 //                            (whitening) and the inverse over the block (mirrored: symmetric to the bit).  Above, the block is
 //                            factored in place in global memory, and
@@ -26,8 +28,11 @@
 // factored, with the iteration and a stop code; scoring writes exact zeros into the class's rows and counts the class.
 // Deterministic: no atomics; every sum has a fixed order; a score depends on its model's count and sum and on its segment only, so
 // neither the batch nor the chunking of the segments under "plda_scratch_mib" shows, bit for bit.
+// The launchers and host helpers named plda_* are declared in eig_dev.hpp: backend_eig.hip calls the same ones.
+#include "dense64.hpp"
+#include "dense64_dev.hpp"
 #include "eig_dev.hpp"
-#include "jfa_dev.hpp"
+#include "jfa.hpp"              // the option jfa_lds_rows, nothing else of JFA's
 #include "plda_plan.hpp"
 
 #include <algorithm>
@@ -38,7 +43,7 @@
 
 namespace sr {
 
-static_assert(PLDA_WG == JFA_WG, "the factorisation is written for JFA_WG lanes");
+static_assert(PLDA_WG == DENSE_WG, "the factorisation is written for DENSE_WG lanes");
 // Rows of at least this many scores (64 KiB) go from the device straight to their model's place in the result; shorter rows come
 // back in one copy and are put in place on the host (a copy per row of 16 KB measured slower than that: 19 against 16 ms at 200 x 2000).
 constexpr int64_t PLDA_ROW_COPY_MIN = 8192;
@@ -87,8 +92,8 @@ static __device__ inline double plda_wave_sum(double v) {
 __global__ __launch_bounds__(PLDA_WG)
 void plda_invert_kernel(double *__restrict__ blocks, int R, int use_lds, int mode, double *__restrict__ logdet, int *__restrict__ flags) {
     extern __shared__ double plda_lds[];
-    double *pan = plda_lds;                    // [R][JFA_PS]
-    double *buf = pan + (size_t)R * JFA_PS;    // [R]
+    double *pan = plda_lds;                    // [R][DENSE_PS]
+    double *buf = pan + (size_t)R * DENSE_PS;    // [R]
     double *mat = buf + R;                     // [R][R], LDS path only
     const int tid = threadIdx.x;
     const int64_t g = blockIdx.x;
@@ -100,7 +105,7 @@ void plda_invert_kernel(double *__restrict__ blocks, int R, int use_lds, int mod
         M = mat;
         __syncthreads();
     }
-    const bool ok = jfa_cholesky(M, R, pan);
+    const bool ok = dense_cholesky(M, R, pan);
     __syncthreads();
     if (!ok) {
         for (int e = tid; e < rr; e += PLDA_WG) Mg[e] = 0.0;
@@ -113,9 +118,9 @@ void plda_invert_kernel(double *__restrict__ blocks, int R, int use_lds, int mod
         logdet[g] = 2.0 * s;
         flags[g] = 0;
     }
-    if (mode != 2) jfa_tri_inverse(M, R, buf);
+    if (mode != 2) dense_tri_inverse(M, R, buf);
     if (mode == 0) {
-        jfa_inverse_from_tri(M, R, buf, nullptr);
+        dense_inverse_from_tri(M, R, buf, nullptr);
     } else {
         for (int e = tid; e < rr; e += PLDA_WG)
             if (e % R > e / R) M[e] = 0.0;
@@ -257,20 +262,20 @@ struct PldaScratch {
 
 static unsigned flat_blocks(int64_t n) { return (unsigned)((n + PLDA_WG - 1) / PLDA_WG); }
 
-static void launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,
+void plda_launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,
                           int64_t rows, int R) {
     ScopedKernelTimer tm(T_JFA_GRAM);
     hipLaunchKernelGGL(plda_centre_kernel, dim3(flat_blocks(rows * R)), dim3(PLDA_WG), 0, st, X, src, M, midx, coef, out, rows, R);
     SR_HIP(hipGetLastError());
 }
 
-static void launch_class_sums(hipStream_t st, const double *Xs, const int64_t *row_start, double *F, int64_t S, int R) {
+void plda_launch_class_sums(hipStream_t st, const double *Xs, const int64_t *row_start, double *F, int64_t S, int R) {
     ScopedKernelTimer tm(T_JFA_GRAM);
     hipLaunchKernelGGL(plda_class_sums_kernel, dim3((unsigned)S, (unsigned)((R + PLDA_WG - 1) / PLDA_WG)), dim3(PLDA_WG), 0, st, Xs, row_start, F, R);
     SR_HIP(hipGetLastError());
 }
 
-static void launch_combine(hipStream_t st, const double *A, int64_t stride_a, const double *B, const double *coef, double *out, int64_t nb, int R) {
+void plda_launch_combine(hipStream_t st, const double *A, int64_t stride_a, const double *B, const double *coef, double *out, int64_t nb, int R) {
     ScopedKernelTimer tm(T_JFA_GRAM);
     const int64_t rr = (int64_t)R * R;
     hipLaunchKernelGGL(plda_combine_kernel, dim3(flat_blocks(nb * rr)), dim3(PLDA_WG), 0, st, A, stride_a, B, coef, out, nb, rr);
@@ -278,8 +283,8 @@ static void launch_combine(hipStream_t st, const double *A, int64_t stride_a, co
 }
 
 // Inverts n blocks in place; the flags and the log-determinants come back to the host (synchronises).  Returns the blocks that failed.
-static int64_t invert_blocks(hipStream_t st, PldaScratch &w, const PldaPlan &pl, double *blocks, int64_t n, int mode, std::vector<int> &flags,
-                             std::vector<double> &logdet) {
+int64_t plda_invert_blocks(hipStream_t st, const PldaPlan &pl, double *blocks, int64_t n, int mode, std::vector<int> &flags, std::vector<double> &logdet) {
+    auto &w = per_device<PldaScratch>();
     static int attr_set[MAX_DEVICES] = {};
     if (attr_set[ctx().device] < pl.factor_lds) {
         SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&plda_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, pl.factor_lds));
@@ -306,7 +311,7 @@ static int64_t invert_blocks(hipStream_t st, PldaScratch &w, const PldaPlan &pl,
             SR_HIP(hipGetLastError());
         }
         if (mode == 0)
-            for (int64_t g = 0; g < n; g++) launch_gemm(T_JFA_FACTOR, st, w.tri.p + g * rr, 1, R, w.tri.p + g * rr, R, 1, blocks + g * rr, R, R, R, R, false, 0);
+            for (int64_t g = 0; g < n; g++) dense_gemm(T_JFA_FACTOR, st, w.tri.p + g * rr, 1, R, w.tri.p + g * rr, R, 1, blocks + g * rr, R, R, R, R, false, 0);
         else
             SR_HIP(hipMemcpyAsync(blocks, w.tri.p, (size_t)(n * rr) * 8, hipMemcpyDeviceToDevice, st));
     }
@@ -320,7 +325,7 @@ static int64_t invert_blocks(hipStream_t st, PldaScratch &w, const PldaPlan &pl,
     return bad;
 }
 
-static void launch_rowdot(hipStream_t st, const double *A, const double *B, double *out, int64_t rows, int R) {
+void plda_launch_rowdot(hipStream_t st, const double *A, const double *B, double *out, int64_t rows, int R) {
     ScopedKernelTimer tm(T_JFA_GRAM);
     hipLaunchKernelGGL(plda_rowdot_kernel, dim3((unsigned)((rows + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG)), dim3(PLDA_WG), 0, st, A, B, out, rows, R);
     SR_HIP(hipGetLastError());
@@ -335,15 +340,15 @@ static void launch_assemble(hipStream_t st, int mode, double *out, int64_t ld, i
 }
 
 // C [R][R] (+)= A^T B over the rows r0 .. of A, B [rows][R], `chunk` rows a launch, in order.
-static void accumulate_gram(hipStream_t st, const double *A, const double *B, double *C, int64_t rows, int64_t chunk, int R) {
+void plda_accumulate_gram(hipStream_t st, const double *A, const double *B, double *C, int64_t rows, int64_t chunk, int R) {
     for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
         const int64_t n = std::min(chunk, rows - r0);
-        launch_gemm(T_JFA_GEMM_A, st, A + r0 * R, 1, R, B + r0 * R, R, 1, C, R, R, R, n, r0 > 0, 0);
+        dense_gemm(T_JFA_GEMM_A, st, A + r0 * R, 1, R, B + r0 * R, R, 1, C, R, R, R, n, r0 > 0, 0);
     }
 }
 
 // The mean of the rows, column by column in row order.
-static std::vector<double> row_mean(const double *X, int64_t n, int R) {
+std::vector<double> plda_row_mean(const double *X, int64_t n, int R) {
     std::vector<double> mu((size_t)R, 0.0);
     for (int64_t i = 0; i < n; i++)
         for (int k = 0; k < R; k++) mu[(size_t)k] += X[i * R + k];
@@ -352,7 +357,7 @@ static std::vector<double> row_mean(const double *X, int64_t n, int R) {
 }
 
 // The lower triangle mirrored: what the device reads of a covariance that is symmetric but for rounding.
-static std::vector<double> mirrored(const double *M, int R) {
+std::vector<double> plda_mirrored(const double *M, int R) {
     std::vector<double> out((size_t)R * R);
     for (int i = 0; i < R; i++)
         for (int j = 0; j <= i; j++) out[(size_t)i * R + j] = out[(size_t)j * R + i] = M[(int64_t)i * R + j];
@@ -365,12 +370,13 @@ void plda_launch_rownorm(hipStream_t st, double *Y, int64_t rows, int R, int *fl
     SR_HIP(hipGetLastError());
 }
 
-static void check_device(const char *what) {
+void plda_check_device(const char *what) {
     if (gpu_runtime_lost()) fail_gpu_runtime_lost(what);
     ensure_device();
 }
 
-static void check_matrix(const double *X, int64_t n, int R, const char *name, const char *rows_name, std::string &why) {
+void plda_check_matrix(const double *X, int64_t n, int R, const char *name, const char *rows_name) {
+    std::string why;
     if (!plda_check_rank(R, why) || !plda_check_rows(n, rows_name, why)) fail("%s", why.c_str());
     if (!X) fail("PLDA back end: null argument (%s)", name);
     if (!plda_check_finite(X, n * R, name, why)) fail("%s", why.c_str());
@@ -380,64 +386,37 @@ static void check_matrix(const double *X, int64_t n, int R, const char *name, co
 static std::vector<double> centre_and_sum(hipStream_t st, PldaScratch &w, const PldaPlan &pl, const double *X, bool sums) {
     const int64_t n = pl.rows, S = pl.groups;
     const int R = pl.R;
-    std::vector<double> mu = row_mean(X, n, R);
+    std::vector<double> mu = plda_row_mean(X, n, R);
     w.X.upload(X, (size_t)(n * R));
     w.mu.upload(mu.data(), (size_t)R);
     w.order.upload(pl.row_order.data(), (size_t)n);
     w.start.upload(pl.row_start.data(), (size_t)S + 1);
     w.Xc.ensure((size_t)(n * R));
     w.F.ensure((size_t)(S * R));
-    launch_centre(st, w.X.p, w.order.p, w.mu.p, nullptr, nullptr, w.Xc.p, n, R);
-    if (sums) launch_class_sums(st, w.Xc.p, w.start.p, w.F.p, S, R);
+    plda_launch_centre(st, w.X.p, w.order.p, w.mu.p, nullptr, nullptr, w.Xc.p, n, R);
+    if (sums) plda_launch_class_sums(st, w.Xc.p, w.start.p, w.F.p, S, R);
     sync_stream();                             // (mu and the plan's tables are host memory of this frame)
     return mu;
-}
-
-// ---- the same launchers for backend_eig.hip (eig_dev.hpp) ----
-
-void plda_launch_centre(hipStream_t st, const double *X, const int64_t *src, const double *M, const int64_t *midx, const double *coef, double *out,
-                        int64_t rows, int R) {
-    launch_centre(st, X, src, M, midx, coef, out, rows, R);
-}
-void plda_launch_class_sums(hipStream_t st, const double *Xs, const int64_t *row_start, double *F, int64_t S, int R) {
-    launch_class_sums(st, Xs, row_start, F, S, R);
-}
-void plda_launch_combine(hipStream_t st, const double *A, int64_t stride_a, const double *B, const double *coef, double *out, int64_t nb, int R) {
-    launch_combine(st, A, stride_a, B, coef, out, nb, R);
-}
-void plda_launch_rowdot(hipStream_t st, const double *A, const double *B, double *out, int64_t rows, int R) { launch_rowdot(st, A, B, out, rows, R); }
-void plda_accumulate_gram(hipStream_t st, const double *A, const double *B, double *C, int64_t rows, int64_t chunk, int R) {
-    accumulate_gram(st, A, B, C, rows, chunk, R);
-}
-int64_t plda_invert_blocks(hipStream_t st, const PldaPlan &pl, double *blocks, int64_t n, int mode, std::vector<int> &flags, std::vector<double> &logdet) {
-    return invert_blocks(st, per_device<PldaScratch>(), pl, blocks, n, mode, flags, logdet);
-}
-std::vector<double> plda_row_mean(const double *X, int64_t n, int R) { return row_mean(X, n, R); }
-std::vector<double> plda_mirrored(const double *M, int R) { return mirrored(M, R); }
-void plda_check_device(const char *what) { check_device(what); }
-void plda_check_matrix(const double *X, int64_t n, int R, const char *name, const char *rows_name) {
-    std::string why;
-    check_matrix(X, n, R, name, rows_name, why);
 }
 
 void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S, int n_iter, int default_start, double *mu_out, double *Sb,
                 double *Sw, int *iterations, int *n_classes, int *stop) {
     std::string why;
-    check_matrix(X, n, R, "X, the training vectors [n][R]", "n, the number of training vectors", why);
+    plda_check_matrix(X, n, R, "X, the training vectors [n][R]", "n, the number of training vectors");
     if (!Sb || !Sw) fail("PLDA training: null argument (Sb and Sw [R][R], the start and the result)");
     if (n_iter < 1) fail("PLDA training: n_iter is %d; run at least one iteration (n_iter >= 1)", n_iter);
     if (default_start != 0 && default_start != 1) fail("PLDA training: default_start is 0 (Sb and Sw hold the start) or 1 (both start from half the total covariance)");
     if (!default_start && (!plda_check_symmetric(Sb, R, "Sb", why) || !plda_check_symmetric(Sw, R, "Sw", why))) fail("%s", why.c_str());
     PldaPlan pl;
     if (!plan_plda_train(n, R, ids, S, (int)jfa_lds_rows(), 1, pl, why)) fail("%s", why.c_str());
-    check_device("sr_plda_train");
+    plda_check_device("sr_plda_train");
     if (!plan_plda_train(n, R, ids, S, (int)jfa_lds_rows(), std::max(1, ctx().n_cu), pl, why)) fail("%s", why.c_str());
     hipStream_t st = ctx().stream;
     auto &w = per_device<PldaScratch>();
     const int64_t rr = (int64_t)R * R, nc = (int64_t)pl.classes.size();
     const std::vector<double> mu = centre_and_sum(st, w, pl, X, true);
     w.T2.ensure((size_t)rr), w.FY.ensure((size_t)rr), w.YY.ensure((size_t)rr), w.YnY.ensure((size_t)rr);
-    accumulate_gram(st, w.Xc.p, w.Xc.p, w.T2.p, n, pl.sum_chunk, R);
+    plda_accumulate_gram(st, w.Xc.p, w.Xc.p, w.T2.p, n, pl.sum_chunk, R);
     // the tables: a speaker's count (sorted order), the classes' counts and sizes
     std::vector<double> wn((size_t)S), csize((size_t)nc), ccount((size_t)nc);
     for (int64_t c = 0; c < nc; c++) {
@@ -456,9 +435,9 @@ void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S
     w.bad.ensure(1);
     if (default_start) {                       // Sb = Sw = T2 / (2 n): half the total covariance each (T2 is symmetric to the bit)
         w.coef.upload(half, 2);
-        launch_combine(st, nullptr, 0, w.T2.p, w.coef.p, w.pairs.p, 2, R);
+        plda_launch_combine(st, nullptr, 0, w.T2.p, w.coef.p, w.pairs.p, 2, R);
     } else {
-        start = mirrored(Sb, R), start_w = mirrored(Sw, R);
+        start = plda_mirrored(Sb, R), start_w = plda_mirrored(Sw, R);
         SR_HIP(hipMemcpyAsync(w.pairs.p, start.data(), (size_t)rr * 8, hipMemcpyHostToDevice, st));
         SR_HIP(hipMemcpyAsync(w.pairs.p + rr, start_w.data(), (size_t)rr * 8, hipMemcpyHostToDevice, st));
     }
@@ -468,30 +447,30 @@ void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S
     for (int it = 0; it < n_iter; it++) {
         double *pair = w.pairs.p + (int64_t)cur * 2 * rr;
         SR_HIP(hipMemcpyAsync(w.work.p, pair, (size_t)(2 * rr) * 8, hipMemcpyDeviceToDevice, st));
-        if (invert_blocks(st, w, pl, w.work.p, 2, 0, flags, logdet)) {
+        if (plda_invert_blocks(st, pl, w.work.p, 2, 0, flags, logdet)) {
             code = flags[0] ? PLDA_STOP_SB : PLDA_STOP_SW;
             break;
         }
         const double *iSb = w.work.p, *iSw = w.work.p + rr;
-        launch_combine(st, iSb, 0, iSw, w.cls_count.p, w.phi.p, nc, R);               // Sb^-1 + c Sw^-1
-        if (invert_blocks(st, w, pl, w.phi.p, nc, 0, flags, logdet)) {
+        plda_launch_combine(st, iSb, 0, iSw, w.cls_count.p, w.phi.p, nc, R);               // Sb^-1 + c Sw^-1
+        if (plda_invert_blocks(st, pl, w.phi.p, nc, 0, flags, logdet)) {
             code = PLDA_STOP_PHI;
             break;
         }
         good = cur;
-        launch_gemm(T_JFA_GEMM_B, st, w.F.p, R, 1, iSw, R, 1, w.G.p, R, S, R, R, false, 0);                                   // G = F Sw^-1
+        dense_gemm(T_JFA_GEMM_B, st, w.F.p, R, 1, iSw, R, 1, w.G.p, R, S, R, R, false, 0);                                   // G = F Sw^-1
         for (int64_t c = 0; c < nc; c++) {
             const PldaClass &k = pl.classes[(size_t)c];
-            launch_gemm(T_JFA_GEMM_L, st, w.G.p + k.start * R, R, 1, w.phi.p + c * rr, R, 1, w.Y.p + k.start * R, R, k.size, R, R, false, 0);      // Yhat_c = G_c Phi_c
+            dense_gemm(T_JFA_GEMM_L, st, w.G.p + k.start * R, R, 1, w.phi.p + c * rr, R, 1, w.Y.p + k.start * R, R, k.size, R, R, false, 0);      // Yhat_c = G_c Phi_c
         }
         {
             ScopedKernelTimer tm(T_JFA_GRAM);
             hipLaunchKernelGGL(plda_scale_rows_kernel, dim3(flat_blocks(S * R)), dim3(PLDA_WG), 0, st, w.Y.p, w.w.p, w.Yn.p, S, R);
             SR_HIP(hipGetLastError());
         }
-        accumulate_gram(st, w.Y.p, w.Y.p, w.YY.p, S, pl.grp_chunk, R);
-        accumulate_gram(st, w.F.p, w.Y.p, w.FY.p, S, pl.grp_chunk, R);
-        accumulate_gram(st, w.Y.p, w.Yn.p, w.YnY.p, S, pl.grp_chunk, R);
+        plda_accumulate_gram(st, w.Y.p, w.Y.p, w.YY.p, S, pl.grp_chunk, R);
+        plda_accumulate_gram(st, w.F.p, w.Y.p, w.FY.p, S, pl.grp_chunk, R);
+        plda_accumulate_gram(st, w.Y.p, w.Yn.p, w.YnY.p, S, pl.grp_chunk, R);
         int next = 0;
         while (next == good || next == cur) next++;
         double *np = w.pairs.p + (int64_t)next * 2 * rr;
@@ -526,15 +505,15 @@ void plda_train(int64_t n, int R, const double *X, const int64_t *ids, int64_t S
 void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb, const double *Sw, const double *E, const int64_t *enrol_n,
                 const double *X, double *out, int64_t *bad_classes) {
     std::string why;
-    check_matrix(E, J, R, "E, the models' enrolment sums [J][R]", "J, the number of models", why);
-    check_matrix(X, T, R, "X, the test vectors [T][R]", "T, the number of test segments", why);
+    plda_check_matrix(E, J, R, "E, the models' enrolment sums [J][R]", "J, the number of models");
+    plda_check_matrix(X, T, R, "X, the test vectors [T][R]", "T, the number of test segments");
     if (!mu || !Sb || !Sw || !out) fail("PLDA scoring: null argument (mu [R], Sb and Sw [R][R] and out [J][T] are all required)");
     if (!plda_check_finite(mu, R, "mu", why) || !plda_check_symmetric(Sb, R, "Sb", why) || !plda_check_symmetric(Sw, R, "Sw", why))
         fail("%s", why.c_str());
     PldaPlan pl;
     const int64_t bound = (int64_t)plda_scratch_mib() << 20;
     if (!plan_plda_score(J, T, R, enrol_n, bound, (int)jfa_lds_rows(), 1, pl, why)) fail("%s", why.c_str());
-    check_device("sr_plda_score");
+    plda_check_device("sr_plda_score");
     if (!plan_plda_score(J, T, R, enrol_n, bound, (int)jfa_lds_rows(), std::max(1, ctx().n_cu), pl, why)) fail("%s", why.c_str());
     hipStream_t st = ctx().stream;
     auto &w = per_device<PldaScratch>();
@@ -549,7 +528,7 @@ void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb,
         cnt[(size_t)s] = (double)enrol_n[j];
     }
     for (int64_t c = 0; c < nc; c++) ccount[(size_t)c] = (double)pl.classes[(size_t)c].count;
-    const std::vector<double> sb = mirrored(Sb, R), sw = mirrored(Sw, R);
+    const std::vector<double> sb = plda_mirrored(Sb, R), sw = plda_mirrored(Sw, R);
     w.X.upload(Es.data(), (size_t)(J * R));
     w.mu.upload(mu, (size_t)R);
     w.coef.upload(cnt.data(), (size_t)J);
@@ -567,14 +546,14 @@ void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb,
     std::vector<int> flags, phi_flags;
     std::vector<double> logdet;
     std::vector<char> ok((size_t)nc, 1);
-    bool all_bad = invert_blocks(st, w, pl, w.work.p, 2, 0, flags, logdet) != 0;
+    bool all_bad = plda_invert_blocks(st, pl, w.work.p, 2, 0, flags, logdet) != 0;
     double ld_0 = 0.0;
     if (!all_bad) {
-        launch_combine(st, iSb, 0, iSw, w.cls_count.p, w.phi.p, nc, R);                // Sb^-1 + c Sw^-1
-        invert_blocks(st, w, pl, w.phi.p, nc, 0, phi_flags, logdet);
-        launch_combine(st, w.phi.p, rr, dSw, w.cls_size.p, w.pc.p, nc, R);             // Phi_c + Sw
-        launch_combine(st, dSb, 0, dSw, w.cls_size.p, w.pc.p + nc * rr, 1, R);         // Sb + Sw
-        invert_blocks(st, w, pl, w.pc.p, nc + 1, 0, flags, logdet);
+        plda_launch_combine(st, iSb, 0, iSw, w.cls_count.p, w.phi.p, nc, R);                // Sb^-1 + c Sw^-1
+        plda_invert_blocks(st, pl, w.phi.p, nc, 0, phi_flags, logdet);
+        plda_launch_combine(st, w.phi.p, rr, dSw, w.cls_size.p, w.pc.p, nc, R);             // Phi_c + Sw
+        plda_launch_combine(st, dSb, 0, dSw, w.cls_size.p, w.pc.p + nc * rr, 1, R);         // Sb + Sw
+        plda_invert_blocks(st, pl, w.pc.p, nc + 1, 0, flags, logdet);
         all_bad = flags[(size_t)nc] != 0;
         ld_0 = logdet[(size_t)nc];
         for (int64_t c = 0; c < nc; c++) ok[(size_t)c] = !phi_flags[(size_t)c] && !flags[(size_t)c];
@@ -583,30 +562,30 @@ void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb,
     int64_t bad = 0;
     for (char o : ok) bad += !o;
     if (!all_bad) {
-        launch_centre(st, w.X.p, nullptr, w.mu.p, nullptr, w.coef.p, w.F.p, J, R);      // f_j = e_j - n_j mu
-        launch_gemm(T_JFA_GEMM_B, st, w.F.p, R, 1, iSw, R, 1, w.G.p, R, J, R, R, false, 0);                                  // G = F Sw^-1
+        plda_launch_centre(st, w.X.p, nullptr, w.mu.p, nullptr, w.coef.p, w.F.p, J, R);      // f_j = e_j - n_j mu
+        dense_gemm(T_JFA_GEMM_B, st, w.F.p, R, 1, iSw, R, 1, w.G.p, R, J, R, R, false, 0);                                  // G = F Sw^-1
         for (int64_t c = 0; c < nc; c++) {
             const PldaClass &k = pl.classes[(size_t)c];
             if (!ok[(size_t)c]) continue;
-            launch_gemm(T_JFA_GEMM_L, st, w.G.p + k.start * R, R, 1, w.phi.p + c * rr, R, 1, w.Y.p + k.start * R, R, k.size, R, R, false, 0);      // Yhat_c = G_c Phi_c
-            launch_gemm(T_JFA_GEMM_L, st, w.Y.p + k.start * R, R, 1, w.pc.p + c * rr, R, 1, w.M.p + k.start * R, R, k.size, R, R, false, 0);      // M = Yhat_c P_c
-            launch_rowdot(st, w.M.p + k.start * R, w.Y.p + k.start * R, w.q.p + k.start, k.size, R);
+            dense_gemm(T_JFA_GEMM_L, st, w.G.p + k.start * R, R, 1, w.phi.p + c * rr, R, 1, w.Y.p + k.start * R, R, k.size, R, R, false, 0);      // Yhat_c = G_c Phi_c
+            dense_gemm(T_JFA_GEMM_L, st, w.Y.p + k.start * R, R, 1, w.pc.p + c * rr, R, 1, w.M.p + k.start * R, R, k.size, R, R, false, 0);      // M = Yhat_c P_c
+            plda_launch_rowdot(st, w.M.p + k.start * R, w.Y.p + k.start * R, w.q.p + k.start, k.size, R);
         }
     }
     for (int64_t ci = 0; ci < pl.n_chunks; ci++) {
         const int64_t t0 = ci * chunk, nt = std::min(chunk, T - t0);
         if (!all_bad) {
             w.Z.upload(X + t0 * R, (size_t)(nt * R));
-            launch_centre(st, w.Z.p, nullptr, w.mu.p, nullptr, nullptr, w.Xc.p, nt, R);
-            launch_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.pc.p + nc * rr, R, 1, w.Z.p, R, nt, R, R, false, 0);              // Z = X P_0
-            launch_rowdot(st, w.Z.p, w.Xc.p, w.a0.p, nt, R);
+            plda_launch_centre(st, w.Z.p, nullptr, w.mu.p, nullptr, nullptr, w.Xc.p, nt, R);
+            dense_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.pc.p + nc * rr, R, 1, w.Z.p, R, nt, R, R, false, 0);              // Z = X P_0
+            plda_launch_rowdot(st, w.Z.p, w.Xc.p, w.a0.p, nt, R);
         }
         for (int64_t c = 0; c < nc; c++) {
             const PldaClass &k = pl.classes[(size_t)c];
             if (ok[(size_t)c]) {
-                launch_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.pc.p + c * rr, R, 1, w.Z.p, R, nt, R, R, false, 0);           // Z = X P_c
-                launch_rowdot(st, w.Z.p, w.Xc.p, w.a.p, nt, R);
-                launch_gemm(T_JFA_GEMM_C, st, w.M.p + k.start * R, R, 1, w.Xc.p, 1, R, w.out.p + k.start * T + t0, T, k.size, nt, R, false, 0);      // M X^T
+                dense_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.pc.p + c * rr, R, 1, w.Z.p, R, nt, R, R, false, 0);           // Z = X P_c
+                plda_launch_rowdot(st, w.Z.p, w.Xc.p, w.a.p, nt, R);
+                dense_gemm(T_JFA_GEMM_C, st, w.M.p + k.start * R, R, 1, w.Xc.p, 1, R, w.out.p + k.start * T + t0, T, k.size, nt, R, false, 0);      // M X^T
             }
             launch_assemble(st, 0, w.out.p, T, k.start, t0, k.size, nt, w.q.p, w.a.p, w.a0.p, ok[(size_t)c] ? logdet[(size_t)c] : 0.0, ld_0,
                             ok[(size_t)c] != 0);
@@ -632,7 +611,7 @@ void plda_score(int64_t J, int64_t T, int R, const double *mu, const double *Sb,
 void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids, int64_t S, double *mu_out, double *A) {
     std::string why;
     if (kind != PLDA_WHITEN && kind != PLDA_WCCN) fail("PLDA back end: the kind is 0 (whiten) or 1 (wccn)");
-    check_matrix(X, n, R, "X, the training vectors [n][R]", "n, the number of training vectors", why);
+    plda_check_matrix(X, n, R, "X, the training vectors [n][R]", "n, the number of training vectors");
     if (!mu_out || !A) fail("PLDA back end: null argument (mu [R] and A [R][R], the results)");
     // whitening has one class: everything
     std::vector<int64_t> zeros;
@@ -643,7 +622,7 @@ void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids
     }
     PldaPlan pl;
     if (!plan_plda_train(n, R, ids, S, (int)jfa_lds_rows(), 1, pl, why)) fail("%s", why.c_str());
-    check_device("sr_backend_fit");
+    plda_check_device("sr_backend_fit");
     if (!plan_plda_train(n, R, ids, S, (int)jfa_lds_rows(), std::max(1, ctx().n_cu), pl, why)) fail("%s", why.c_str());
     hipStream_t st = ctx().stream;
     auto &w = per_device<PldaScratch>();
@@ -660,17 +639,17 @@ void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids
         w.midx.upload(midx.data(), (size_t)n);
         w.coef.upload(coef.data(), (size_t)n);
         w.Xw.ensure((size_t)(n * R));
-        launch_centre(st, w.Xc.p, nullptr, w.F.p, w.midx.p, w.coef.p, w.Xw.p, n, R);
+        plda_launch_centre(st, w.Xc.p, nullptr, w.F.p, w.midx.p, w.coef.p, w.Xw.p, n, R);
         rows = w.Xw.p;
     }
     w.T2.ensure((size_t)rr), w.work.ensure((size_t)rr);
-    accumulate_gram(st, rows, rows, w.T2.p, n, pl.sum_chunk, R);
+    plda_accumulate_gram(st, rows, rows, w.T2.p, n, pl.sum_chunk, R);
     const double inv_n = 1.0 / (double)n;
     w.cls_size.upload(&inv_n, 1);
-    launch_combine(st, nullptr, 0, w.T2.p, w.cls_size.p, w.work.p, 1, R);               // the covariance
+    plda_launch_combine(st, nullptr, 0, w.T2.p, w.cls_size.p, w.work.p, 1, R);               // the covariance
     std::vector<int> flags;
     std::vector<double> logdet;
-    if (invert_blocks(st, w, pl, w.work.p, 1, 1, flags, logdet))
+    if (plda_invert_blocks(st, pl, w.work.p, 1, 1, flags, logdet))
         fail("PLDA back end: the %s covariance of these %lld vectors of %d dimensions does not factor (dependent columns, or too few vectors); "
              "pass more vectors or reduce the dimension", kind == PLDA_WCCN ? "within-class" : "total", (long long)n, R);
     w.work.download(A, (size_t)rr);
@@ -680,18 +659,18 @@ void backend_fit(int kind, int64_t n, int R, const double *X, const int64_t *ids
 
 void backend_apply(int64_t n, int R, const double *X, const double *mu, const double *A, int length_norm, double *Y, int64_t *zero_rows) {
     std::string why;
-    check_matrix(X, n, R, "X, the vectors [n][R]", "n, the number of vectors", why);
+    plda_check_matrix(X, n, R, "X, the vectors [n][R]", "n, the number of vectors");
     if (!mu || !A || !Y) fail("PLDA back end: null argument (mu [R], A [R][R] and Y [n][R] are all required)");
     if (!plda_check_finite(mu, R, "mu", why) || !plda_check_finite(A, (int64_t)R * R, "A", why)) fail("%s", why.c_str());
-    check_device("sr_backend_apply");
+    plda_check_device("sr_backend_apply");
     hipStream_t st = ctx().stream;
     auto &w = per_device<PldaScratch>();
     w.X.upload(X, (size_t)(n * R));
     w.mu.upload(mu, (size_t)R);
     w.work.upload(A, (size_t)R * R);
     w.Xc.ensure((size_t)(n * R)), w.Y.ensure((size_t)(n * R));
-    launch_centre(st, w.X.p, nullptr, w.mu.p, nullptr, nullptr, w.Xc.p, n, R);
-    launch_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.work.p, 1, R, w.Y.p, R, n, R, R, false, 0);      // (X - mu) A^T
+    plda_launch_centre(st, w.X.p, nullptr, w.mu.p, nullptr, nullptr, w.Xc.p, n, R);
+    dense_gemm(T_JFA_GEMM_B, st, w.Xc.p, R, 1, w.work.p, 1, R, w.Y.p, R, n, R, R, false, 0);      // (X - mu) A^T
     int64_t zeros = 0;
     if (length_norm) {
         w.flags.ensure((size_t)n);
@@ -707,20 +686,19 @@ void backend_apply(int64_t n, int R, const double *X, const double *mu, const do
 }
 
 void cosine_score(int64_t J, int64_t T, int R, const double *E, const double *X, double *out) {
-    std::string why;
-    check_matrix(E, J, R, "E, the models' vectors [J][R]", "J, the number of models", why);
-    check_matrix(X, T, R, "X, the test vectors [T][R]", "T, the number of test segments", why);
+    plda_check_matrix(E, J, R, "E, the models' vectors [J][R]", "J, the number of models");
+    plda_check_matrix(X, T, R, "X, the test vectors [T][R]", "T, the number of test segments");
     if (!out) fail("cosine scoring: null argument (out, the score matrix [J][T])");
     if (J > (((int64_t)1 << 36) / T)) fail("cosine scoring: a score matrix of more than 2^36 values; split the trial list");
-    check_device("sr_cosine_score");
+    plda_check_device("sr_cosine_score");
     hipStream_t st = ctx().stream;
     auto &w = per_device<PldaScratch>();
     w.X.upload(E, (size_t)(J * R));
     w.Xc.upload(X, (size_t)(T * R));
     w.q.ensure((size_t)J), w.a.ensure((size_t)T), w.out.ensure((size_t)(J * T));
-    launch_rowdot(st, w.X.p, w.X.p, w.q.p, J, R);
-    launch_rowdot(st, w.Xc.p, w.Xc.p, w.a.p, T, R);
-    launch_gemm(T_JFA_GEMM_C, st, w.X.p, R, 1, w.Xc.p, 1, R, w.out.p, T, J, T, R, false, 0);       // E X^T
+    plda_launch_rowdot(st, w.X.p, w.X.p, w.q.p, J, R);
+    plda_launch_rowdot(st, w.Xc.p, w.Xc.p, w.a.p, T, R);
+    dense_gemm(T_JFA_GEMM_C, st, w.X.p, R, 1, w.Xc.p, 1, R, w.out.p, T, J, T, R, false, 0);       // E X^T
     launch_assemble(st, 1, w.out.p, T, 0, 0, J, T, w.q.p, w.a.p, nullptr, 0.0, 0.0, true);
     w.out.download(out, (size_t)(J * T));
     sync_stream();

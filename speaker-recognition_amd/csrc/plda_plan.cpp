@@ -1,4 +1,5 @@
-// plda_plan.cpp -- the decisions of the i-vector back end (plda_plan.hpp).  Host-only.
+// plda_plan.cpp -- the decisions of the i-vector back end (plda_plan.hpp); the GEMM's grids, the factorisation's path and their LDS
+// bytes are the dense layer's (dense64_plan.hpp).  Host-only.
 #include "plda_plan.hpp"
 
 #include <algorithm>
@@ -107,20 +108,11 @@ bool plda_check_enrol(const int64_t *enrol_n, int64_t J, std::string &why) {
     return true;
 }
 
-int plda_factor_lds_bytes(int R, int path) {
-    // the panel [R][JFA_NB + 1], one vector [R], and on the LDS path the block itself
-    return (int)(((int64_t)R * (JFA_NB + 1) + (int64_t)R + (path == 0 ? (int64_t)R * R : 0)) * (int64_t)sizeof(double));
-}
-
-static PldaGrid gemm_grid(int64_t M, int64_t N) { return PldaGrid{(N + JFA_TILE - 1) / JFA_TILE, (M + JFA_TILE - 1) / JFA_TILE}; }
-static PldaGrid flat_grid(int64_t n) { return PldaGrid{(n + PLDA_WG - 1) / PLDA_WG, 1}; }
+static Grid2 flat_grid(int64_t n) { return Grid2{(n + PLDA_WG - 1) / PLDA_WG, 1}; }
 
 static bool check_common(int R, int lds_rows, int n_cu, std::string &why) {
     if (!plda_check_rank(R, why)) return false;
-    if (lds_rows < 0 || lds_rows > JFA_LDS_MAX_R) {
-        why = fmt("jfa_lds_rows must be 0 (automatic) or 1 .. %lld", JFA_LDS_MAX_R);
-        return false;
-    }
+    if (!dense_check_lds_rows(lds_rows, why)) return false;
     if (n_cu < 1) {
         why = "PLDA back end: the plan needs the number of compute units";
         return false;
@@ -145,10 +137,10 @@ static int64_t sort_by_count(const std::vector<int64_t> &count, PldaPlan &p) {
 
 static void fill_paths(int R, int lds_rows, PldaPlan &p) {
     p.R = R;
-    p.lds_rows = jfa_lds_limit(lds_rows);
+    p.lds_rows = dense_lds_limit(lds_rows);
     p.path = R <= p.lds_rows ? 0 : 1;
-    p.factor_lds = plda_factor_lds_bytes(R, p.path);
-    p.gemm_lds = 2 * JFA_KSTEP * (JFA_TILE + 4) * (int)sizeof(double);
+    p.factor_lds = dense_factor_lds_bytes(R, p.path, 1);
+    p.gemm_lds = dense_gemm_lds_bytes();
 }
 
 bool plan_plda_train(int64_t n, int R, const int64_t *ids, int64_t S, int lds_rows, int n_cu, PldaPlan &p, std::string &why) {
@@ -178,11 +170,11 @@ bool plan_plda_train(int64_t n, int R, const int64_t *ids, int64_t S, int lds_ro
     p.bytes_blocks = (9 + nc) * rr * 8;
     p.bytes_rows = (2 * n + 4 * S) * R * 8;
     p.centre = flat_grid(n * R);
-    p.class_sums = PldaGrid{S, (R + PLDA_WG - 1) / PLDA_WG};
-    p.invert = PldaGrid{std::max<int64_t>(2, nc), 1};
-    p.gemm_rows = gemm_grid(std::max(widest, p.grp_chunk), R);
-    p.gemm_acc = gemm_grid(R, R);
-    if (p.path == 1) p.tri = PldaGrid{p.invert.x, (R + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG};
+    p.class_sums = Grid2{S, (R + PLDA_WG - 1) / PLDA_WG};
+    p.invert = Grid2{std::max<int64_t>(2, nc), 1};
+    p.gemm_rows = dense_gemm_grid(std::max(widest, p.grp_chunk), R);
+    p.gemm_acc = dense_gemm_grid(R, R);
+    if (p.path == 1) p.tri = Grid2{p.invert.x, (R + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG};
     p.invert_rounds = (p.invert.x + n_cu - 1) / n_cu;
     return true;
 }
@@ -215,12 +207,12 @@ bool plan_plda_score(int64_t J, int64_t T, int R, const int64_t *enrol_n, int64_
     p.bytes_blocks = (5 + 2 * nc) * rr * 8;
     p.bytes_rows = (4 * J * R + J * T + J) * 8;
     p.centre = flat_grid(std::max(J, p.chunk) * R);
-    p.invert = PldaGrid{std::max<int64_t>(2, nc + 1), 1};
-    p.gemm_rows = gemm_grid(std::max(widest, p.chunk), R);
-    p.rowdot = PldaGrid{(std::max(J, p.chunk) + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG, 1};
-    p.gemm_cross = gemm_grid(widest, p.chunk);
+    p.invert = Grid2{std::max<int64_t>(2, nc + 1), 1};
+    p.gemm_rows = dense_gemm_grid(std::max(widest, p.chunk), R);
+    p.rowdot = Grid2{(std::max(J, p.chunk) + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG, 1};
+    p.gemm_cross = dense_gemm_grid(widest, p.chunk);
     p.assemble = flat_grid(widest * p.chunk);
-    if (p.path == 1) p.tri = PldaGrid{p.invert.x, (R + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG};
+    if (p.path == 1) p.tri = Grid2{p.invert.x, (R + PLDA_ROWS_PER_WG - 1) / PLDA_ROWS_PER_WG};
     p.invert_rounds = (p.invert.x + n_cu - 1) / n_cu;
     return true;
 }

@@ -18,7 +18,7 @@
 //                                select and the compaction are skipped.
 //   norm_shift_kernel            as2's operands: X - (the full row's or column's mean) and its square, elementwise.
 //   norm_apply_kernel            elementwise over J x T: the normalisation from per-row / per-column moments, or (as2) from the four
-//                                products  Es SelT^T, (Es .* Es) SelT^T, SelE Ts, SelE (Ts .* Ts)  that jfa.hip's GEMM kernel forms
+//                                products  Es SelT^T, (Es .* Es) SelT^T, SelE Ts, SelE (Ts .* Ts)  that the dense layer's GEMM forms
 //                                (Sel*: 0/1 rows of the selection; Es = Ez - mu(Ez[j,:]), Ts = Tt - mu(Tt[:,t]): the shift keeps the
 //                                cancellation in q / N - (s / N)^2 down; a pair whose products cannot tell its variance from 0 -- a
 //                                selected set that is constant in a row that is not -- takes its moments from the values
@@ -28,7 +28,7 @@
 // Deterministic: no atomics on global memory, no float atomics anywhere (the histogram's are integer, in LDS).  A row's selection and
 // moments are the same bits alone, in any batch, from run to run; an as2 score depends on its model's row of Ez and its segment's
 // column of Tt only, so the chunking of the test segments under "norm_scratch_mib" does not show, bit for bit.
-#include "jfa_dev.hpp"
+#include "dense64.hpp"
 #include "norm_plan.hpp"
 #include "score_norm.hpp"
 
@@ -388,10 +388,10 @@ void score_norm(int mode, int64_t J, int64_t T, int64_t Cz, int64_t Ct, int top_
             // SelT [n][C]: the selections of the columns t0 .. (their own moments, as1's, are not used)
             launch_select(st, w.Tt.p + t0, 1, T, n, C, N, nullptr, w.SelT.p, w.mt.p, w.st.p, w.ft.p);
             launch_shift(st, w.Tt.p, T, t0, C, n, w.mc.p, false, w.Ts.p, w.Ts2.p);                                       // Ts [C][n]
-            launch_gemm(T_JFA_GEMM_A, st, w.Es.p, C, 1, w.SelT.p, 1, C, w.P1.p, n, J, n, C, false, 0);                 // Es SelT^T
-            launch_gemm(T_JFA_GEMM_A, st, w.Es2.p, C, 1, w.SelT.p, 1, C, w.P2.p, n, J, n, C, false, 0);                // (Es .* Es) SelT^T
-            launch_gemm(T_JFA_GEMM_B, st, w.SelE.p, C, 1, w.Ts.p, n, 1, w.P3.p, n, J, n, C, false, 0);                 // SelE Ts
-            launch_gemm(T_JFA_GEMM_B, st, w.SelE.p, C, 1, w.Ts2.p, n, 1, w.P4.p, n, J, n, C, false, 0);                // SelE (Ts .* Ts)
+            dense_gemm(T_JFA_GEMM_A, st, w.Es.p, C, 1, w.SelT.p, 1, C, w.P1.p, n, J, n, C, false, 0);                 // Es SelT^T
+            dense_gemm(T_JFA_GEMM_A, st, w.Es2.p, C, 1, w.SelT.p, 1, C, w.P2.p, n, J, n, C, false, 0);                // (Es .* Es) SelT^T
+            dense_gemm(T_JFA_GEMM_B, st, w.SelE.p, C, 1, w.Ts.p, n, 1, w.P3.p, n, J, n, C, false, 0);                 // SelE Ts
+            dense_gemm(T_JFA_GEMM_B, st, w.SelE.p, C, 1, w.Ts2.p, n, 1, w.P4.p, n, J, n, C, false, 0);                // SelE (Ts .* Ts)
             launch_apply(st, NORM_APPLY_PAIR, w.S.p, w.out.p, J, T, t0, n, w.mfull.p, nullptr, w.mc.p, nullptr, w.P1.p, w.P2.p, w.P3.p, w.P4.p, n,
                          N, NormPairSrc{w.Ez.p, w.Tt.p, w.SelT.p, w.SelE.p, T, (int)C}, w.counts.p);
             const int64_t nc = J * ((n + NORM_WG - 1) / NORM_WG) * 2;

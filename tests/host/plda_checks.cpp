@@ -85,7 +85,7 @@ int main() {
         const int64_t neg[4] = {0, -1, 1, 0};
         CHECK(train_refused(4, 3, neg, 2, 0, 256, "row 1 has label -1"));
         CHECK(train_refused(4, 3, ids, 2, -1, 256, "jfa_lds_rows must be 0"));
-        CHECK(train_refused(4, 3, ids, 2, JFA_LDS_MAX_R + 1, 256, "jfa_lds_rows must be 0"));
+        CHECK(train_refused(4, 3, ids, 2, DENSE_LDS_MAX_R + 1, 256, "jfa_lds_rows must be 0"));
         CHECK(train_refused(4, 3, ids, 2, 0, 0, "number of compute units"));
         CHECK(score_refused(0, 5, 3, en, GiB, 0, 256, "J, the number of models is 0"));
         CHECK(score_refused(3, 0, 3, en, GiB, 0, 256, "T, the number of test segments is 0"));
@@ -151,11 +151,11 @@ int main() {
                                 if (row >= 0 && row < n) seen[(size_t)row] = 1;
                             }
                         }
-                        const int limit = lds_rows == 0 ? JFA_LDS_MAX_R : lds_rows;
+                        const int limit = lds_rows == 0 ? DENSE_LDS_MAX_R : lds_rows;
                         CHECK(p.lds_rows == limit && p.path == (R <= limit ? 0 : 1));
                         CHECK(p.factor_lds == (R * 17 + R + (p.path == 0 ? R * R : 0)) * 8 && p.factor_lds <= 160 * 1024);
                         CHECK(p.tri.y == (p.path == 1 ? (R + 3) / 4 : 0) && p.tri.x == (p.path == 1 ? p.invert.x : 0));
-                        CHECK(p.sum_chunk == std::min(n, PLDA_SUM_CHUNK) && p.sum_chunk % JFA_KSTEP * (p.sum_chunks > 1) == 0);
+                        CHECK(p.sum_chunk == std::min(n, PLDA_SUM_CHUNK) && p.sum_chunk % DENSE_KSTEP * (p.sum_chunks > 1) == 0);
                         CHECK((p.sum_chunks - 1) * p.sum_chunk < n && n <= p.sum_chunks * p.sum_chunk);
                         CHECK((p.grp_chunks - 1) * p.grp_chunk < S && S <= p.grp_chunks * p.grp_chunk);
                         const int64_t nc = (int64_t)p.classes.size();
@@ -191,7 +191,7 @@ int main() {
                     CHECK(p.gemm_cross.x == (p.chunk + 63) / 64 && p.gemm_cross.y == (widest + 63) / 64 && p.gemm_cross.y <= 65535);
                     CHECK(p.assemble.x == (widest * p.chunk + 255) / 256 && p.assemble.x <= 0x7fffffffLL);
                     CHECK(p.invert.x == std::max<int64_t>(2, (int64_t)p.classes.size() + 1) && p.gemm_rows.y <= 65535);
-                    CHECK(p.rowdot.x == (std::max(J, p.chunk) + 3) / 4 && p.tri.y == (R > JFA_LDS_MAX_R ? (R + 3) / 4 : 0));
+                    CHECK(p.rowdot.x == (std::max(J, p.chunk) + 3) / 4 && p.tri.y == (R > DENSE_LDS_MAX_R ? (R + 3) / 4 : 0));
                 }
             }
     // ---- at the limits: the largest shapes the checks let through, every product in int64

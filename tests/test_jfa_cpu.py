@@ -268,9 +268,19 @@ def test_jfa_kernels_do_not_spill(built_lib):
     import test_abi_cpu
     res = test_abi_cpu._kernel_resources("jfa")
     names = " ".join(res)
-    for kernel in ("jfa_scale_kernel", "jfa_gram_kernel", "jfa_gemm_kernel", "jfa_factor_kernel"):
+    for kernel in ("jfa_scale_kernel", "jfa_gram_kernel", "jfa_factor_kernel"):
         assert kernel in names
-    assert len(res) == 4
+    assert len(res) == 3
+    for name, r in res.items():
+        assert r["scratch"] == 0, (name, r)
+
+
+def test_dense64_gemm_kernel_does_not_spill(built_lib):
+    """the float64 GEMM every JFA, PLDA, eigen back end and score normalisation product goes through: present, alone in its file, no scratch"""
+    import test_abi_cpu
+    res = test_abi_cpu._kernel_resources("dense64")
+    assert "dense_gemm_kernel" in " ".join(res)
+    assert len(res) == 1
     for name, r in res.items():
         assert r["scratch"] == 0, (name, r)
 
