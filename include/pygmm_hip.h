@@ -1039,6 +1039,67 @@ int sr_calib_counts(int64_t n, const double *llr /*[n]*/, const int8_t *lab /*[n
                     int64_t *fa /*[m]*/, int64_t *counts /*[3] or NULL*/);
 int sr_calib_plan(int S, int64_t n, int n_thr, int call, int64_t scratch_bytes, int n_cu, int64_t *out, int n_out);
 
+/* ---- Who spoke when: windowed scores, the hold rule and a Viterbi decode on the device (csrc/timeline.hip) ----
+ * A scoring pass's per-frame matrix [S][n_frames] (fp32, on the device) becomes a label per window of every recording of the batch.
+ * Per recording of n frames, window W >= 1 and hop H >= 1 frames (independent of each other):
+ *   windows   Nw = 0 if n = 0, else 1 + ceil(max(0, n - W) / H) (sr_timeline_windows); window j covers frames [j H, min(j H + W, n)),
+ *             c_j of them (the last may be short).  With W < H that count can name a last window that starts at or behind frame n
+ *             (the last frames lie in the gap between two windows); it is not formed: Nw = min(that, ceil(n / H)).
+ *   sums      sum[j][s] = the float64 sum of the fp32 per-frame values of column s, added in frame order; q[j][s] = sum[j][s] / c_j in
+ *             float64.  A NaN quotient becomes -inf before any comparison; the windows that had one are counted per recording.
+ *   states    one per column.  bg >= 0: column bg is the "nobody" state, its emission q[j][bg] + threshold, its label -1; bg = -1: every
+ *             column is a speaker.  Ties are broken everywhere in one order -- the speaker columns ascending, the nobody state last --
+ *             and the first in that order wins.  A window whose best emission is -inf gets -1.
+ *   mode 0    raw: the first maximum of the emissions in that order.
+ *   mode 1    hold (the reference GUI's rule, gui.py:195-204): shown[0] = raw[0]; for j >= 1, if raw[j] != -1 and raw[j-1] != -1 and
+ *             raw[j-1] != raw[j] then shown[j] = shown[j-1], else shown[j] = raw[j].  Each recording on its own.
+ *   mode 2    viterbi: the path that maximises sum_j e_j(l_j) - beta (number of label changes), beta >= 0, every run but the last at
+ *             least min_dur = m windows (1 .. 16).  Float64, states (s, k), k = 1 .. m:
+ *               j = 0: d(s, 1) = e_0(s), every other state -inf.
+ *               enter = max_s d_{j-1}(s, m) - beta, the first maximum in the order above.
+ *               m = 1: d_j(s, 1) = e + max(d_{j-1}(s, 1), enter), staying wins equality.
+ *               m >= 2: d_j(s, 1) = e + enter; d_j(s, k) = e + d_{j-1}(s, k - 1) for 1 < k < m;
+ *                       d_j(s, m) = e + max(d_{j-1}(s, m), d_{j-1}(s, m - 1)), staying wins equality.
+ *               end state: the first maximum over all (s, k), k from m down to 1 the major order, the order above the minor; labels
+ *               by traceback.  Every operation is one float64 add or one compare ("a wins over b": a >= b), nothing is fused; the path
+ *               score (d of the end state; 0 for an empty recording) is returned per recording.  Modes 0 and 1 return NaN there.
+ *               Emissions of +inf are outside the contract (-inf + inf is a NaN in the recurrence).
+ * sr_timeline_windows: Nw as above (0 for n <= 0, W < 1 or H < 1).  Host only.
+ * sr_timeline_plan: what a call decides for S columns, min_dur and a recording of n_frames (csrc/timeline_plan.cpp; host only).
+ *   Writes 16 fields (n_out >= 16) and returns 16, -1 on refusal: the windows; the forward kernel's variant (0: one wave, S <= 64;
+ *   1: a lane per state, S <= 1024; 2: lanes loop over states, S <= 4096), its lanes, states per lane, the windows of emissions it
+ *   holds ahead (the tile); the slots of the minimum-duration ring per state (m - 1; none for m <= 2), 1 when the ring sits in LDS, the
+ *   forward kernel's LDS bytes; the frames a workgroup of the sum kernel spans at most (3 H + W), the frames it stages at a time, its
+ *   LDS bytes, its grid (workgroups of four windows; blocks of 64 columns); back-pointer bytes per window (a stay bit per state in
+ *   64-bit words + the entering state); the built limits of S (4096) and min_dur (16).
+ * sr_timeline_decide: the decision on window sums in host memory -- upload, the decision kernels, one copy back; the direct test of
+ *   those kernels.  sums[Nw_total][S], counts[Nw_total] (frames per window, >= 1), win_off[U + 1] (window offsets of the recordings,
+ *   from 0).  label_out[Nw_total]; path_score_out[U] and bad_windows_out[U] may be NULL.
+ * sr_timeline_batch: scores the feature batch (the per-frame matrix is the one sr_score_batch_set(frame_ll_out) returns for the same
+ *   batch and flags, bit for bit: a saturated pass redone on the precise engines, the partial-product pairs patched), forms the window
+ *   sums and decides.  win_off_out[U + 1] and label_out[Nw_total] are required (Nw_total from sr_timeline_windows over the batch's
+ *   utterances); sums_out[Nw_total][S], path_score_out[U], bad_windows_out[U] may be NULL.  The call needs the memory frame_ll_out
+ *   needs: S x n_frames floats on the device.
+ * sr_fullset_timeline_batch: the same for a full-covariance set; every column is a speaker (bg = -1).
+ * sr_timeline_pcm_batch: sr_mfcc_extract_batch (CMVN, nd orders of deltas) on resident PCM, then sr_timeline_batch; the features
+ *   stay on the device.  Frame counts: sr_mfcc_num_frames.
+ * The results are the same bits from run to run and do not depend on the recordings decided in the same call (no atomics).
+ * Refused, before the device is touched, with the remedy: window < 1, hop < 1, min_dur outside 1 .. 16, a NaN or negative beta, a NaN
+ * threshold, bg outside [-1, S), mode outside 0 .. 2, S > 4096, a window of sr_timeline_decide with a count < 1, more than 2^30
+ * windows, a null argument; a process forked after the GPU runtime was initialised is refused as well.
+ * Timer kinds (none is added): SR_T_CMVN the sum kernel; SR_T_SCORE_REF the decision and forward kernels; SR_T_ESTEP the traceback. */
+int64_t sr_timeline_windows(int64_t n_frames, int64_t window, int64_t hop);
+int sr_timeline_plan(int S, int min_dur, int64_t n_frames, int window, int hop, int32_t *out, int n_out);
+int sr_timeline_decide(const double *sums, const int32_t *counts, const int64_t *win_off, int U, int S, int bg, double threshold, int mode,
+                       double beta, int min_dur, int *label_out, double *path_score_out, int64_t *bad_windows_out);
+int sr_timeline_batch(SRModelSet *set, SRBatch *features, int window, int hop, int bg, double threshold, int mode, double beta, int min_dur,
+                      int flags, int64_t *win_off_out, int *label_out, double *sums_out, double *path_score_out, int64_t *bad_windows_out);
+int sr_fullset_timeline_batch(SRFullSet *set, SRBatch *features, int window, int hop, double threshold, int mode, double beta, int min_dur,
+                              int64_t *win_off_out, int *label_out, double *sums_out, double *path_score_out, int64_t *bad_windows_out);
+int sr_timeline_pcm_batch(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int window, int hop, int bg, double threshold, int mode,
+                          double beta, int min_dur, int flags, int64_t *win_off_out, int *label_out, double *sums_out, double *path_score_out,
+                          int64_t *bad_windows_out);
+
 #ifdef __cplusplus
 }
 #endif

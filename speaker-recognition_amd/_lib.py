@@ -54,6 +54,7 @@ EXT_SYMBOLS = [
     "sr_sym_eig", "sr_gen_eig", "sr_lda_fit", "sr_backend_project", "sr_plda_score_diag", "sr_eig_plan",
     "sr_calib_train", "sr_calib_eval", "sr_calib_apply", "sr_calib_counts", "sr_calib_plan",
     "sr_feature_norm_batch", "sr_feature_norm_plan", "sr_norm_quantile",
+    "sr_timeline_windows", "sr_timeline_plan", "sr_timeline_decide", "sr_timeline_batch", "sr_fullset_timeline_batch", "sr_timeline_pcm_batch",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -279,6 +280,14 @@ def lib():
         "sr_feature_norm_batch": (vp, [vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_int32)]),
         "sr_feature_norm_plan": (i32, [i32, i32, i32, i64, i32, C.POINTER(C.c_int32), i32]),
         "sr_norm_quantile": (dbl, [dbl]),
+        "sr_timeline_windows": (i64, [i64, i64, i64]),
+        "sr_timeline_plan": (i32, [i32, i32, i64, i32, i32, C.POINTER(C.c_int32), i32]),
+        "sr_timeline_decide": (i32, [dp, C.POINTER(C.c_int32), C.POINTER(i64), i32, i32, i32, dbl, i32, dbl, i32, C.POINTER(i32), dp,
+                                     C.POINTER(i64)]),
+        "sr_timeline_batch": (i32, [vp, vp, i32, i32, i32, dbl, i32, dbl, i32, i32, C.POINTER(i64), C.POINTER(i32), dp, dp, C.POINTER(i64)]),
+        "sr_fullset_timeline_batch": (i32, [vp, vp, i32, i32, dbl, i32, dbl, i32, C.POINTER(i64), C.POINTER(i32), dp, dp, C.POINTER(i64)]),
+        "sr_timeline_pcm_batch": (i32, [vp, vp, vp, i32, i32, i32, i32, dbl, i32, dbl, i32, i32, C.POINTER(i64), C.POINTER(i32), dp, dp,
+                                        C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -539,6 +548,51 @@ def feature_norm_plan(mode: str = "warp", window: int = 301, dim: int = 39, max_
     v = (C.c_int32 * 12)()
     check(lib().sr_feature_norm_plan(feature_norm_mode(mode), int(window), int(dim), int(max_frames), int(n_cu), v, 12), "sr_feature_norm_plan")
     return dict(zip(FEATURE_NORM_PLAN_FIELDS, (int(x) for x in v)))
+
+
+TIMELINE_MODES = ("none", "hold", "viterbi")       # the C ABI's modes 0 (raw), 1, 2 under the names of ``smooth=``
+TIMELINE_PLAN_FIELDS = ("windows", "variant", "lanes", "states_per_lane", "tile", "chain_slots", "chain_lds", "fwd_lds", "sum_span", "sum_chunk",
+                        "sum_lds", "sum_grid_x", "sum_grid_y", "bp_bytes", "max_states", "max_min_dur")
+
+
+def timeline_mode(smooth) -> int:
+    """The C ABI's number of a smoothing name (-1 for anything else: the library refuses it)."""
+    return TIMELINE_MODES.index(smooth) if isinstance(smooth, str) and smooth in TIMELINE_MODES else -1
+
+
+def timeline_windows(n_frames: int, window: int, hop: int) -> int:
+    """Windows of a recording of ``n_frames``: 0 if empty, else 1 + ceil(max(0, n - W) / H), and with W < H no window that
+    would start at or behind frame n (sr_timeline_windows; no GPU needed)."""
+    return int(lib().sr_timeline_windows(int(n_frames), int(window), int(hop)))
+
+
+def timeline_plan(S: int, min_dur: int = 1, n_frames: int = 0, window: int = 150, hop: int = 40) -> dict:
+    """What the timeline decides for ``S`` columns, a minimum turn of ``min_dur`` windows and a recording of ``n_frames``
+    (csrc/timeline_plan.cpp; no GPU needed): the windows, the forward kernel's variant, lanes, states per lane and tile, the ring of
+    the minimum-duration chain, LDS bytes, the sum kernel's span, chunk, LDS bytes and grid, back-pointer bytes per window, limits."""
+    v = (C.c_int32 * 16)()
+    check(lib().sr_timeline_plan(int(S), int(min_dur), int(n_frames), int(window), int(hop), v, 16), "sr_timeline_plan")
+    return dict(zip(TIMELINE_PLAN_FIELDS, (int(x) for x in v)))
+
+
+def timeline_decide(sums, counts, win_off, bg: int = -1, threshold: float = 0.0, mode: int = 0, beta: float = 0.0, min_dur: int = 1):
+    """``sr_timeline_decide`` on window sums [Nw_total, S] in host memory, their frame counts and the recordings' window offsets
+    [U + 1]: -> (labels [Nw_total] int32, path scores [U], NaN-window counts [U])."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.ndim != 2:
+        raise ValueError("expected sums [windows, columns], got shape %r" % (sums.shape,))
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    win_off = np.ascontiguousarray(win_off, dtype=np.int64)
+    U = len(win_off) - 1
+    if U < 0 or len(counts) != len(sums) or (U >= 0 and int(win_off[-1]) != len(sums)):
+        raise ValueError("counts, sums and window offsets do not agree")
+    labels = np.zeros(len(sums), dtype=np.int32)
+    path = np.zeros(max(U, 1), dtype=np.float64)
+    bad = np.zeros(max(U, 1), dtype=np.int64)
+    check(lib().sr_timeline_decide(as_dp(sums), as_i32p(counts), as_i64p(win_off), U, sums.shape[1], int(bg), float(threshold), int(mode),
+                                   float(beta), int(min_dur), as_i32p(labels), as_dp(path), as_i64p(bad)),
+          "sr_timeline_decide")
+    return labels, path[:U], bad[:U]
 
 
 def norm_quantile(p: float) -> float:

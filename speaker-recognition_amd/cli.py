@@ -34,7 +34,7 @@ def read_wav(fname):
 def get_args(argv=None):
     parser = argparse.ArgumentParser(description="Speaker Recognition Command Line Tool",
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
-    parser.add_argument("-t", "--task", help='Task to do. Either "enroll" or "predict"', required=True)
+    parser.add_argument("-t", "--task", help='Task to do: "enroll", "predict" or "timeline"', required=True)
     parser.add_argument("-i", "--input", help="Input Files(to predict) or Directories(to enroll)", required=True)
     parser.add_argument("-m", "--model", help="Model file to save(in enroll) or use(in predict)", required=True)
     parser.add_argument("--mixtures", type=int, default=32, help="GMM order per speaker (default 32, gmmset.py:16)")
@@ -64,6 +64,14 @@ def get_args(argv=None):
                              "cmvn: sliding-window mean / mean and variance). enroll: stored in the model; predict: the model's own "
                              "setting holds unless the flag is given")
     parser.add_argument("--norm-window", type=int, default=None, help="frames of the --feature-norm window (2 .. 1024; default 301)")
+    parser.add_argument("--window", type=float, default=1.5, help="timeline: seconds of a window (default 1.5, the reference GUI's)")
+    parser.add_argument("--hop", type=float, default=0.4, help="timeline: seconds between two windows (default 0.4)")
+    parser.add_argument("--smooth", choices=["none", "hold", "viterbi"], default="hold",
+                        help="timeline: none (the best model per window), hold (the GUI's rule: a new label shows once two windows in "
+                             "a row agree) or viterbi (the best path under --switch-penalty)")
+    parser.add_argument("--switch-penalty", type=float, default=None,
+                        help="timeline, --smooth viterbi: the price of a label change, in nats per frame of window score (no default)")
+    parser.add_argument("--min-duration", type=float, default=None, help="timeline, --smooth viterbi: seconds a turn lasts at least")
     return parser.parse_args(argv)
 
 
@@ -163,6 +171,33 @@ def task_predict(input_files, input_model, gpus=1, reject_threshold=None, remove
     return out
 
 
+def task_timeline(input_files, input_model, args):
+    """One line per segment of every input file: ``<file> <start s> <end s> <name or None>``."""
+    m = ModelInterface.load(input_model)
+    fn = _feature_norm_setting(args)
+    if fn is not None:
+        m.feature_norm = fn
+        m._norm_setting()
+    if args.smooth == "viterbi" and args.switch_penalty is None:
+        print("--smooth viterbi needs --switch-penalty (there is no data-tuned default)")
+        sys.exit(2)
+    if args.reject_threshold is not None:
+        try:
+            m._check_reject()
+        except ValueError as e:
+            print("--reject-threshold: %s" % e)
+            sys.exit(2)
+    out = []
+    for f in sorted(glob.glob(os.path.expanduser(input_files))):
+        fs, signal = read_wav(f)
+        segs = m.timeline(fs, signal, window_s=args.window, hop_s=args.hop, smooth=args.smooth, switch_penalty=args.switch_penalty,
+                          min_duration_s=args.min_duration, reject_threshold=args.reject_threshold)
+        for a, b, name in segs:
+            print("%s %.2f %.2f %s" % (f, a, b, name))
+        out.append((f, segs))
+    return out
+
+
 def _make_interface(args):
     if args is None:
         return ModelInterface()
@@ -187,8 +222,10 @@ def main(argv=None):
         task_enroll(args.input, args.model, args)
     elif args.task == "predict":
         task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence, args.top_c, _feature_norm_setting(args))
+    elif args.task == "timeline":
+        task_timeline(args.input, args.model, args)
     else:
-        print('task must be "enroll" or "predict"')
+        print('task must be "enroll", "predict" or "timeline"')
         sys.exit(2)
 
 

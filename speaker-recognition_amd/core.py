@@ -223,6 +223,20 @@ class ModelSet:
                                             _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_score_batch_set_topc")
         return (sums, arg) + ((fll,) if frame_ll else ()) + ((sel,) if selection else ())
 
+    def timeline(self, feats: Batch, window: int, hop: int, bg=None, threshold: float = 0.0, smooth: str = "hold", switch_penalty=None,
+                 min_windows: int = 1, scores: bool = False, clamp_compat: bool = True):
+        """Who speaks when in every recording of a feature batch (sr_timeline_batch): the batch is scored once, the per-frame
+        values are summed over windows of ``window`` frames every ``hop`` frames on the device, and every window gets a label: a
+        column of the set, or -1 ("nobody") where column ``bg`` (the UBM) plus ``threshold`` beats every speaker.  ``smooth``:
+        "none" (the first maximum per window), "hold" (the reference GUI's rule: a new label shows once two consecutive windows
+        agree) or "viterbi" (the best path under ``switch_penalty`` per label change, runs of at least ``min_windows`` windows;
+        ``switch_penalty`` has no default and must be given).  -> a list of int32 label arrays, one per recording; with
+        ``scores`` -> (labels, path scores [U] (NaN unless viterbi), window sums [Nw, S] per recording)."""
+        tail = _timeline_args(window, hop, bg, threshold, smooth, switch_penalty, min_windows)
+        lengths = np.diff(feats.offsets())
+        return _timeline_call(lib().sr_timeline_batch, "sr_timeline_batch", (self._h, feats._h),
+                              tail + (_lib.SR_CLAMP_COMPAT if clamp_compat else 0,), lengths, len(self), scores)
+
     def bw_stats(self, feats: Batch, model: int = 0, ll: bool = False, resident: bool = False):
         """Baum-Welch statistics of every utterance of a feature batch against model ``model`` of the set, the UBM
         (sr_bw_stats_batch): -> (N[U, K], F[U, K * D][, ll[U], dropped[U]]), float64 (dropped: int64).  N[u, k] = sum_t gamma_k(t),
@@ -339,6 +353,15 @@ class MfccExtractor:
                                               _lib.SR_CLAMP_COMPAT if clamp_compat else 0), "sr_predict_pcm_batch_open")
         return sums, labels, margins
 
+    def timeline_batch(self, models: ModelSet, pcm: Batch, window: int, hop: int, nd: int = 0, bg=None, threshold: float = 0.0,
+                       smooth: str = "hold", switch_penalty=None, min_windows: int = 1, scores: bool = False, clamp_compat: bool = True):
+        """``ModelSet.timeline`` from resident PCM in one call (sr_timeline_pcm_batch): MFCC -> CMVN / deltas -> scoring -> window
+        sums -> labels; the bits of ``extract_batch`` followed by ``ModelSet.timeline``."""
+        tail = _timeline_args(window, hop, bg, threshold, smooth, switch_penalty, min_windows)
+        lengths = [max(0, self.num_frames(int(n)) - int(nd)) for n in np.diff(pcm.offsets())]
+        return _timeline_call(lib().sr_timeline_pcm_batch, "sr_timeline_pcm_batch", (self._h, models._h, pcm._h, int(nd)),
+                              tail + (_lib.SR_CLAMP_COMPAT if clamp_compat else 0,), lengths, len(models), scores)
+
     def predict_batch_topc(self, models: ModelSet, pcm: Batch, bg: int, top_c: int, nd: int = 0, clamp_compat: bool = True):
         """``predict_batch`` through ``ModelSet.score_topc`` (sr_predict_pcm_batch_topc): the features stay on the device;
         -> (sums[U, S], argmax[U] int32), the bits of ``extract_batch`` followed by ``score_topc``."""
@@ -356,6 +379,42 @@ class MfccExtractor:
                 self._h = None
         except Exception:
             pass
+
+
+def _timeline_args(window, hop, bg, threshold, smooth, switch_penalty, min_windows):
+    """The checked arguments of a timeline call, as the C ABI takes them: (window, hop, bg, threshold, mode, beta, min_dur)."""
+    mode = _lib.timeline_mode(smooth)
+    if mode < 0:
+        raise ValueError("smooth must be 'none', 'hold' or 'viterbi' (got %r)" % (smooth,))
+    if mode == 2 and switch_penalty is None:
+        raise ValueError("smooth='viterbi' needs an explicit switch_penalty: there is no data-tuned default")
+    for name, v in (("window", window), ("hop", hop), ("min_windows", min_windows)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer number of %s (got %r)" % (name, "windows" if name == "min_windows" else "frames", v))
+    return (int(window), int(hop), -1 if bg is None else int(bg), float(threshold), mode,
+            0.0 if switch_penalty is None else float(switch_penalty), int(min_windows))
+
+
+def _timeline_call(fn, what, head, tail, lengths, S, scores):
+    """Runs one of the sr_*timeline*_batch calls: ``head`` / ``tail`` are its arguments before / after (window ... min_dur [flags]);
+    ``lengths`` the frames of every recording.  -> per-recording label arrays[, path scores[U], sums per recording]."""
+    window, hop = tail[0], tail[1]
+    U = len(lengths)
+    nw = [_lib.timeline_windows(int(n), window, hop) if window >= 1 and hop >= 1 else 0 for n in lengths]
+    total = int(sum(nw))
+    win_off = np.zeros(U + 1, dtype=np.int64)
+    labels = np.full(max(total, 1), -1, dtype=np.int32)
+    sums = np.zeros((max(total, 1), S), dtype=np.float64) if scores else None
+    path = np.zeros(max(U, 1), dtype=np.float64)
+    bad = np.zeros(max(U, 1), dtype=np.int64)
+    check(fn(*head, *tail, _lib.as_i64p(win_off), _lib.as_i32p(labels), _lib.as_dp(sums) if scores else None, _lib.as_dp(path),
+             _lib.as_i64p(bad)), what)
+    if [int(x) for x in np.diff(win_off)] != nw:
+        raise SRError("%s: the library counted other windows than the caller (%r against %r)" % (what, np.diff(win_off).tolist(), nw))
+    out = [labels[win_off[u]:win_off[u + 1]].copy() for u in range(U)]
+    if not scores:
+        return out
+    return out, path[:U].copy(), [sums[win_off[u]:win_off[u + 1]].copy() for u in range(U)]
 
 
 def open_set_decide(sums, n_frames, bg: int, threshold: float):

@@ -279,6 +279,54 @@ class ModelInterface(object):
         feats = [self._features(fs, sig) for fs, sig in items]
         return self.gmmset.predict(feats)
 
+    def _timeline_frames(self, window_s, hop_s, min_duration_s):
+        """(frame shift in seconds, window, hop in frames, minimum turn in windows) of a timeline call."""
+        shift = float(self.feature_kwargs.get("win_shift_ms", 16)) / 1000.0
+        for name, v in (("window_s", window_s), ("hop_s", hop_s)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+                raise ValueError("%s must be a positive number of seconds (got %r)" % (name, v))
+        W, H = max(1, int(round(window_s / shift))), max(1, int(round(hop_s / shift)))
+        if min_duration_s is None:
+            return shift, W, H, 1
+        if isinstance(min_duration_s, bool) or not isinstance(min_duration_s, (int, float)) or not min_duration_s >= 0:
+            raise ValueError("min_duration_s must be a number of seconds >= 0 (got %r)" % (min_duration_s,))
+        m = max(1, int(np.ceil(min_duration_s / (H * shift) - 1e-9)))
+        if m > 16:
+            raise ValueError("min_duration_s = %r is %d hops of %g s: the decode holds a turn for at most 16 windows (use a longer hop)"
+                             % (min_duration_s, m, H * shift))
+        return shift, W, H, m
+
+    def timeline(self, fs, signal, window_s=1.5, hop_s=0.4, smooth="hold", switch_penalty=None, min_duration_s=None,
+                 reject_threshold=None):
+        """Extension: who speaks when in a recording -> ``[(start_s, end_s, name or None)]``, intervals that tile
+        [0, duration of the features] without gaps.  The features are extracted once for the whole recording (``feature_norm``
+        is honoured; silence removal is not applied: it would change the time axis), scored once, and the per-frame values are
+        summed over windows of ``window_s`` every ``hop_s`` on the device (``core.ModelSet.timeline``).  ``smooth``: "none",
+        "hold" (the reference GUI's rule, gui.py:195-204) or "viterbi" (needs ``switch_penalty``; ``min_duration_s`` is the
+        shortest turn).  ``reject_threshold`` (a number): the model's UBM becomes the "nobody" state, whose windows come back
+        with the name None; only a model enrolled from a UBM can.  Unlike the GUI's loop the windows are not extracted and
+        voice-activity-filtered one by one."""
+        from . import timeline as tl
+        from .core import Batch, _timeline_args
+        shift, W, H, m = self._timeline_frames(window_s, hop_s, min_duration_s)
+        _timeline_args(W, H, None, 0.0, smooth, switch_penalty, m)
+        full = getattr(self, "covariance_type", "diag") == "full"
+        if reject_threshold is not None:
+            self._check_reject()
+        feat = np.asarray(self._features_of(fs, signal))
+        batch = Batch.from_features([feat])
+        kw = dict(smooth=smooth, switch_penalty=switch_penalty, min_windows=m)
+        if full:
+            labels = self.gmmset._full_set().timeline(batch, W, H, **kw)[0]
+            names = list(self.gmmset.y)
+        elif reject_threshold is not None:
+            labels = self.gmmset._open_model_set().timeline(batch, W, H, bg=0, threshold=float(reject_threshold), **kw)[0]
+            names = [None] + list(self.gmmset.y)
+        else:
+            labels = self.gmmset._model_set().timeline(batch, W, H, **kw)[0]
+            names = list(self.gmmset.y)
+        return [(a, b, None if lab < 0 else names[lab]) for a, b, lab in tl.segments(labels, len(feat), W, H, shift)]
+
     def dump(self, fname):
         """ dump all models to file"""
         self.gmmset.before_pickle()

@@ -356,6 +356,15 @@ class FullSet(object):
                    "sr_fullset_predict_pcm_batch")
         return sums, arg
 
+    def timeline(self, batch: Batch, window, hop, threshold=0.0, smooth="hold", switch_penalty=None, min_windows=1, scores=False):
+        """``core.ModelSet.timeline`` for a full-covariance set (sr_fullset_timeline_batch): every column is a speaker (no "nobody"
+        state).  -> a list of int32 label arrays, one per recording[, path scores, window sums per recording]."""
+        from .core import _timeline_args, _timeline_call
+        tail = _timeline_args(window, hop, None, threshold, smooth, switch_penalty, min_windows)
+        tail = tail[:2] + tail[3:]                     # (no bg argument)
+        return _timeline_call(lib().sr_fullset_timeline_batch, "sr_fullset_timeline_batch", (self._h, batch._h), tail,
+                              np.diff(batch.offsets()), self.size, scores)
+
     def __len__(self):
         return self.size
 
