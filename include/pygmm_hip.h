@@ -1100,6 +1100,81 @@ int sr_timeline_pcm_batch(SRMfcc *m, SRModelSet *set, SRBatch *pcm, int nd, int 
                           double beta, int min_dur, int flags, int64_t *win_off_out, int *label_out, double *sums_out, double *path_score_out,
                           int64_t *bad_windows_out);
 
+/* ---- Who spoke when, nobody enrolled: BIC segments and agglomerative clustering on the device (csrc/diar.hip) ----
+ * A feature batch of U recordings, [n_u][D] fp32, resident; 1 <= D <= 64.  All arithmetic below is float64, nothing is fused.
+ *   base segments   L >= 1 frames each: n_seg = floor(n / L), or 1 if that is 0 and n > 0, or 0 if n = 0 (sr_diar_segments).  Segment i
+ *                   covers frames [i L, (i + 1) L); the last reaches to n.
+ *   statistics      of a segment or a cluster, diar_stat_len = 1 + D + D (D + 1) / 2 doubles: N (the frame count), s[D] = sum x,
+ *                   Q[D (D + 1) / 2] = sum x x^T, the lower triangle by rows.  Every entry is summed in frame order, one product and one
+ *                   add per frame.  A merge adds statistics element by element: stat_i = stat_i + stat_j.
+ *   logdet          Sigma = (Q - s s^T / N) / N + ridge I, ridge >= 0; ld = 2 sum_r log L_rr of its lower Cholesky factor.  A pivot that
+ *                   is not finite or not positive fails the cluster: every distance that involves it is +inf, it never merges, and the
+ *                   initial clusters that failed are counted per recording (fail_out).
+ *   delta-BIC       dBIC(a, b) = 1/2 [(N_a + N_b) ld_ab - N_a ld_a - N_b ld_b] - lambda 1/2 (D + D (D + 1) / 2) log(N_a + N_b), lambda > 0;
+ *                   ld_ab is the logdet of the summed statistics.  Negative: one Gaussian explains both.
+ *   change          mode 1 ("bic"): for each boundary b = 1 .. n_seg - 1 and half-width m >= 1 segments, c[b] = dBIC(the sum of segments
+ *                   [max(0, b - m), b), the sum of segments [b, min(n_seg, b + m))), the sums taken in index order (+inf when a
+ *                   factorisation fails).  b is kept iff c[b] > 0, c[b] >= c[b'] for every b' with |b - b'| < m, and no earlier b' in
+ *                   that range has the same value.  The initial clusters are the runs of base segments between kept boundaries, their
+ *                   statistics the sums of their segments in index order.  Mode 0 ("uniform"): every base segment is an initial cluster.
+ *   agglomeration   per recording: alive flags, statistics, ld and a table of distances of which the entries i < j are used.  A step:
+ *                   the live pair (i, j), i < j, of smallest distance, the first in row-major order among equals; stop unless
+ *                   live > k_max (k_max > 0; 0: no cap), or live > k_min and d < threshold; stop also when that distance is +inf;
+ *                   otherwise merge j into i: add the statistics, mark j dead, recompute ld_i and dist(i, k) for every live k.
+ *                   The root of a cluster is its smallest member; labels number the final clusters by first appearance.
+ *   matrix mode     the same loop on a symmetric dissimilarity [n][n], n <= 4096: linkage 0 average, (c_i d_ik + c_j d_jk) / (c_i + c_j)
+ *                   over the cluster sizes c (two products, one add, one division); 1 complete (the larger); 2 single (the smaller).
+ *                   The same argmin, tie order, log and labels.
+ * sr_diar_segments: n_seg as above (0 for n <= 0 or L < 1).  Host only.
+ * sr_diar_plan: what a call decides (csrc/diar_plan.cpp; host only) for recordings of lengths[U] frames under a bound of scratch_bytes
+ *   (<= 0: the option diar_scratch_mib, default 1024).  Writes 16 fields (n_out >= 16): the factorisation's bucket width (D rounded up
+ *   to 16 / 32 / 48 / 64), the doubles of a statistic, the entries of (s, Q) a lane of the statistics kernel owns, its lanes, the
+ *   frames it stages at a time, its LDS bytes, the change kernel's LDS bytes, the number of groups, the built limits of D (64) and of a
+ *   recording's initial clusters (4096), the waves (matrices) per workgroup of the pair / row kernels, the argmin kernel's workgroups per
+ *   recording at most (its workgroups hold 256 lanes), the steps between two reads of the stop word, the bytes of all recordings, the
+ *   bound, 0.  group_begin_out[groups + 1] (recordings [g, g + 1) run together) and rec_out[U][3] (base segments, the most initial
+ *   clusters, bytes on the device) may be NULL.  Returns the number of groups, -1 on refusal.  A recording whose tables exceed the bound
+ *   on its own is refused with the byte count and the remedy (a longer L); a group holds at most 65535 recordings.  The results do not
+ *   depend on the bound, bit for bit.
+ * sr_diar_stats_batch: the statistics of the base segments, brought home: seg_off_out[U + 1], stats_out[n_seg_total][diar_stat_len]
+ *   (cap: the segments stats_out holds).  The direct test of that kernel.
+ * sr_diar_bic_matrix: dBIC of every pair of n <= 4096 clusters from statistics in host memory: out[n][n] (symmetric, 0 on the diagonal),
+ *   ld_out[n] (NaN for a cluster that failed; may be NULL), *fail_out the count of those (may be NULL).  The direct test of the
+ *   factorisation.
+ * sr_diar_cluster_batch: the whole chain.  cap: the entries the per-cluster outputs hold (the batch's base segments always suffice).
+ *   init_cl_off_out[U + 1]: the initial clusters of the recordings; init_off_out[cap + U]: per recording n_init + 1 run boundaries in
+ *   base-segment indices, recording u's at init_cl_off[u] + u; label_out[cap]: a label per initial cluster; merge_i_out, merge_j_out,
+ *   merge_d_out[cap] (may be NULL): recording u's log in its first n_merges_out[u] entries from init_cl_off[u] (zeros behind);
+ *   n_merges_out, n_clusters_out, fail_out[U] (may be NULL).  The merge log is a dendrogram: sr_diar_cut re-cuts it on the host.
+ * sr_diar_cluster_pcm_batch: sr_mfcc_extract_batch (CMVN, nd orders of deltas) on resident PCM, then sr_diar_cluster_batch; the
+ *   features stay on the device.  Frame counts: sr_mfcc_num_frames; the plan's refusals are made from them, before the feature stage runs.
+ * sr_ahc_matrix: the matrix mode.  merge_*_out[n - 1], label_out[n].
+ * sr_diar_cut: the labels a stop rule gives on a merge log (the steps it takes are a prefix of the log).  Returns the number of
+ *   clusters, -1 on refusal; *n_merges_out the steps taken.  Host only.
+ * The results are the same bits from run to run and do not depend on the recordings clustered in the same call (no atomics).
+ * Refused, before the device is touched, with the remedy: D > 64; L < 1, m < 1, lambda <= 0, ridge < 0, a non-finite lambda or ridge, a
+ * NaN threshold; k_min < 1, k_max in 1 .. k_min - 1 or negative; a change mode outside 0 .. 1; more than 4096 initial clusters (uniform
+ * mode; bic mode refuses once the detector has counted them); a NaN, -inf or asymmetric matrix, linkage outside 0 .. 2; a null argument;
+ * a process forked after the GPU runtime was initialised.
+ * Timer kinds (none is added): SR_T_CMVN the statistics and gather kernels; SR_T_SCORE_REF the factorisations (logdet, pairs, change,
+ * rows); SR_T_ESTEP the argmin and merge kernels. */
+int64_t sr_diar_segments(int64_t n_frames, int64_t L);
+int sr_diar_plan(int D, int L, int change, const int64_t *lengths, int U, int64_t scratch_bytes, int64_t *out, int n_out,
+                 int32_t *group_begin_out, int64_t *rec_out);
+int sr_diar_stats_batch(SRBatch *features, int L, int64_t cap, int64_t *seg_off_out, double *stats_out);
+int sr_diar_bic_matrix(int D, int64_t n, const double *stats, double lambda, double ridge, double *out, double *ld_out, int64_t *fail_out);
+int sr_diar_cluster_batch(SRBatch *features, int L, int change, int m, double lambda, double ridge, double threshold, int k_min, int k_max,
+                          int64_t cap, int64_t *init_cl_off_out, int64_t *init_off_out, int32_t *merge_i_out, int32_t *merge_j_out,
+                          double *merge_d_out, int32_t *label_out, int64_t *n_merges_out, int64_t *n_clusters_out, int64_t *fail_out);
+int sr_diar_cluster_pcm_batch(SRMfcc *m, SRBatch *pcm, int nd, int L, int change, int half_width, double lambda, double ridge, double threshold,
+                              int k_min, int k_max, int64_t cap, int64_t *init_cl_off_out, int64_t *init_off_out, int32_t *merge_i_out,
+                              int32_t *merge_j_out, double *merge_d_out, int32_t *label_out, int64_t *n_merges_out, int64_t *n_clusters_out,
+                              int64_t *fail_out);
+int sr_ahc_matrix(int64_t n, const double *dist, int linkage, double threshold, int k_min, int k_max, int32_t *merge_i_out, int32_t *merge_j_out,
+                  double *merge_d_out, int64_t *n_merges_out, int32_t *label_out, int64_t *n_clusters_out);
+int64_t sr_diar_cut(int64_t n, const int32_t *merge_i, const int32_t *merge_j, const double *merge_d, int64_t n_merges, double threshold,
+                    int k_min, int k_max, int32_t *label_out, int64_t *n_merges_out);
+
 #ifdef __cplusplus
 }
 #endif

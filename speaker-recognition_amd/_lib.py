@@ -55,6 +55,8 @@ EXT_SYMBOLS = [
     "sr_calib_train", "sr_calib_eval", "sr_calib_apply", "sr_calib_counts", "sr_calib_plan",
     "sr_feature_norm_batch", "sr_feature_norm_plan", "sr_norm_quantile",
     "sr_timeline_windows", "sr_timeline_plan", "sr_timeline_decide", "sr_timeline_batch", "sr_fullset_timeline_batch", "sr_timeline_pcm_batch",
+    "sr_diar_segments", "sr_diar_plan", "sr_diar_stats_batch", "sr_diar_bic_matrix", "sr_diar_cluster_batch", "sr_diar_cluster_pcm_batch",
+    "sr_ahc_matrix", "sr_diar_cut",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -288,6 +290,18 @@ def lib():
         "sr_fullset_timeline_batch": (i32, [vp, vp, i32, i32, dbl, i32, dbl, i32, C.POINTER(i64), C.POINTER(i32), dp, dp, C.POINTER(i64)]),
         "sr_timeline_pcm_batch": (i32, [vp, vp, vp, i32, i32, i32, i32, dbl, i32, dbl, i32, i32, C.POINTER(i64), C.POINTER(i32), dp, dp,
                                         C.POINTER(i64)]),
+        "sr_diar_segments": (i64, [i64, i64]),
+        "sr_diar_plan": (i32, [i32, i32, i32, C.POINTER(i64), i32, i64, C.POINTER(i64), i32, C.POINTER(C.c_int32), C.POINTER(i64)]),
+        "sr_diar_stats_batch": (i32, [vp, i32, i64, C.POINTER(i64), dp]),
+        "sr_diar_bic_matrix": (i32, [i32, i64, dp, dbl, dbl, dp, dp, C.POINTER(i64)]),
+        "sr_diar_cluster_batch": (i32, [vp, i32, i32, i32, dbl, dbl, dbl, i32, i32, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "sr_diar_cluster_pcm_batch": (i32, [vp, vp, i32, i32, i32, i32, dbl, dbl, dbl, i32, i32, i64, C.POINTER(i64), C.POINTER(i64),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(i64),
+                                            C.POINTER(i64)]),
+        "sr_ahc_matrix": (i32, [i64, dp, i32, dbl, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, C.POINTER(i64), C.POINTER(C.c_int32),
+                                C.POINTER(i64)]),
+        "sr_diar_cut": (i64, [i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, i64, dbl, i32, i32, C.POINTER(C.c_int32), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -593,6 +607,95 @@ def timeline_decide(sums, counts, win_off, bg: int = -1, threshold: float = 0.0,
                                    float(beta), int(min_dur), as_i32p(labels), as_dp(path), as_i64p(bad)),
           "sr_timeline_decide")
     return labels, path[:U], bad[:U]
+
+
+DIAR_CHANGE_MODES = ("uniform", "bic")
+AHC_LINKAGES = ("average", "complete", "single")
+DIAR_PLAN_FIELDS = ("bucket", "stat_len", "entries_per_lane", "stats_wg", "stats_chunk", "stats_lds", "change_lds", "groups", "max_dim",
+                    "max_init", "waves", "argmin_blocks", "cadence", "bytes", "bound")
+
+
+def diar_change_mode(change) -> int:
+    """The C ABI's number of a change-detection name (-1 for anything else: the library refuses it)."""
+    return DIAR_CHANGE_MODES.index(change) if isinstance(change, str) and change in DIAR_CHANGE_MODES else -1
+
+
+def ahc_linkage(linkage) -> int:
+    return AHC_LINKAGES.index(linkage) if isinstance(linkage, str) and linkage in AHC_LINKAGES else -1
+
+
+def diar_segments(n_frames: int, L: int) -> int:
+    """Base segments of a recording of ``n_frames``: floor(n / L), 1 if that is 0 and n > 0 (sr_diar_segments; no GPU needed)."""
+    return int(lib().sr_diar_segments(int(n_frames), int(L)))
+
+
+def diar_stat_len(D: int) -> int:
+    return 1 + D + D * (D + 1) // 2
+
+
+def diar_plan(D: int, lengths=(), L: int = 100, change: str = "bic", scratch_bytes: int = 0) -> dict:
+    """What the diarisation decides for ``D`` dimensions and recordings of ``lengths`` frames (csrc/diar_plan.cpp; no GPU needed):
+    the factorisation's bucket width, the layout of a statistic, the kernels' shapes, the grouping of the recordings under the bound
+    (``scratch_bytes`` 0: the option diar_scratch_mib), per recording its base segments, the most initial clusters and its bytes;
+    ``edges``: the initial-cluster counts at which a kernel's indexing wraps (waves per workgroup, argmin workgroups, its lanes)."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    U = len(lengths)
+    v = (C.c_int64 * 16)()
+    groups = np.zeros(U + 1, dtype=np.int32)
+    rec = np.zeros((max(U, 1), 3), dtype=np.int64)
+    n = check(lib().sr_diar_plan(int(D), int(L), diar_change_mode(change), as_i64p(lengths), U, int(scratch_bytes), v, 16,
+                                 groups.ctypes.data_as(C.POINTER(C.c_int32)), as_i64p(rec)), "sr_diar_plan")
+    out = dict(zip(DIAR_PLAN_FIELDS, (int(x) for x in v)))
+    out["group_begin"] = groups[:n + 1].tolist() if U else []
+    out["n_seg"], out["n_init_bound"], out["rec_bytes"] = (rec[:U, k].tolist() for k in range(3))
+    out["edges"] = [out["waves"], out["argmin_blocks"], out["stats_wg"]]
+    return out
+
+
+def diar_bic_matrix(stats, D: int, penalty: float = 1.0, ridge: float = 1e-3):
+    """``sr_diar_bic_matrix`` on statistics [n, 1 + D + D (D + 1) / 2] in host memory: -> (delta-BIC [n, n], logdets [n] with NaN
+    where the factorisation failed, the count of those)."""
+    stats = np.ascontiguousarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or (1 <= int(D) <= 64 and stats.shape[1] != diar_stat_len(int(D))):
+        raise ValueError("expected statistics [clusters, 1 + D + D (D + 1) / 2], got shape %r for D = %r" % (stats.shape, D))
+    n = len(stats)
+    out = np.zeros((n, n), dtype=np.float64)
+    ld = np.zeros(max(n, 1), dtype=np.float64)
+    nf = C.c_int64(0)
+    check(lib().sr_diar_bic_matrix(int(D), n, as_dp(stats), float(penalty), float(ridge), as_dp(out), as_dp(ld), C.byref(nf)),
+          "sr_diar_bic_matrix")
+    return out, ld[:n], int(nf.value)
+
+
+def ahc_matrix(dist, linkage: int = 0, threshold: float = 0.0, k_min: int = 1, k_max: int = 0):
+    """``sr_ahc_matrix``: -> (labels [n] int32, merge_i, merge_j, merge_d of the steps taken)."""
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError("expected a square dissimilarity matrix, got shape %r" % (dist.shape,))
+    n = len(dist)
+    mi = np.zeros(max(n - 1, 1), dtype=np.int32)
+    mj = np.zeros(max(n - 1, 1), dtype=np.int32)
+    md = np.zeros(max(n - 1, 1), dtype=np.float64)
+    lab = np.zeros(max(n, 1), dtype=np.int32)
+    nm, nc = C.c_int64(0), C.c_int64(0)
+    check(lib().sr_ahc_matrix(n, as_dp(dist), int(linkage), float(threshold), int(k_min), int(k_max), as_i32p(mi), as_i32p(mj), as_dp(md),
+                              C.byref(nm), as_i32p(lab), C.byref(nc)), "sr_ahc_matrix")
+    t = int(nm.value)
+    return lab[:n], mi[:t], mj[:t], md[:t]
+
+
+def diar_cut(n: int, merge_i, merge_j, merge_d, threshold: float = 0.0, k_min: int = 1, k_max: int = 0):
+    """``sr_diar_cut``: the labels [n] a stop rule gives on a merge log, and the steps it takes (no GPU needed)."""
+    mi = np.ascontiguousarray(merge_i, dtype=np.int32).reshape(-1)
+    mj = np.ascontiguousarray(merge_j, dtype=np.int32).reshape(-1)
+    md = np.ascontiguousarray(merge_d, dtype=np.float64).reshape(-1)
+    if not (len(mi) == len(mj) == len(md)):
+        raise ValueError("the three columns of the merge log differ in length")
+    lab = np.zeros(max(int(n), 1), dtype=np.int32)
+    nm = C.c_int64(0)
+    check(int(lib().sr_diar_cut(int(n), as_i32p(mi), as_i32p(mj), as_dp(md), len(mi), float(threshold), int(k_min), int(k_max), as_i32p(lab),
+                                C.byref(nm))), "sr_diar_cut")
+    return lab[:int(n)], int(nm.value)
 
 
 def norm_quantile(p: float) -> float:

@@ -34,9 +34,9 @@ def read_wav(fname):
 def get_args(argv=None):
     parser = argparse.ArgumentParser(description="Speaker Recognition Command Line Tool",
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
-    parser.add_argument("-t", "--task", help='Task to do: "enroll", "predict" or "timeline"', required=True)
+    parser.add_argument("-t", "--task", help='Task to do: "enroll", "predict", "timeline" or "diarize"', required=True)
     parser.add_argument("-i", "--input", help="Input Files(to predict) or Directories(to enroll)", required=True)
-    parser.add_argument("-m", "--model", help="Model file to save(in enroll) or use(in predict)", required=True)
+    parser.add_argument("-m", "--model", help="Model file to save(in enroll) or use(in predict); diarize needs none", default=None)
     parser.add_argument("--mixtures", type=int, default=32, help="GMM order per speaker (default 32, gmmset.py:16)")
     parser.add_argument("--win-length-ms", type=float, default=32)
     parser.add_argument("--win-shift-ms", type=float, default=16)
@@ -72,7 +72,21 @@ def get_args(argv=None):
     parser.add_argument("--switch-penalty", type=float, default=None,
                         help="timeline, --smooth viterbi: the price of a label change, in nats per frame of window score (no default)")
     parser.add_argument("--min-duration", type=float, default=None, help="timeline, --smooth viterbi: seconds a turn lasts at least")
-    return parser.parse_args(argv)
+    parser.add_argument("--rttm", default=None, help="diarize: also write the segments to this file in the RTTM format")
+    parser.add_argument("--speakers", type=int, default=None, help="diarize: exactly this many speakers")
+    parser.add_argument("--max-speakers", type=int, default=None, help="diarize: at most this many speakers")
+    parser.add_argument("--penalty", type=float, default=1.0, help="diarize: the weight of the BIC penalty (default 1; larger: fewer speakers)")
+    args = parser.parse_args(argv)
+    if args.task != "diarize" and args.model is None:
+        parser.error("the following arguments are required: -m/--model")
+    if args.speakers is not None and args.max_speakers is not None:
+        parser.error("--speakers and --max-speakers exclude each other")
+    for name in ("speakers", "max_speakers"):
+        if getattr(args, name) is not None and getattr(args, name) < 1:
+            parser.error("--%s must be >= 1" % name.replace("_", "-"))
+    if not args.penalty > 0:
+        parser.error("--penalty must be > 0")
+    return args
 
 
 def task_enroll(input_dirs, output_model, args=None):
@@ -198,6 +212,26 @@ def task_timeline(input_files, input_model, args):
     return out
 
 
+def task_diarize(input_files, args):
+    """One line per segment of every input file: ``<file> <start s> <end s> <spkN>``; with --rttm the same segments in RTTM."""
+    from .timeline import to_rttm
+    m = _make_interface(args)
+    kw = {} if args.switch_penalty is None else dict(switch_penalty=args.switch_penalty)
+    out, rttm = [], []
+    for f in sorted(glob.glob(os.path.expanduser(input_files))):
+        fs, signal = read_wav(f)
+        segs = m.diarize(fs, signal, penalty=args.penalty, n_speakers=args.speakers, max_speakers=args.max_speakers, window_s=args.window,
+                         hop_s=args.hop, min_duration_s=args.min_duration, **kw)
+        for a, b, name in segs:
+            print("%s %.2f %.2f %s" % (f, a, b, name))
+        rttm.append(to_rttm(segs, recording_id=os.path.splitext(os.path.basename(f))[0]))
+        out.append((f, segs))
+    if args.rttm:
+        with open(args.rttm, "w") as fh:
+            fh.write("".join(rttm))
+    return out
+
+
 def _make_interface(args):
     if args is None:
         return ModelInterface()
@@ -224,8 +258,10 @@ def main(argv=None):
         task_predict(args.input, args.model, args.gpus, args.reject_threshold, args.remove_silence, args.top_c, _feature_norm_setting(args))
     elif args.task == "timeline":
         task_timeline(args.input, args.model, args)
+    elif args.task == "diarize":
+        task_diarize(args.input, args)
     else:
-        print('task must be "enroll", "predict" or "timeline"')
+        print('task must be "enroll", "predict", "timeline" or "diarize"')
         sys.exit(2)
 
 

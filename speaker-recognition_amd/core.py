@@ -145,6 +145,28 @@ class Batch:
         out = (Batch(h),) + ((rk,) if ranks else ()) + ((deg[:self.n_utt],) if counts else ())
         return out if len(out) > 1 else out[0]
 
+    def segment_stats(self, L: int):
+        """Full-covariance statistics of the base segments of ``L`` frames of every recording of a feature batch, computed on the
+        device and brought home (sr_diar_stats_batch): -> (segment offsets [U + 1], statistics [n_seg, 1 + D + D (D + 1) / 2]
+        float64: N, s, the lower triangle of Q by rows)."""
+        lengths = np.diff(self.offsets())
+        cap = int(sum(_lib.diar_segments(int(n), int(L)) for n in lengths)) if isinstance(L, (int, np.integer)) and L >= 1 else 0
+        seg_off = np.zeros(self.n_utt + 1, dtype=np.int64)
+        stats = np.zeros((max(cap, 1), _lib.diar_stat_len(max(self.dim, 1))), dtype=np.float64)
+        check(lib().sr_diar_stats_batch(self._h, int(L), cap, _lib.as_i64p(seg_off), _lib.as_dp(stats)), "sr_diar_stats_batch")
+        return seg_off, stats[:cap]
+
+    def diarize(self, L: int = 100, change: str = "bic", half_width: int = 2, penalty: float = 1.0, ridge: float = 1e-3,
+                threshold: float = 0.0, k_min: int = 1, k_max: int = 0):
+        """Clusters the frames of every recording of a feature batch with nobody enrolled (sr_diar_cluster_batch; include/pygmm_hip.h
+        "Who spoke when, nobody enrolled"): base segments of ``L`` frames, BIC change detection (``change`` "bic", half-width
+        ``half_width`` segments) or none ("uniform"), agglomerative clustering under delta-BIC with weight ``penalty`` until no pair
+        lies below ``threshold`` (never below ``k_min`` clusters; ``k_max`` > 0: down to at most that many whatever the distance).
+        -> a list with one dict per recording: ``labels`` (per initial cluster), ``init_off`` (the initial clusters' runs in
+        base-segment indices), ``merge_i``, ``merge_j``, ``merge_d`` (the steps taken), ``n_clusters``, ``failed``, ``n_seg``."""
+        tail = _diar_args(L, change, half_width, penalty, ridge, threshold, k_min, k_max)
+        return _diar_call(lib().sr_diar_cluster_batch, "sr_diar_cluster_batch", (self._h,), tail, np.diff(self.offsets()))
+
     def __del__(self):
         try:
             if self._owner and self._h:
@@ -362,6 +384,14 @@ class MfccExtractor:
         return _timeline_call(lib().sr_timeline_pcm_batch, "sr_timeline_pcm_batch", (self._h, models._h, pcm._h, int(nd)),
                               tail + (_lib.SR_CLAMP_COMPAT if clamp_compat else 0,), lengths, len(models), scores)
 
+    def diarize_batch(self, pcm: Batch, nd: int = 0, L: int = 100, change: str = "bic", half_width: int = 2, penalty: float = 1.0,
+                      ridge: float = 1e-3, threshold: float = 0.0, k_min: int = 1, k_max: int = 0):
+        """``Batch.diarize`` from resident PCM in one call (sr_diar_cluster_pcm_batch): MFCC -> CMVN / deltas -> statistics ->
+        change detection -> clustering; the bits of ``extract_batch`` followed by ``Batch.diarize``."""
+        tail = _diar_args(L, change, half_width, penalty, ridge, threshold, k_min, k_max)
+        lengths = [max(0, self.num_frames(int(n)) - int(nd)) for n in np.diff(pcm.offsets())]
+        return _diar_call(lib().sr_diar_cluster_pcm_batch, "sr_diar_cluster_pcm_batch", (self._h, pcm._h, int(nd)), tail, lengths)
+
     def predict_batch_topc(self, models: ModelSet, pcm: Batch, bg: int, top_c: int, nd: int = 0, clamp_compat: bool = True):
         """``predict_batch`` through ``ModelSet.score_topc`` (sr_predict_pcm_batch_topc): the features stay on the device;
         -> (sums[U, S], argmax[U] int32), the bits of ``extract_batch`` followed by ``score_topc``."""
@@ -393,6 +423,39 @@ def _timeline_args(window, hop, bg, threshold, smooth, switch_penalty, min_windo
             raise ValueError("%s must be an integer number of %s (got %r)" % (name, "windows" if name == "min_windows" else "frames", v))
     return (int(window), int(hop), -1 if bg is None else int(bg), float(threshold), mode,
             0.0 if switch_penalty is None else float(switch_penalty), int(min_windows))
+
+
+def _diar_args(L, change, half_width, penalty, ridge, threshold, k_min, k_max):
+    """The checked arguments of a diarisation call, as the C ABI takes them: (L, change, m, lambda, ridge, threshold, k_min, k_max)."""
+    mode = _lib.diar_change_mode(change)
+    if mode < 0:
+        raise ValueError("change must be 'bic' or 'uniform' (got %r)" % (change,))
+    for name, v in (("L", L), ("half_width", half_width), ("k_min", k_min), ("k_max", k_max)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer (got %r)" % (name, v))
+    return (int(L), mode, int(half_width), float(penalty), float(ridge), float(threshold), int(k_min), int(k_max))
+
+
+def _diar_call(fn, what, head, tail, lengths):
+    """Runs sr_diar_cluster_batch / _pcm_batch; ``lengths``: the frames of every recording.  -> a dict per recording."""
+    L = tail[0]
+    U = len(lengths)
+    n_seg = [_lib.diar_segments(int(n), L) if L >= 1 else 0 for n in lengths]
+    cap = int(sum(n_seg))
+    i32 = C.POINTER(C.c_int32)
+    cl_off = np.zeros(U + 1, dtype=np.int64)
+    init_off = np.zeros(cap + U + 1, dtype=np.int64)
+    mi, mj, lab = (np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3))
+    md = np.zeros(max(cap, 1), dtype=np.float64)
+    nm, nc, nf = (np.zeros(max(U, 1), dtype=np.int64) for _ in range(3))
+    check(fn(*head, *tail, cap, _lib.as_i64p(cl_off), _lib.as_i64p(init_off), mi.ctypes.data_as(i32), mj.ctypes.data_as(i32), _lib.as_dp(md),
+             lab.ctypes.data_as(i32), _lib.as_i64p(nm), _lib.as_i64p(nc), _lib.as_i64p(nf)), what)
+    out = []
+    for u in range(U):
+        a, b, t = int(cl_off[u]), int(cl_off[u + 1]), int(nm[u])
+        out.append(dict(labels=lab[a:b].copy(), init_off=init_off[a + u:b + u + 1].copy(), merge_i=mi[a:a + t].copy(), merge_j=mj[a:a + t].copy(),
+                        merge_d=md[a:a + t].copy(), n_clusters=int(nc[u]), failed=int(nf[u]), n_seg=n_seg[u]))
+    return out
 
 
 def _timeline_call(fn, what, head, tail, lengths, S, scores):

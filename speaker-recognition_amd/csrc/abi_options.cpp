@@ -5,6 +5,8 @@
 #include "bw_stats.hpp"
 #include "calib.hpp"
 #include "calib_plan.hpp"
+#include "diar.hpp"
+#include "diar_plan.hpp"
 #include "em.hpp"
 #include "featnorm.hpp"
 #include "featnorm_plan.hpp"
@@ -122,6 +124,8 @@ int sr_set_option(const char *key, long value) {
         set_scratch_mib(key, value, NORM_DEFAULT_SCRATCH, set_norm_scratch_mib);
     } else if (k == "calib_scratch_mib") {
         set_scratch_mib(key, value, CALIB_DEFAULT_SCRATCH, set_calib_scratch_mib);
+    } else if (k == "diar_scratch_mib") {
+        set_scratch_mib(key, value, DIAR_DEFAULT_SCRATCH, set_diar_scratch_mib);
     } else if (k == "plda_scratch_mib") {
         set_scratch_mib(key, value, PLDA_DEFAULT_SCRATCH, set_plda_scratch_mib);
     } else if (k == "jfa_lds_rows") {

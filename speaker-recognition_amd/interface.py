@@ -306,14 +306,18 @@ class ModelInterface(object):
         shortest turn).  ``reject_threshold`` (a number): the model's UBM becomes the "nobody" state, whose windows come back
         with the name None; only a model enrolled from a UBM can.  Unlike the GUI's loop the windows are not extracted and
         voice-activity-filtered one by one."""
-        from . import timeline as tl
-        from .core import Batch, _timeline_args
+        from .core import _timeline_args
         shift, W, H, m = self._timeline_frames(window_s, hop_s, min_duration_s)
         _timeline_args(W, H, None, 0.0, smooth, switch_penalty, m)
-        full = getattr(self, "covariance_type", "diag") == "full"
         if reject_threshold is not None:
             self._check_reject()
-        feat = np.asarray(self._features_of(fs, signal))
+        return self._timeline_of(np.asarray(self._features_of(fs, signal)), shift, W, H, m, smooth, switch_penalty, reject_threshold)
+
+    def _timeline_of(self, feat, shift, W, H, m, smooth, switch_penalty, reject_threshold):
+        """``timeline`` on the recording's feature matrix, its arguments checked and in frames."""
+        from . import timeline as tl
+        from .core import Batch
+        full = getattr(self, "covariance_type", "diag") == "full"
         batch = Batch.from_features([feat])
         kw = dict(smooth=smooth, switch_penalty=switch_penalty, min_windows=m)
         if full:
@@ -326,6 +330,71 @@ class ModelInterface(object):
             labels = self.gmmset._model_set().timeline(batch, W, H, **kw)[0]
             names = list(self.gmmset.y)
         return [(a, b, None if lab < 0 else names[lab]) for a, b, lab in tl.segments(labels, len(feat), W, H, shift)]
+
+    def _diarize_args(self, segment_s, change, penalty, n_speakers, max_speakers, gmm_order):
+        """(frame shift in seconds, frames per base segment, k_min, k_max) of a diarize call, its arguments checked."""
+        from . import _lib
+        shift = float(self.feature_kwargs.get("win_shift_ms", 16)) / 1000.0
+        if isinstance(segment_s, bool) or not isinstance(segment_s, (int, float)) or not segment_s > 0:
+            raise ValueError("segment_s must be a positive number of seconds (got %r)" % (segment_s,))
+        if _lib.diar_change_mode(change) < 0:
+            raise ValueError("change must be 'bic' or 'uniform' (got %r)" % (change,))
+        if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or not penalty > 0 or not np.isfinite(penalty):
+            raise ValueError("penalty must be a finite number > 0 (got %r)" % (penalty,))
+        for name, v in (("n_speakers", n_speakers), ("max_speakers", max_speakers)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1):
+                raise ValueError("%s must be None or an integer >= 1 (got %r)" % (name, v))
+        if n_speakers is not None and max_speakers is not None:
+            raise ValueError("give n_speakers (exactly that many) or max_speakers (at most that many), not both")
+        if isinstance(gmm_order, bool) or not isinstance(gmm_order, (int, np.integer)) or gmm_order < 1:
+            raise ValueError("gmm_order must be an integer >= 1 (got %r)" % (gmm_order,))
+        L = max(1, int(round(segment_s / shift)))
+        if n_speakers is not None:
+            return shift, L, int(n_speakers), int(n_speakers)
+        return shift, L, 1, 0 if max_speakers is None else int(max_speakers)
+
+    def diarize(self, fs, signal, segment_s=1.0, change="bic", penalty=1.0, n_speakers=None, max_speakers=None, resegment=True,
+                gmm_order=8, **timeline_kw):
+        """Extension: who speaks when in a recording with nobody enrolled -> ``[(start_s, end_s, "spk0"), ...]``, intervals that
+        tile [0, duration of the features] without gaps.  The features are extracted as ``timeline`` extracts them and clustered
+        on the device (``core.Batch.diarize``: base segments of ``segment_s``, BIC change detection or ``change="uniform"``,
+        agglomerative clustering under delta-BIC with weight ``penalty``; ``n_speakers`` forces that many clusters,
+        ``max_speakers`` caps them).  With ``resegment`` one model of ``gmm_order`` mixtures per cluster is fitted on that cluster's
+        frames by the batched fit of this interface's ``covariance_type``, and ``timeline(smooth="viterbi")`` decodes the
+        recording over those models (``timeline_kw``: window_s, hop_s, switch_penalty -- 5.0 here, not tuned on data --,
+        min_duration_s).  A recording that ends with one cluster skips the resegmentation.  Speakers are named by first
+        appearance: spk0, spk1, ..."""
+        from . import diarize as dz
+        from .core import Batch, _timeline_args
+        shift, L, k_min, k_max = self._diarize_args(segment_s, change, penalty, n_speakers, max_speakers, gmm_order)
+        kw = dict(dict(window_s=1.5, hop_s=0.4, switch_penalty=5.0, min_duration_s=None), **timeline_kw)
+        if set(kw) - {"window_s", "hop_s", "switch_penalty", "min_duration_s"}:
+            raise ValueError("diarize passes window_s, hop_s, switch_penalty and min_duration_s on to timeline (got %r)" % sorted(timeline_kw))
+        _, W, H, m = self._timeline_frames(kw["window_s"], kw["hop_s"], kw["min_duration_s"])
+        _timeline_args(W, H, None, 0.0, "viterbi", kw["switch_penalty"], m)
+        feat = np.asarray(self._features_of(fs, signal))
+        res = Batch.from_features([feat]).diarize(L=L, change=change, penalty=float(penalty), k_min=k_min, k_max=k_max)[0]
+        labels, ranges = res["labels"], dz.frame_ranges(res["init_off"], len(feat), L)
+        if not resegment or res["n_clusters"] <= 1:
+            return [(a, b, "spk%d" % lab) for a, b, lab in dz.frame_segments(res["init_off"], labels, len(feat), L, shift)]
+        sub = self._cluster_models(feat, labels, ranges, res["n_clusters"], gmm_order)
+        return sub._timeline_of(feat, shift, W, H, m, "viterbi", kw["switch_penalty"], None)
+
+    def _cluster_models(self, feat, labels, ranges, n_clusters, gmm_order):
+        """An interface of this one's settings whose speakers are the clusters: one model per cluster, fitted on its frames by the
+        batched fit (the features make the round trip through the host that ``train`` makes)."""
+        sub = ModelInterface(gmm_order=int(gmm_order), feature_kwargs=self.feature_kwargs, diff=self.diff, nd=self.nd, lpc=self.lpc,
+                             gmm_kwargs=self.gmm_kwargs, verbose=False, covariance_type=getattr(self, "covariance_type", "diag"),
+                             feature_norm=getattr(self, "feature_norm", None))
+        sub.UBM_MODEL_FILE = None
+        for c in range(int(n_clusters)):
+            rows = np.concatenate([feat[a:b] for (a, b), lab in zip(ranges.tolist(), labels) if lab == c], axis=0)
+            if len(rows) < int(gmm_order):
+                raise ValueError("cluster spk%d holds %d frames, fewer than gmm_order = %d mixtures: lower gmm_order, or raise penalty / "
+                                 "lower max_speakers so that small clusters merge" % (c, len(rows), gmm_order))
+            sub.features["spk%d" % c] = list(rows)
+        sub.train()
+        return sub
 
     def dump(self, fname):
         """ dump all models to file"""
