@@ -12,7 +12,7 @@ static std::string fmt(const char *f, long long a = 0, long long b = 0) {
     return buf;
 }
 
-// the padded widths the vector layout packs rows of up to BW_MAX_DIM dimensions at (gmm_model.cpp: pick_padded_dim)
+// the padded widths the vector layout packs rows of up to BW_MAX_DIM dimensions at (model_pack.cpp: pick_padded_dim)
 static int bw_padded_dim(int D) {
     static const int dims[] = {8, 13, 16, 24, 26, 32, 34, 39, 40};
     for (int d : dims)

@@ -702,14 +702,14 @@ void score_batch_set_open(SRModelSet &set, SRBatch &feat, double *sums_out, cons
 
 // Work items of the pipelined shared-sigma kernel over a 32-frame tile table: tiles in order, every full one an item of its own, the
 // ragged tails (1000-frame utterances leave 8 of 32 columns: 2.3 % of the pass's MFMAs on dead frames) packed greedily, in order,
-// up to four and up to 32 columns to an item, all packed items together at the END of the list (pack_tail_tiles, gmm_model.hpp).
+// up to four and up to 32 columns to an item, all packed items together at the END of the list (pack_tail_tiles, score_plan.hpp).
 // The table is padded with empty items to whole rounds of H2P_ROUND_ITEMS = 8 workgroups x 12 waves: the kernel reads
 // (tiles + n_tiles)[unit] for every unit of a launched round without a bound of its own.
 namespace sr {
 void ensure_work_table(TileTable &tt, bool pack_tails) {
     if ((tt.n_work > 0 && tt.work_packed == pack_tails) || tt.n_tiles == 0) return;
     static_assert(sizeof(TileDesc) == sizeof(int4), "work items travel in the tile table's buffer");
-    // (pack_tail_tiles, gmm_model.cpp: full tiles in order, the packed items together at the end of the list)
+    // (pack_tail_tiles, score_plan.cpp: full tiles in order, the packed items together at the end of the list)
     std::vector<int> counts(tt.h_tiles.size());
     for (size_t t = 0; t < counts.size(); t++) counts[t] = tt.h_tiles[t].count;
     const std::vector<WorkItem> items = pack_tail_tiles(counts, tt.frames_per_tile, pack_tails);

@@ -51,6 +51,12 @@ struct MelLayout {
     }
 };
 MelLayout mel_layout(const SRMfcc &m);
+// Sweep starts of the MFCC kernels' mel gather (mfcc.hip: four lanes per band, one ds_read_b128 each per step, bands {0,3,5,6},
+// {1,2,4,7}, {8,11,13,14}, {9,10,12,15} of a pass of 16 served together over 16 slots of 16 bytes): start[b] <= col0[b], a multiple
+// of 4, >= 0, moved down only as far as the band's padded run still fits pass_len[b / 16]; per group the choice with the fewest extra
+// LDS cycles, then the least padding.  Host-only.
+void mel_sweep_starts(const int *col0, const int *cnt, int n_bands, const int pass_len[4], int *start);
+int mel_sweep_extra_cycles(const int *start, const int *cnt, int n_bands, int pass);      // extra LDS cycles per read instruction of that pass
 
 enum MfccKernel { MFCC_F32_FAST = 0, MFCC_F32_GENERIC = 1, MFCC_F64_FAST = 2, MFCC_F64_GENERIC = 3 };
 

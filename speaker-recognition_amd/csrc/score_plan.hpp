@@ -96,6 +96,13 @@ ScorePlan plan_score(const SRModelSet &set, int64_t n_rows, int n_utt, const Sco
 // Model groups of a pass over `n_tiles` > 0 tiles of plan.tile_frames frames: gcb[g] .. gcb[g + 1] = group g's chunks (blocks for the
 // shared-sigma engines); G = gcb.size() - 1.
 std::vector<int> plan_groups(const SRModelSet &set, const ScorePlan &plan, int n_tiles, const ScoreOptions &opt, int n_cu);
+// Work items of the pipelined shared-sigma kernel over a table of tiles with `counts[t]` frames each (<= frames_per_tile): item =
+// {tile, tile or -1, tile or -1, tile or -1}.  Every FULL tile is an item of its own, in order; with `pack_tails` the ragged ones are
+// packed greedily, in order, up to four and up to frames_per_tile columns to an item, and all packed items come LAST (their waves
+// close several tiles per model block: together at the end of the grid they stay in step with each other, scattered they push their
+// workgroups out of phase with the others of their XCD and the parameter stream out of its L2).  Host-only: tests/host/host_checks.cpp.
+struct WorkItem { int t[4]; };
+std::vector<WorkItem> pack_tail_tiles(const std::vector<int> &counts, int frames_per_tile, bool pack_tails);
 
 // Packs the layouts a set needs (all of them for small sets; for large ones the vector layout plus
 // the one the dispatcher will pick, or the one forced by score_engine at creation time).

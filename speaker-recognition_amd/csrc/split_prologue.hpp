@@ -3,7 +3,7 @@
 //
 // Contraction step ks covers features 8 ks .. 8 ks + 7, two slots each (x'^2 against A2, x' against A1).  Lane (col, hh) of the
 // wave holds slots 8 hh .. 8 hh + 7 of every step for frame `col`: BOTH powers of features f0..f3 = 8 ks + 4 hh + 0..3, in the
-// order f0^2 f1^2 f0 f1 f2^2 f3^2 f2 f3 -- pairs as the packed instructions produce them (gmm_model.cpp packs the mixture side
+// order f0^2 f1^2 f0 f1 f2^2 f3^2 f2 f3 -- pairs as the packed instructions produce them (model_pack.cpp: split_slot packs the mixture side
 // to match).  The very last slot (feature 8 KS - 1 >= dim, first power) carries the constant 1 that picks up C_k.  breg[ks][part] = the 16-bit parts of this lane's 8 slots of step ks.
 //
 // Round 4.  This prologue is what the 256 x 39 point mostly WAS: 0.17 of its 0.32 ms with nothing else in the kernel, and --

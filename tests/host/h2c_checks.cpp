@@ -1,5 +1,5 @@
 // h2c_checks.cpp -- the compact order of the pipelined shared-sigma kernel on the host: csrc/score_shapes.hpp's map (h2c_map,
-// h2c_younger) and csrc/gmm_model.cpp's pack_h2_compact beside the flat pack_models_h2_shared.  A stand-alone program, built by
+// h2c_younger) and csrc/model_pack_shared.cpp's pack_h2_compact beside the flat pack_models_h2_shared.  A stand-alone program, built by
 // tests/test_h2c_host.py with g++ -fsanitize=address,undefined (host code only).
 //   map:   a wave's fragment reads and waits replayed on an in-order queue for every part length: the fragment an MFMA step names
 //          has arrived, belongs to the image being multiplied, and its register is refilled only after the image's last use of it;

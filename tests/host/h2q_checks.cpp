@@ -1,6 +1,6 @@
 // h2q_checks.cpp -- pairs of blocks in the compact pipelined shared-sigma kernel, on the host: the pair arithmetic of
 // csrc/score_shapes.hpp (h2q_*: what the kernel indexes its stages and images with) and the premise pairing rests on -- in
-// csrc/gmm_model.cpp's pack_h2_compact every block's quadratic-half image of a mixture tile holds the same bytes.  A stand-alone
+// csrc/model_pack_shared.cpp's pack_h2_compact every block's quadratic-half image of a mixture tile holds the same bytes.  A stand-alone
 // program, built by tests/test_h2q_host.py with g++ -fsanitize=address,undefined (host code only).
 //   pairs:  for every (15, m), m = 0 .. 15 (0: a lone block), a mixture tile is walked stage by stage from h2q_stage_block /
 //           h2q_stage_image and compared with the order [Q][L_0 .. L_14][L'_0 .. L'_(m-1)] written out by hand: stages, images

@@ -1,7 +1,8 @@
-// Host-side checks of csrc/gmm_model.cpp, csrc/score_plan.cpp (the dispatcher's decisions: mode "plan") and csrc/mfcc_plan.cpp (the MFCC
+// Host-side checks of what csrc/gmm_model.hpp declares, csrc/score_plan.cpp (the dispatcher's decisions: mode "plan") and csrc/mfcc_plan.cpp (the MFCC
 // stage's table layout and launch decisions: mode "mfcc"); model packers, text format, tail packing, the MFCC kernels' mel sweep starts), built by tests/test_host_sanitizers.py with -fsanitize=address,undefined (and once
 // with -fsanitize=thread): the model packers (every layout, threaded and not), the text parser on mutated model texts, and
-// the printf / strtod-free number conversions against libc.  Test infrastructure: not part of lib/pygmm.so.
+// the printf / strtod-free number conversions against libc.  Mode "pack": every packer's image against tests/host/pack_table.inc.
+// Test infrastructure: not part of lib/pygmm.so.
 #include "gmm_model.hpp"
 #include "mfcc_plan.hpp"
 #include "score_plan.hpp"
@@ -448,7 +449,243 @@ static int check_mfcc_plan() {
     return bad;
 }
 
+// ---- mode "pack": the packed images of every layout, pinned (tests/host/pack_table.inc) ----
+// A row is one (set, layout) pair: an FNV-1a 64-bit hash over the raw bytes of every vector member of the packed struct (each
+// member's byte count, as 8 bytes, goes in ahead of its bytes), every integer member exactly, every double member to a relative
+// 1e-12 (libm's log / log2 may differ in the last place between CPUs; the images are fp32 or 16-bit roundings of such sums).
+// Sets: make_plan_set's kinds 0 (independent), 1 (UBM + MAP-like copies), 2 (orders K and K / 2), then one of
+//   mod 1  weight K / 2 of the middle model 0 (of every model for kind 1: the set stays shared)      -- the fp16 dead-mixture rule
+//   mod 2  weight K / 2 of the middle model -0.25
+//   mod 3  sigma (K / 2, D / 2) of the middle model 0, its mean 10 (mean - centre != 0: no NaN in the image) -- vector layout only;
+//          flush_band comes out infinite
+// Layouts: every one that accepts the set -- the matrix-core ones up to MAX_MATRIX_DIM dimensions, the shared-sigma ones where
+// models_share_sigma_and_weights holds, the compact order for every h2-shared image (empty where the form does not apply).
+// `pack print` writes the table; it is recorded ONCE from the commit named above the table, never from the code under test.
+enum { PK_VECTOR, PK_BF16X3, PK_F16X2, PK_BX3_SHARED, PK_H2_SHARED, PK_H2_COMPACT, PK_LAYOUTS };
+static const char *const kPackLayoutNames[PK_LAYOUTS] = {"PK_VECTOR", "PK_BF16X3", "PK_F16X2", "PK_BX3_SHARED", "PK_H2_SHARED", "PK_H2_COMPACT"};
+struct PackSet { int S, K, D, kind, mod; };
+struct PackRow {
+    PackSet set;
+    int layout;
+    unsigned long long hash;
+    long long iv[6];       // the struct's integer members in declaration order (h2-shared: then its ref's), the rest 0
+    double dv[8];          // its double members in declaration order (h2-shared: then its ref's), the rest 0
+};
+struct PackError { const char *what, *text; };
+#include "pack_table.inc"
+
+struct Fnv {
+    uint64_t h = 0xcbf29ce484222325ull;
+    void bytes(const void *p, size_t n) {
+        const unsigned char *b = (const unsigned char *)p;
+        for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ull;
+    }
+    template <class T>
+    void vec(const std::vector<T> &v) {
+        const uint64_t n = (uint64_t)v.size() * sizeof(T);
+        bytes(&n, 8);
+        if (n) bytes(v.data(), (size_t)n);
+    }
+};
+
+static std::vector<GMM> make_pack_set(const PackSet &ps) {
+    auto ms = make_plan_set(PlanSet{ps.S, ps.K, ps.D, ps.kind});
+    const int mid = ps.S / 2, k = ms[mid].nr_mixtures / 2;
+    if (ps.mod == 1)
+        for (int s = 0; s < ps.S; s++)
+            if (s == mid || ps.kind == 1) ms[s].weights[ms[s].nr_mixtures / 2] = 0.0;
+    if (ps.mod == 2) ms[mid].weights[k] = -0.25;
+    if (ps.mod == 3) {
+        ms[mid].sigma[(size_t)k * ps.D + ps.D / 2] = 0.0;
+        ms[mid].mean[(size_t)k * ps.D + ps.D / 2] = 10.0;
+    }
+    return ms;
+}
+
+static void add_split(const PackedSplit &p, Fnv &f, PackRow &r, int i0, int d0) {
+    f.vec(p.params), f.vec(p.chunks), f.vec(p.model_chunk_begin), f.vec(p.center), f.vec(p.scale);
+    r.iv[i0] = p.scheme, r.iv[i0 + 1] = p.parts, r.iv[i0 + 2] = p.ks;
+    r.dv[d0] = p.amp, r.dv[d0 + 1] = p.pad_waste, r.dv[d0 + 2] = p.sigma_ratio, r.dv[d0 + 3] = p.coef_max;
+}
+
+// the rows of one set, in layout order
+static std::vector<PackRow> pack_rows(const PackSet &ps, bool vector_and_h2_shared_only = false) {
+    const auto ms = make_pack_set(ps);
+    std::vector<const GMM *> v;
+    for (auto &g : ms) v.push_back(&g);
+    std::vector<PackRow> rows;
+    auto row = [&](int layout) -> PackRow & {
+        rows.push_back(PackRow{ps, layout, 0, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}});
+        return rows.back();
+    };
+    const bool shared = models_share_sigma_and_weights(v);
+    {
+        const PackedModels p = pack_models(v);
+        PackRow &r = row(PK_VECTOR);
+        Fnv f;
+        f.vec(p.params), f.vec(p.center), f.vec(p.chunks), f.vec(p.model_chunk_begin), f.vec(p.model_mixtures);
+        r.hash = f.h;
+        r.iv[0] = p.n_models, r.iv[1] = p.dim, r.iv[2] = p.dp, r.iv[3] = shared;
+        r.dv[0] = p.flush_band;
+    }
+    if (ps.D > MAX_MATRIX_DIM || ps.mod == 3) return rows;
+    for (int scheme : {SPLIT_BF16X3, SPLIT_F16X2}) {
+        if (vector_and_h2_shared_only) break;
+        const PackedSplit p = pack_models_split(v, scheme);
+        PackRow &r = row(scheme == SPLIT_BF16X3 ? PK_BF16X3 : PK_F16X2);
+        Fnv f;
+        add_split(p, f, r, 0, 0);
+        r.hash = f.h;
+    }
+    if (!shared) return rows;
+    if (!vector_and_h2_shared_only) {
+        const PackedBx3Shared p = pack_models_bx3_shared(v);
+        PackRow &r = row(PK_BX3_SHARED);
+        Fnv f;
+        f.vec(p.params), f.vec(p.blocks), f.vec(p.center);
+        r.hash = f.h;
+        r.iv[0] = p.kq, r.iv[1] = p.kl, r.iv[2] = p.n_tiles;
+        r.dv[0] = p.amp, r.dv[1] = p.pad_waste;
+    }
+    const PackedH2Shared hs = pack_models_h2_shared(v);
+    {
+        PackRow &r = row(PK_H2_SHARED);
+        Fnv f;
+        f.vec(hs.params), f.vec(hs.blocks), f.vec(hs.center), f.vec(hs.scale), f.vec(hs.q_desc), f.vec(hs.l_desc);
+        r.iv[0] = hs.kqf, r.iv[1] = hs.klf, r.iv[2] = hs.n_tiles;
+        r.dv[0] = hs.amp, r.dv[1] = hs.pad_waste, r.dv[2] = hs.sigma_ratio, r.dv[3] = hs.coef_max;
+        add_split(hs.ref, f, r, 3, 4);
+        r.hash = f.h;
+    }
+    if (!vector_and_h2_shared_only) {
+        const PackedH2Compact p = pack_h2_compact(hs, ps.D);
+        PackRow &r = row(PK_H2_COMPACT);
+        Fnv f;
+        f.vec(p.params), f.vec(p.blocks), f.vec(p.q_desc), f.vec(p.l_desc);
+        r.hash = f.h;
+        r.iv[0] = p.nk, r.iv[1] = p.nf, r.iv[2] = p.nb;
+    }
+    return rows;
+}
+
+static std::vector<PackSet> pack_sets() {
+    static const int shapes[][3] = {{1, 1, 1},    {1, 4, 8},    {3, 5, 13},   {2, 33, 39}, {15, 32, 39}, {16, 32, 39}, {31, 64, 37},
+                                    {16, 33, 40}, {4, 32, 64},  {2, 7, 65},   {2, 4, 100}, {2, 4, 130}};
+    static const int kinds[][2] = {{0, 0}, {1, 0}, {2, 0}, {0, 1}, {1, 1}, {0, 2}, {0, 3}};      // {kind, mod}
+    std::vector<PackSet> sets;
+    for (const auto &sh : shapes)
+        for (const auto &km : kinds) {
+            if (km[0] == 1 && sh[0] < 2) continue;          // a UBM without copies is kind 0 again
+            if (km[0] == 2 && sh[1] < 2) continue;          // no order K / 2 below K = 2
+            if (km[1] == 3 && sh[0] * sh[1] < 2) continue;  // a lone mixture IS the centre
+            sets.push_back(PackSet{sh[0], sh[1], sh[2], km[0], km[1]});
+        }
+    return sets;
+}
+// the set of mode "threads": host_parallel_for goes threaded at pieces x cost >= 2^22 (64 pieces for pack_models, 5 blocks for
+// pack_models_h2_shared); its two rows stand at the end of the table
+static const PackSet kThreadedPackSet = {64, 2048, 39, 1, 0};
+
+static std::string pack_error(int which) {
+    try {
+        auto ms = make_plan_set(PlanSet{3, 5, 13, 0});
+        std::vector<const GMM *> v;
+        for (auto &g : ms) v.push_back(&g);
+        GMM other;
+        if (which == 0) ms[1] = GMM();
+        if (which == 1) other = make_plan_set(PlanSet{1, 5, 14, 0})[0], v[1] = &other;
+        if (which == 2) v.clear();
+        if (which == 3) (void)pick_padded_dim(MAX_DIM + 1);
+        else (void)pack_models(v);
+    } catch (const std::exception &e) {
+        return e.what();
+    }
+    return "(no error)";
+}
+
+static void print_double(double v) {
+    if (std::isinf(v)) printf("%sINFINITY", v < 0 ? "-" : "");
+    else printf("%.17g", v);
+}
+
+static int print_pack_table() {
+    auto sets = pack_sets();
+    printf("static const PackRow kPackRows[] = {\n");
+    size_t n_single = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1) sets.assign(1, kThreadedPackSet);
+        for (const PackSet &ps : sets)
+            for (const PackRow &r : pack_rows(ps, pass == 1)) {
+                printf("    {{%d, %d, %d, %d, %d}, %s, 0x%016llxull, {", ps.S, ps.K, ps.D, ps.kind, ps.mod, kPackLayoutNames[r.layout], r.hash);
+                for (int i = 0; i < 6; i++) printf("%s%lld", i ? ", " : "", r.iv[i]);
+                printf("}, {");
+                for (int i = 0; i < 8; i++) {
+                    if (std::isnan(r.dv[i])) return fprintf(stderr, "a NaN among the doubles of a row\n"), 1;
+                    printf("%s", i ? ", " : "");
+                    print_double(r.dv[i]);
+                }
+                printf("}},\n");
+                n_single += pass == 0;
+            }
+    }
+    printf("};\nstatic const size_t kPackSingleRows = %zu;       // the rows of mode \"pack\"; the rest belong to mode \"threads\"\n", n_single);
+    printf("static const PackError kPackErrors[] = {\n");
+    static const char *const what[4] = {"an untrained model", "a model of another dimension", "an empty set", "dimension MAX_DIM + 1"};
+    for (int i = 0; i < 4; i++) printf("    {\"%s\", \"%s\"},\n", what[i], pack_error(i).c_str());
+    printf("};\n");
+    return 0;
+}
+
+static bool same_double(double got, double want) {
+    if (std::isinf(want) || std::isinf(got)) return got == want;
+    return std::fabs(got - want) <= 1e-12 * std::max(std::fabs(got), std::fabs(want));     // (false for a NaN)
+}
+
+static int compare_pack_rows(const std::vector<PackRow> &got, const PackRow *want, size_t n_want) {
+    int bad = 0;
+    if (got.size() != n_want) return printf("pack: %zu rows, the table has %zu\n", got.size(), n_want), 1;
+    for (size_t i = 0; i < got.size(); i++) {
+        const PackRow &g = got[i], &w = want[i];
+        bool ok = std::memcmp(&g.set, &w.set, sizeof g.set) == 0 && g.layout == w.layout && g.hash == w.hash && std::memcmp(g.iv, w.iv, sizeof g.iv) == 0;
+        for (int d = 0; d < 8; d++) ok = ok && same_double(g.dv[d], w.dv[d]);
+        if (ok) continue;
+        bad++;
+        printf("pack row %zu (%d x %d x %d kind %d mod %d, %s): hash %016llx, ints {%lld, %lld, %lld, %lld, %lld, %lld}, doubles {", i, g.set.S, g.set.K,
+               g.set.D, g.set.kind, g.set.mod, kPackLayoutNames[g.layout], g.hash, g.iv[0], g.iv[1], g.iv[2], g.iv[3], g.iv[4], g.iv[5]);
+        for (int d = 0; d < 8; d++) printf("%s%.17g", d ? ", " : "", g.dv[d]);
+        printf("}; the table has %d x %d x %d kind %d mod %d, %s: hash %016llx, ints {%lld, %lld, %lld, %lld, %lld, %lld}, doubles {", w.set.S, w.set.K,
+               w.set.D, w.set.kind, w.set.mod, kPackLayoutNames[w.layout], w.hash, w.iv[0], w.iv[1], w.iv[2], w.iv[3], w.iv[4], w.iv[5]);
+        for (int d = 0; d < 8; d++) printf("%s%.17g", d ? ", " : "", w.dv[d]);
+        printf("}\n");
+    }
+    return bad;
+}
+
+static int check_pack() {
+    std::vector<PackRow> got;
+    for (const PackSet &ps : pack_sets())
+        for (const PackRow &r : pack_rows(ps)) got.push_back(r);
+    int bad = compare_pack_rows(got, kPackRows, kPackSingleRows);
+    for (int i = 0; i < 4; i++) {
+        const std::string e = pack_error(i);
+        if (e != kPackErrors[i].text) { printf("pack error of %s: '%s', want '%s'\n", kPackErrors[i].what, e.c_str(), kPackErrors[i].text); bad++; }
+    }
+    return bad;
+}
+
+static int check_pack_threaded() {
+    const size_t n_all = sizeof kPackRows / sizeof kPackRows[0];
+    return compare_pack_rows(pack_rows(kThreadedPackSet, true), kPackRows + kPackSingleRows, n_all - kPackSingleRows);
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "pack") == 0) {
+        if (argc > 2 && std::strcmp(argv[2], "print") == 0) return print_pack_table();
+        const int bad = check_pack();
+        if (bad) return printf("pack: %d rows differ\n", bad), 70;
+        printf("host checks ok\n");
+        return 0;
+    }
     if (argc > 1 && std::strcmp(argv[1], "mfcc") == 0) {
         const int bad = check_mfcc_plan();
         if (bad) return printf("mfcc plan: %d\n", bad), 90;
@@ -464,6 +701,7 @@ int main(int argc, char **argv) {
     const bool big = argc > 1 && std::strcmp(argv[1], "threads") == 0;     // sizes at which the packers go multi-threaded
     int rc = big ? check_packers(150, 1024, 39) : (check_packers(17, 37, 13) | check_packers(31, 64, 39));
     if (rc) return printf("packers: %d\n", rc), 10 + rc;
+    if (big && (rc = check_pack_threaded())) return printf("threaded pack: %d rows differ\n", rc), 70;
     if (!big) {
         if ((rc = check_tail_packing())) return printf("tail packing: %d\n", rc), 40 + rc;
         if ((rc = check_mel_starts())) return printf("mel starts: %d\n", rc), 60 + rc;

@@ -62,7 +62,7 @@ def test_text_format_host_side(built_lib, oracle_built, gmm_golden, tmp_path):
 
 
 def test_text_numbers_equal_libc(built_lib):
-    """The model text is written and read without printf / strtod (csrc/gmm_model.cpp fast_g6, fast_decimal): every number
+    """The model text is written and read without printf / strtod (csrc/model_text.cpp fast_g6, fast_decimal): every number
     must still come out as `out << v` (= "%g") writes it and go in as `in >> v` reads it -- checked against Python's own
     '%g' and float(), which are libc's, over magnitudes, rounding ties at the 7th digit and odd spellings."""
     from speaker_recognition_amd.pygmm import GMM

@@ -1,5 +1,5 @@
-"""csrc/gmm_model.cpp (text format, number conversions, every packer), csrc/score_plan.cpp (the dispatcher) and csrc/mfcc_plan.cpp (the MFCC
-stage's table layout and launch decisions) under AddressSanitizer + UBSan, and the threaded
+"""csrc/model_text.cpp (text format, number conversions), csrc/fp_parts.cpp and csrc/model_pack*.cpp (every packer), csrc/score_plan.cpp (the
+dispatcher) and csrc/mfcc_plan.cpp (the MFCC stage's table layout and launch decisions) under AddressSanitizer + UBSan, and the threaded
 packers under ThreadSanitizer: tests/host/host_checks.cpp, built here with g++ (host code only, no GPU, no HIP runtime).  The
 same for csrc/multi_plan.cpp (the multi-GPU predictor's sharding plan), by a program of its own: tests/host/multi_checks.cpp."""
 import os
@@ -12,8 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "speaker-recognition_amd", "csrc")
 
 
-def _build_and_run(tmp_path, flags, args, env=None, program="host_checks", sources=("gmm_model.cpp", "score_plan.cpp", "mfcc_plan.cpp"),
-                   ok="host checks ok"):
+HOST_CHECKS_SOURCES = ("model_text.cpp", "fp_parts.cpp", "model_pack.cpp", "model_pack_shared.cpp", "score_plan.cpp", "mfcc_plan.cpp")
+
+
+def _build_and_run(tmp_path, flags, args, env=None, program="host_checks", sources=HOST_CHECKS_SOURCES, ok="host checks ok"):
     exe = str(tmp_path / program)
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer", *flags, "-I", CSRC, "-I", "/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", os.path.join(ROOT, "tests", "host", program + ".cpp"), *[os.path.join(CSRC, s) for s in sources],
@@ -35,6 +37,15 @@ def test_score_plan_under_asan_ubsan(tmp_path):
     """The dispatcher's decisions (engine, shapes, model groups) on sets packed by the library's own pack_model_set, against the
     values recorded from the commit before the plan became a function of its own (tests/host/host_checks.cpp, mode "plan")."""
     _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], ["plan"],
+                   env={"ASAN_OPTIONS": "detect_leaks=1"})
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_packed_images_under_asan_ubsan(tmp_path):
+    """Every packer's image of small sets -- each layout, shared and independent sets, dead, negative-weight and zero-sigma mixtures --
+    and the packers' error texts, against the hashes and figures recorded from the commit before the packers were first touched
+    (tests/host/pack_table.inc; tests/host/host_checks.cpp, mode "pack")."""
+    _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], ["pack"],
                    env={"ASAN_OPTIONS": "detect_leaks=1"})
 
 
