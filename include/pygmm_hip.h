@@ -1175,6 +1175,58 @@ int sr_ahc_matrix(int64_t n, const double *dist, int linkage, double threshold, 
 int64_t sr_diar_cut(int64_t n, const int32_t *merge_i, const int32_t *merge_j, const double *merge_d, int64_t n_merges, double threshold,
                     int k_min, int k_max, int32_t *label_out, int64_t *n_merges_out);
 
+/* ---- Speaker embeddings from a neural network the caller brings: x-vector forward pass on the device (csrc/xvector.hip) ----
+ * A network is an ordered list of layers that ends at the embedding layer: frame layers (kind 0, tdnn: a dilated 1-D convolution
+ * over integer frame offsets), exactly one pooling layer (kind 1, stats_pool: mean and standard deviation over a segment's remaining
+ * frames), then segment layers (kind 2, affine).  A tdnn or affine layer computes  y = scale * act(W x_ctx + b) + shift  per channel
+ * (affine, activation, batch-norm: Kaldi's order; a batch-norm in front of the activation is folded into W and b by the caller, with
+ * scale and shift left out).  Valid convolution only: over a segment of T input frames output frame u is
+ * b + sum_j W_j x[u + o_j - o_1], u = 0 .. T - (o_m - o_1) - 1.
+ * Descriptor table: 16 int32 per layer {kind, c_in, c_out, act (0 none, 1 relu), 1 when scale and shift are given, number of offsets
+ * m, offsets[9], 0}; var_floor[n_layers] (read for the pooling layer); W[l]: float [c_out][m * c_in], offset-major; b, scale, shift[l]:
+ * float [c_out] (scale[l] and shift[l] NULL together, or the arrays themselves NULL).  Entries of a pooling layer are ignored.
+ * Arithmetic: weights are rounded once to bf16 (round to nearest even) by sr_xvector_create; features are fp32, rounded to bf16 by a
+ * convert kernel; every layer accumulates in fp32 on the bf16 matrix cores in an order that depends on the layer alone (offsets
+ * ascending, channels ascending inside an offset); the epilogue runs in fp32: z = acc + b, a = act(z), y = fma(scale, a, shift);
+ * activations are stored as bf16 (round to nearest even), the last layer and a tapped layer as fp32.  The pooling reads the bf16
+ * activations and sums x and x^2 in float64 in an order that depends on the segment's frame count alone (no atomics):
+ * std = sqrt(max(sum x^2 / n - mean^2, var_floor)); it writes [mean | std] as fp32.  A segment's embedding is the same bits alone,
+ * in any batch, at any position of a batch, under any "xvector_scratch_mib" and from run to run.
+ * sr_xvector_create needs no device (the weights go there with the first forward pass and stay).  sr_xvector_info writes 12 fields:
+ * layers, the pooling layer's index, input width, embedding width, context (frames consumed: a segment needs context + 1), the layer
+ * kernel's tile rows, tile columns, K per stage, channel granule, LDS bytes, workgroup size, the device the weights live on (-1: none yet).
+ * sr_xvector_plan: host only.  lengths[n_seg]: the segments' frames.  Writes 16 fields: tile rows, tile columns, K per stage, granule,
+ * context, embedding width, chunks, LDS bytes, the pooling layer's index, the last layer that runs, the result's rows and columns, the
+ * bytes of the two ping-ponged activation buffers, the largest chunk's bytes, the bound (scratch_bytes <= 0: the option
+ * "xvector_scratch_mib", 1 .. 2^20, default 1024).  Optional outputs: width_pad_out[n_layers + 1] the stages' padded widths;
+ * rows_out[(n_layers + 1) * n_seg] every segment's rows at every stage; chunk_begin_out[chunks + 1]; tile_count_out[n_layers * chunks];
+ * tiles_out[3 * tiles_cap]: layer tile_layer's tile list of chunk tile_chunk as (segment within the chunk, first output row, rows).
+ * A chunk is whole segments; a segment costs its two largest frame-level activations (they are ping-ponged) plus its rows of the
+ * segment-level stages and of the result.  Returns the number of chunks.
+ * sr_xvector_extract_batch: a resident feature batch; segs: NULL (one segment per utterance) or int32 [n_seg][3] (utterance, first
+ * frame, frames).  tap: -1 for the embeddings, fp32 [n_seg][E]; a layer's index for that layer's output instead: fp32 [sum of rows]
+ * [c_out] for a frame layer, [n_seg][2 C] for the pooling, [n_seg][c_out] for a segment layer.  tap_bf16 != 0: the tapped layer stores
+ * bf16 as it does inside the network and the result is those values widened.  out_cap: floats `out` holds.  times_ms_out: NULL or
+ * [n_layers + 1]: the device time of the convert kernels [0] and of every layer [1 + l] (the call's own events; no timer kind is added).
+ * sr_xvector_extract: the same from host rows X[n_rows][dim] and offsets[n_utt + 1].
+ * Refused, before the device is touched, with the remedy: widths outside 1 .. 4096; more than 9 offsets, an offset outside -16 .. 16,
+ * offsets that do not ascend; consecutive layers that disagree; no stats_pool, more than one, or none followed by an affine layer; a
+ * last layer whose act is not none; non-finite weights; non-finite host features; a feature width other than the first layer's; a
+ * segment outside its utterance or shorter than context + 1 (names the segment and the frames needed); a segment whose activations
+ * alone exceed the bound (names the bytes); a null argument; a process forked after the GPU runtime was initialised. */
+typedef struct SRXvector SRXvector;
+SRXvector *sr_xvector_create(int n_layers, const int32_t *desc, const double *var_floor, const float *const *W, const float *const *b,
+                             const float *const *scale, const float *const *shift);
+void sr_xvector_free(SRXvector *net);
+int sr_xvector_info(SRXvector *net, int32_t *out, int n_out);
+int sr_xvector_plan(int n_layers, const int32_t *desc, const double *var_floor, const int64_t *lengths, int64_t n_seg, int tap, int tap_bf16,
+                    int64_t scratch_bytes, int64_t *out, int n_out, int32_t *width_pad_out, int64_t *rows_out, int64_t *chunk_begin_out,
+                    int64_t *tile_count_out, int tile_layer, int64_t tile_chunk, int32_t *tiles_out, int64_t tiles_cap);
+int sr_xvector_extract_batch(SRXvector *net, SRBatch *features, const int32_t *segs, int64_t n_seg, int tap, int tap_bf16, float *out,
+                             int64_t out_cap, double *times_ms_out);
+int sr_xvector_extract(SRXvector *net, const float *X, int64_t n_rows, int dim, const int64_t *offsets, int n_utt, const int32_t *segs,
+                       int64_t n_seg, int tap, int tap_bf16, float *out, int64_t out_cap, double *times_ms_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,7 @@ EXT_SYMBOLS = [
     "sr_timeline_windows", "sr_timeline_plan", "sr_timeline_decide", "sr_timeline_batch", "sr_fullset_timeline_batch", "sr_timeline_pcm_batch",
     "sr_diar_segments", "sr_diar_plan", "sr_diar_stats_batch", "sr_diar_bic_matrix", "sr_diar_cluster_batch", "sr_diar_cluster_pcm_batch",
     "sr_ahc_matrix", "sr_diar_cut",
+    "sr_xvector_create", "sr_xvector_free", "sr_xvector_info", "sr_xvector_plan", "sr_xvector_extract_batch", "sr_xvector_extract",
 ]
 
 SR_CLAMP_COMPAT = 1
@@ -302,6 +303,13 @@ def lib():
         "sr_ahc_matrix": (i32, [i64, dp, i32, dbl, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, C.POINTER(i64), C.POINTER(C.c_int32),
                                 C.POINTER(i64)]),
         "sr_diar_cut": (i64, [i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, i64, dbl, i32, i32, C.POINTER(C.c_int32), C.POINTER(i64)]),
+        "sr_xvector_create": (vp, [i32, C.POINTER(C.c_int32), dp, C.POINTER(fp), C.POINTER(fp), C.POINTER(fp), C.POINTER(fp)]),
+        "sr_xvector_free": (None, [vp]),
+        "sr_xvector_info": (i32, [vp, C.POINTER(C.c_int32), i32]),
+        "sr_xvector_plan": (i32, [i32, C.POINTER(C.c_int32), dp, C.POINTER(i64), i64, i32, i32, i64, C.POINTER(i64), i32, C.POINTER(C.c_int32),
+                                  C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, i64, C.POINTER(C.c_int32), i64]),
+        "sr_xvector_extract_batch": (i32, [vp, vp, C.POINTER(C.c_int32), i64, i32, i32, fp, i64, dp]),
+        "sr_xvector_extract": (i32, [vp, fp, i64, i32, C.POINTER(i64), i32, C.POINTER(C.c_int32), i64, i32, i32, fp, i64, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

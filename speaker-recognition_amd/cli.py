@@ -34,7 +34,7 @@ def read_wav(fname):
 def get_args(argv=None):
     parser = argparse.ArgumentParser(description="Speaker Recognition Command Line Tool",
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
-    parser.add_argument("-t", "--task", help='Task to do: "enroll", "predict", "timeline" or "diarize"', required=True)
+    parser.add_argument("-t", "--task", help='Task to do: "enroll", "predict", "timeline", "diarize" or "embed"', required=True)
     parser.add_argument("-i", "--input", help="Input Files(to predict) or Directories(to enroll)", required=True)
     parser.add_argument("-m", "--model", help="Model file to save(in enroll) or use(in predict); diarize needs none", default=None)
     parser.add_argument("--mixtures", type=int, default=32, help="GMM order per speaker (default 32, gmmset.py:16)")
@@ -75,6 +75,7 @@ def get_args(argv=None):
     parser.add_argument("--rttm", default=None, help="diarize: also write the segments to this file in the RTTM format")
     parser.add_argument("--speakers", type=int, default=None, help="diarize: exactly this many speakers")
     parser.add_argument("--max-speakers", type=int, default=None, help="diarize: at most this many speakers")
+    parser.add_argument("--out", default=None, help="embed: the .npz to write (names, embeddings)")
     parser.add_argument("--penalty", type=float, default=1.0, help="diarize: the weight of the BIC penalty (default 1; larger: fewer speakers)")
     args = parser.parse_args(argv)
     if args.task != "diarize" and args.model is None:
@@ -86,6 +87,8 @@ def get_args(argv=None):
             parser.error("--%s must be >= 1" % name.replace("_", "-"))
     if not args.penalty > 0:
         parser.error("--penalty must be > 0")
+    if args.task == "embed" and args.out is None:
+        parser.error("embed needs --out")
     return args
 
 
@@ -232,6 +235,35 @@ def task_diarize(input_files, args):
     return out
 
 
+def task_embed(input_files, input_model, args):
+    """One embedding per input file through the network ``-m net.npz`` (xvector.XVector.save): writes ``names`` and ``embeddings``
+    [n, E] to ``--out``.  Features: MFCC (+ LPC-15 unless --no-lpc or --deltas, as the other tasks), per-utterance CMVN, and the
+    --win-length-ms / --win-shift-ms / --fft-size / --deltas / --feature-norm flags."""
+    import numpy as np
+
+    from .core import Batch, MfccExtractor
+    from .xvector import XVector
+    net = XVector.load(input_model)
+    files = sorted(glob.glob(os.path.expanduser(input_files)))
+    if not files:
+        print("No wav file found!")
+        sys.exit(1)
+    wavs = [read_wav(f) for f in files]
+    rates = sorted(set(fs for fs, _ in wavs))
+    if len(rates) != 1:
+        print("embed: the files have different sample rates (%s); embed them one rate at a time" % ", ".join(str(r) for r in rates))
+        sys.exit(2)
+    ex = MfccExtractor(rates[0], win_length_ms=args.win_length_ms, win_shift_ms=args.win_shift_ms, FFT_SIZE=args.fft_size,
+                       n_lpc=0 if args.no_lpc or args.deltas > 0 else 15)
+    emb = ex.embed_batch(net, Batch.from_pcm([sig for _, sig in wavs]), nd=args.deltas, norm=args.feature_norm,
+                         norm_window=301 if args.norm_window is None else args.norm_window)
+    with open(args.out, "wb") as fh:
+        np.savez(fh, names=np.asarray(files), embeddings=emb)
+    for f in files:
+        print(f)
+    return files, emb
+
+
 def _make_interface(args):
     if args is None:
         return ModelInterface()
@@ -260,8 +292,10 @@ def main(argv=None):
         task_timeline(args.input, args.model, args)
     elif args.task == "diarize":
         task_diarize(args.input, args)
+    elif args.task == "embed":
+        task_embed(args.input, args.model, args)
     else:
-        print('task must be "enroll", "predict", "timeline" or "diarize"')
+        print('task must be "enroll", "predict", "timeline", "diarize" or "embed"')
         sys.exit(2)
 
 

@@ -334,6 +334,12 @@ class MfccExtractor:
         out = Batch(h)
         return out if norm is None else out.normalise(norm, norm_window)
 
+    def embed_batch(self, net, pcm: Batch, nd: int = 0, cmvn: bool = True, norm=None, segments=None, norm_window: int = 301) -> np.ndarray:
+        """Speaker embeddings from resident PCM: ``extract_batch`` followed by ``net.extract`` (an ``xvector.XVector``), the features
+        never leaving the device; the bits of the two calls made one after the other.  ``segments``: as ``XVector.extract``, in
+        feature frames.  -> float32 [n, E]."""
+        return net.extract(self.extract_batch(pcm, nd, cmvn, norm, norm_window), segments=segments)
+
     def extract(self, signal, nd: int = 0, cmvn: bool = True) -> np.ndarray:
         """One utterance -> float64 [T - nd, n_ceps*(nd+1)] (what MFCCExtractor.extract returns,
         MFCC.py:49-79, plus optional deltas)."""

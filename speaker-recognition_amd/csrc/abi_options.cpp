@@ -27,6 +27,8 @@
 #include "silence_plan.hpp"
 #include "topc.hpp"
 #include "topc_plan.hpp"
+#include "xvector.hpp"
+#include "xvector_plan.hpp"
 
 #include <string>
 
@@ -128,6 +130,11 @@ int sr_set_option(const char *key, long value) {
         set_scratch_mib(key, value, DIAR_DEFAULT_SCRATCH, set_diar_scratch_mib);
     } else if (k == "plda_scratch_mib") {
         set_scratch_mib(key, value, PLDA_DEFAULT_SCRATCH, set_plda_scratch_mib);
+    } else if (k == "xvector_scratch_mib") {
+        set_scratch_mib(key, value, XV_DEFAULT_SCRATCH, set_xvector_scratch_mib);
+    } else if (k == "debug_xvector_mfma_shape") {
+        if (value != 0 && value != 1) fail("debug_xvector_mfma_shape must be 0 (v_mfma_f32_32x32x16_bf16, what the library runs) or 1 (v_mfma_f32_16x16x32_bf16)");
+        set_xvector_mfma_shape((int)value);                         // timing hook (scripts/time_xvector.py): the shape not chosen, kept to be measured against
     } else if (k == "jfa_lds_rows") {
         std::string why;
         if (!dense_check_lds_rows(value, why)) fail("%s rows", why.c_str());
